@@ -13,16 +13,20 @@ step-equivalents (408 forwards), hence
     latent-frames/s = 21 / (51 * sum over the 4 stages of that stage's mean step time)
                                                            (whole-job: summed over ranks, each rank = one chunk)
 
-Inputs (weights, KV caches, context, latents) are synthetic and resident in HBM before the timed region.
+Inputs (weights, KV caches, context, latents) are synthetic, seeded (identical from run to run for the same arguments) and
+resident in HBM before the timed region.  `--dump-outputs DIR` writes what the last timed step handed its caller (the stage's
+updated latents and both flow predictions; the last chunk's latents for the wavefront) as float32 DIR/<name>.npy.
 
 What is timed: by default every step is ONE hipGraph replay (both forwards + the fused CFG / UniPC update with its scalars
 in device tables: the north star's "hipGraph capture of one denoise step", exactly what
-mmpl_amd.pipeline.CausalFPSInferencePipeline replays 50 times per stage).  `--eager` times plain launches instead.  After
-the timed region one more rotation of the four stages runs eagerly with a hipEvent pair around every self-attention
-launch on the launch stream: that pass gives the `eager` figures printed beside the headline and the `roofline` object
-(per-kernel events cannot be recorded inside a graph replay; the kernels are the same binaries with the same arguments,
-and the rocprofv3 kernel trace of this command, profiles/, covers both passes).  `cpu_baseline` = the oracle (a CPU port)
-timed on a bounded sample: one transformer block per stage shape.
+mmpl_amd.pipeline.CausalFPSInferencePipeline replays 50 times per stage).  `--eager` times plain launches instead.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own: a same-run MFMA
+probe before the warm-up; after the timed region one more rotation of the four stages eagerly with a hipEvent pair around every
+self-attention launch on the launch stream: that pass gives the `eager` figures printed beside the headline and the `roofline`
+object (per-kernel events cannot be recorded inside a graph replay; the kernels are the same binaries with the same arguments,
+and the rocprofv3 kernel trace of this command, profiles/, covers both passes); the VAE decode of one chunk; and `cpu_baseline`
+= the oracle (a CPU port) timed on a bounded sample: one transformer block per stage shape.
 
 N > 1: one process per GPU, and the default line is a MEASUREMENT of the path the reference's multi-GPU scripts run: ONE video of
 C = 2 x lanes chunks through the real pipeline and the real dependency chain (chunk c on lane c % lanes, anchors handed lane ->
@@ -73,12 +77,17 @@ def parse():
     ap.add_argument("--i2v-model", action="store_true",
                     help="Wan-I2V MODEL TYPE (in_dim 36 + the CLIP image stream in every block's cross-attention, model.py:563-616) instead of the "
                          "T2V backbone the reference's I2V scripts run; synthetic CLIP features; not the headline workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="disable the per-kernel hipEvent pairs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: MFMA probe, per-kernel hipEvent pairs (`eager`, `roofline`), VAE decode, "
+                         "CPU baseline (the --no-* switches below leave one of them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (float32 DIR/<name>.npy) after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: disable the per-kernel hipEvent pairs")
     ap.add_argument("--profile-all", action="store_true",
-                    help="time every kernel class (adds gemm_tflops / kernel_time_share; ~0.5-1 %% slower than the default, "
+                    help="with --full: time every kernel class (adds gemm_tflops / kernel_time_share; ~0.5-1 %% slower than the default, "
                          "which times the roofline kernel -- self-attention -- only)")
-    ap.add_argument("--no-vae", action="store_true", help="skip the (untimed-region) VAE decode measurement")
+    ap.add_argument("--no-vae", action="store_true", help="with --full: skip the (untimed-region) VAE decode measurement")
     ap.add_argument("--cfg-split", action="store_true",
                     help="N/2 chunk lanes x (cond, uncond) rank pairs exchanging flow predictions every step "
                          "(the reference's device_cond/device_uncond seam) instead of N chunk lanes; default from 4 ranks on")
@@ -103,8 +112,8 @@ def parse():
     ap.add_argument("--rotation", action="store_true", help="N > 1: the K-rotating-steps line (occupancy MODEL for `value`) instead of the measured wavefront")
     ap.add_argument("--attn-stats", action="store_true", help="count the self-attention blocks the FAST softmax pass could not hold (one atomic per "
                          "256-row block inside the timed region; always on with --heavy-tail)")
-    ap.add_argument("--probe-seconds", type=float, default=1.5, help="same-run calibration: seconds of back-to-back MFMAs per instruction shape right "
-                         "before the warm-up (0 = skip)")
+    ap.add_argument("--probe-seconds", type=float, default=1.5, help="with --full, same-run calibration: seconds of back-to-back MFMAs per instruction "
+                         "shape right before the warm-up (0 = skip)")
     ap.add_argument("--heavy-tail-gain", type=float, default=8.0, help="QK-norm gain multiplier of --heavy-tail (8 = the test's; logit std ~ gain^2 nats)")
     ap.add_argument("--heavy-tail", action="store_true",
                     help="NOT the headline: the statistics real checkpoints have and unit-variance synthetic weights do not (QK-norm gains x8, "
@@ -116,7 +125,20 @@ def parse():
     ap.add_argument("--no-attn-history", action="store_true",
                     help="A/B: stateless self-attention (no per-block pass history; every block whose FAST pass fails pays for both passes every step)")
     ap.add_argument("--cpu-budget-s", type=float, default=150.0, help="stop adding stage shapes to the CPU baseline after this many seconds")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.profile_all and not args.full:
+        ap.error("--profile-all needs --full (per-kernel timing is not part of a plain run)")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> tensor) as float32 out_dir/<name>.npy, at most 64 MB in all."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in host.values()) <= 64 << 20, {k: a.shape for k, a in host.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def cpu_baseline(cfg, lat_h, lat_w, stage_shapes, budget_s):
@@ -262,7 +284,7 @@ def run_wavefront(args, dist, rank, world, dev, gloo):
         args.sampling_steps = max(2, min(50, k)) if world > 1 else 50
     pipe.sampling_steps = args.sampling_steps
     torch.cuda.synchronize()
-    marks = {}
+    marks, last = {}, {}
 
     def make_chunk(c, initial, sink):
         m = marks.setdefault(c, {})
@@ -277,6 +299,7 @@ def run_wavefront(args, dist, rank, world, dev, gloo):
         _, lat_c = pipe.inference(noises[c].to(dev), ["a cat running on the grass"], initial_latent=initial, return_latents=True, decode=False)
         torch.cuda.synchronize()
         m["t_end"] = time.time()
+        last["latents"] = lat_c
         return lat_c
 
     def to_initial(recv):
@@ -302,6 +325,8 @@ def run_wavefront(args, dist, rank, world, dev, gloo):
                             initial_like=torch.empty([1, 2, 16, lat_h, lat_w], device=dev, dtype=torch.bfloat16))
     barrier()
     wall = time.time() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)               # this rank's last chunk (the video's last one on one rank)
     mine = {"rank": rank, "marks": marks, "handoff": (ho.stats if ho is not None else {}), "t0": t0}
     everyone = [mine]
     if dist is not None and world > 1:
@@ -384,7 +409,7 @@ def run_wavefront(args, dist, rank, world, dev, gloo):
            "handoff_latency_note": "recv complete - max(anchors available on the producer, consumer ready): RCCL p2p + header (+ host staging under gloo)",
            "producer_waited_for_consumer_s": {str(c): v for c, v in sorted(wait_ho.items())},
            "achieved_pflops_all_gpus": flops / wall / 1e15}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline(cfg, lat_h, lat_w, T2V_STAGE_SHAPES, args.cpu_budget_s)
         except Exception as e:  # the baseline is a reported extra; never lose the GPU measurement over it
@@ -421,6 +446,7 @@ def main():
     gloo = dist is not None and args.dist_backend == "gloo"
     torch.cuda.set_device(local_rank)
     dev = torch.device(f"cuda:{local_rank}")
+    torch.manual_seed(0)                   # the synthetic caches, contexts and latents: the same inputs in every run with these arguments
     if args.wavefront_chunks > 0 or (world > 1 and not args.rotation):
         run_wavefront(args, dist, rank, world, dev, gloo)
         if dist is not None:
@@ -652,7 +678,7 @@ def main():
     # same-run calibration of THIS box: what it sustains on nothing but MFMAs (random operands), per instruction shape, right before
     # the warm-up steps (which bring clocks / power back to the workload's own steady state before the timed region)
     probe = None
-    if args.probe_seconds > 0:
+    if args.full and args.probe_seconds > 0:
         probe = {}
         torch.cuda.synchronize()
         for shape, name in ((32, "v_mfma_f32_32x32x16_bf16"), (16, "v_mfma_f32_16x16x32_bf16")):
@@ -666,7 +692,8 @@ def main():
         pair.exchange(stage_state[0]["mine"], stage_state[0]["flow"])
     torch.cuda.current_stream().wait_stream(side)
     barrier()
-    if not args.no_profile and not graphed:
+    profile = args.full and not args.no_profile
+    if profile and not graphed:
         lib.mmpl_profile_enable(1 if args.profile_all else ((1 << 1) << 1))      # default: kind 1 = self-attention only
     # the K timed steps keep rotating through the four stage shapes; every step is also bracketed by a HIP event pair so
     # that the chunk time can be assembled per stage (exact for any K, not only multiples of 4)
@@ -684,16 +711,19 @@ def main():
     elapsed = time.perf_counter() - t0
     step_s = [e0.elapsed_time(e1) * 1e-3 for e0, e1 in ev]
     attn_blocks, attn_redone, attn_waves_bad, attn_predicted, attn_remembered = eng.read_attn_stats() if attn_stats is not None else (None,) * 5   # of the timed region (graph replays included)
-    # ---- eager pass (after the timed region when that one replayed graphs): one rotation of the four stages with a hipEvent
+    if args.dump_outputs and rank == 0:
+        st = stage_state[(args.warmup + args.steps - 1) % 4]          # the last timed step's stage: its updated latents and both flows
+        dump_outputs(args.dump_outputs, {"latents": st["lat"], "flow_cond": st["fc"], "flow_uncond": st["fu"]})
+    # ---- eager pass (--full, after the timed region when that one replayed graphs): one rotation of the four stages with a hipEvent
     # pair around every self-attention launch (all kernel classes with --profile-all) -> `eager` figures and `roofline`
     eager_step_s = None
-    if graphed:
+    if graphed and args.full:
         for st in stage_state:
             st["sched"].set_timesteps(50, shift=5.0)
         for i in range(4):
             one_step(i, eager=True)                         # untimed: eager launch path warm
         torch.cuda.synchronize()
-        if not args.no_profile:
+        if profile:
             lib.mmpl_profile_enable(1 if args.profile_all else ((1 << 1) << 1))
         n_eager = 8
         eev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_eager)]
@@ -704,14 +734,14 @@ def main():
         torch.cuda.synchronize()
         eager_step_s = [e0.elapsed_time(e1) * 1e-3 for e0, e1 in eev]
     prof = None
-    if not args.no_profile:
+    if profile:
         n = len(KIND_NAMES)
         ms, fl, cnt = (C.c_double * n)(), (C.c_double * n)(), (C.c_longlong * n)()
         lib.mmpl_profile_read(n, ms, fl, cnt)
         lib.mmpl_profile_enable(0)
         prof = {KIND_NAMES[k]: dict(ms=ms[k], flops=fl[k], launches=int(cnt[k])) for k in range(n) if cnt[k]}
     vae_s = None
-    if rank == 0 and not args.no_vae:
+    if rank == 0 and args.full and not args.no_vae:
         # Wan 3D-VAE decode of one 21-latent-frame chunk (reported separately from the DiT metric)
         try:
             from mmpl_amd.synthetic import vae_state_dict
@@ -869,7 +899,7 @@ def main():
                                    "achieved": vfl / vae_s / 1e12, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                                    "frac": vfl / vae_s / 1e12 / MFMA_PEAK_TFLOPS, "algorithmic_flops": vfl, "seconds": vae_s,
                                    "note": "reported beside the DiT metric, not part of `value` (0.35 % of a chunk)"}
-        if not args.no_cpu_baseline:           # rank 0 only (this branch), whatever the world size
+        if args.full and not args.no_cpu_baseline:           # rank 0 only (this branch), whatever the world size
             try:
                 res["cpu_baseline"] = cpu_baseline(cfg, lat_h, lat_w, stage_shapes, args.cpu_budget_s)
             except Exception as e:  # the baseline is a reported extra; never lose the GPU measurement over it

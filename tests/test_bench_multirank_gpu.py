@@ -28,7 +28,7 @@ def _scale_to_50(k, n_chunks, model="tiny", lat=(16, 24)):
 def _run(extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--model", "small", "--res", "tiny",
-           "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-vae"] + extra
+           "--steps", "8", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-vae"] + extra
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -158,7 +158,7 @@ def test_single_gpu_bench_line_fields_and_heavy_tail_switches():
     diagnostic switches of the self-attention's pass history (`--heavy-tail [--heavy-tail-heads P]`, `--no-attn-history`): the counters
     add up, and without the history nothing is predicted or remembered."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--model", "small", "--res", "tiny", "--steps", "12", "--warmup", "4", "--no-cpu-baseline", "--no-vae",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--model", "small", "--res", "tiny", "--steps", "12", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-vae",
             "--probe-seconds", "0"]
 
     def run(extra):
@@ -180,3 +180,30 @@ def test_single_gpu_bench_line_fields_and_heavy_tail_switches():
     n = run(["--heavy-tail", "--heavy-tail-gain", "12", "--heavy-tail-heads", "0.5", "--no-attn-history"])
     assert n["attn_history"].startswith("off") and n["attn_blocks_predicted"] == 0 and n["attn_blocks_fast_on_remembered_reference"] == 0
     assert n["attn_blocks_redone"] >= h["attn_blocks_redone"]           # with the history a failing block does not keep paying twice
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain one-rank run (no --full) times exactly --steps steps and prints the headline without the measurements that take runs
+    of their own (probe, per-kernel eager pass, VAE decode, CPU baseline); `--dump-outputs` writes what the last timed step computed,
+    and two runs with the same arguments write the same arrays (seeded inputs, identical launch sequences)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "small", "--res", "tiny", "--steps", "5", "--warmup", "2",
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["metric"] == "video_latent_frames_per_sec" and r["value"] > 0 and r["unit"] == "latent-frames/s" and r["higher_is_better"] is True
+        assert r["dtype"] == "bf16" and r["steps"] == 5 and r["ms_per_step"] > 0
+        assert not {"roofline", "eager", "cpu_baseline", "vae_roofline", "gemm_tflops", "kernel_time_share"} & set(r)
+        assert r["vae_decode_s_per_chunk"] is None
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("latents", "flow_cond", "flow_uncond")})
+    # 2 warm-up + 5 timed steps rotate s0..s3: the last timed step is stage s2 (6 query frames of 16 x 24 latents)
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.shape == (6, 16, 16, 24) and np.isfinite(a).all() and a.any(), n
+        assert np.array_equal(a, dumps[1][n]), n

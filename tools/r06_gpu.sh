@@ -33,13 +33,13 @@ for spec in "$@"; do
       timeout 2400 python -m pytest $arg -m gpu -q -s > $out/tests$n.log 2>&1; echo "rc=$? ($arg)" >> $out/tests$n.log
       grep -E "passed|failed|rc=|Error|error|rel|redo|408 forwards|chunk" $out/tests$n.log | tail -40 ;;
     bench)
-      python bench.py > $out/bench_14B_720p.json 2> $out/bench.err; line $out/bench_14B_720p.json default ;;
+      python bench.py --full > $out/bench_14B_720p.json 2> $out/bench.err; line $out/bench_14B_720p.json default ;;
     profall)
-      python bench.py $SHORT --profile-all > $out/bench_14B_720p_profile_all.json 2>> $out/bench.err; line $out/bench_14B_720p_profile_all.json profile-all ;;
+      python bench.py --full $SHORT --profile-all > $out/bench_14B_720p_profile_all.json 2>> $out/bench.err; line $out/bench_14B_720p_profile_all.json profile-all ;;
     bench13)
-      python bench.py --model 1.3B --res 480p --no-cpu-baseline --profile-all > $out/bench_1p3B_480p.json 2>> $out/bench.err; line $out/bench_1p3B_480p.json 1.3B/480p ;;
+      python bench.py --full --model 1.3B --res 480p --no-cpu-baseline --profile-all > $out/bench_1p3B_480p.json 2>> $out/bench.err; line $out/bench_1p3B_480p.json 1.3B/480p ;;
     bench480)
-      python bench.py --res 480p $SHORT > $out/bench_14B_480p.json 2>> $out/bench.err; line $out/bench_14B_480p.json 14B/480p ;;
+      python bench.py --full --res 480p $SHORT > $out/bench_14B_480p.json 2>> $out/bench.err; line $out/bench_14B_480p.json 14B/480p ;;
     chunk)
       python tools/full_chunk.py > $out/full_chunk_14B_720p.json 2>> $out/bench.err; tail -c 600 $out/full_chunk_14B_720p.json ;;
     chunk13)
@@ -48,24 +48,24 @@ for spec in "$@"; do
                  # history on / off alternating on ONE box
       for w in "" "--heavy-tail" "--heavy-tail --heavy-tail-heads 0.15"; do
         for h in "" "--no-attn-history" "" "--no-attn-history"; do
-          python bench.py $SHORT --attn-stats $w $h > $out/hist_tmp.json 2>> $out/bench.err; line $out/hist_tmp.json "[$w] [$h]" >> $out/attn_history_ab.log
+          python bench.py --full $SHORT --attn-stats $w $h > $out/hist_tmp.json 2>> $out/bench.err; line $out/hist_tmp.json "[$w] [$h]" >> $out/attn_history_ab.log
         done
       done; cat $out/attn_history_ab.log ;;
     ht)          # the heavy-tail lines kept under profiles/: x3, x8, x8 on 15 % of the heads (20 steps like the default line)
-      python bench.py --no-cpu-baseline --no-vae --heavy-tail --heavy-tail-gain 3 > $out/bench_14B_720p_heavy_tail_x3.json 2>> $out/bench.err; line $out/bench_14B_720p_heavy_tail_x3.json x3
-      python bench.py --no-cpu-baseline --no-vae --heavy-tail > $out/bench_14B_720p_heavy_tail_x8.json 2>> $out/bench.err; line $out/bench_14B_720p_heavy_tail_x8.json x8
-      python bench.py --no-cpu-baseline --no-vae --heavy-tail --heavy-tail-heads 0.15 > $out/bench_14B_720p_heavy_tail_x8_p15.json 2>> $out/bench.err; line $out/bench_14B_720p_heavy_tail_x8_p15.json "x8 p=0.15" ;;
+      python bench.py --full --no-cpu-baseline --no-vae --heavy-tail --heavy-tail-gain 3 > $out/bench_14B_720p_heavy_tail_x3.json 2>> $out/bench.err; line $out/bench_14B_720p_heavy_tail_x3.json x3
+      python bench.py --full --no-cpu-baseline --no-vae --heavy-tail > $out/bench_14B_720p_heavy_tail_x8.json 2>> $out/bench.err; line $out/bench_14B_720p_heavy_tail_x8.json x8
+      python bench.py --full --no-cpu-baseline --no-vae --heavy-tail --heavy-tail-heads 0.15 > $out/bench_14B_720p_heavy_tail_x8_p15.json 2>> $out/bench.err; line $out/bench_14B_720p_heavy_tail_x8_p15.json "x8 p=0.15" ;;
     htlong)      # heavy tail x8 over 40 timed steps (every stage replayed 12 times): the history's steady state, on / off
       for h in "" "--no-attn-history"; do
-        python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-vae --heavy-tail $h > $out/htlong_tmp.json 2>> $out/bench.err; line $out/htlong_tmp.json "x8, 40 steps [$h]" >> $out/heavy_tail_x8_40_steps.log
+        python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-vae --heavy-tail $h > $out/htlong_tmp.json 2>> $out/bench.err; line $out/htlong_tmp.json "x8, 40 steps [$h]" >> $out/heavy_tail_x8_40_steps.log
       done; cat $out/heavy_tail_x8_40_steps.log ;;
     i2vmodel)
-      python bench.py $SHORT --i2v-model > $out/bench_i2v_model_type_14B_720p.json 2>> $out/bench.err; line $out/bench_i2v_model_type_14B_720p.json "Wan-I2V model type 14B/720p" ;;
+      python bench.py --full $SHORT --i2v-model > $out/bench_i2v_model_type_14B_720p.json 2>> $out/bench.err; line $out/bench_i2v_model_type_14B_720p.json "Wan-I2V model type 14B/720p" ;;
     insitu)      # two PREBUILT libraries alternating in situ (tools/build/libmmpl_hip_{prev,new}.so): 14B / 720p --profile-all and 1.3B / 480p
       for v in prev new prev new; do
         cp tools/build/libmmpl_hip_$v.so mmpl_amd/lib/libmmpl_hip.so
-        python bench.py $SHORT --profile-all $arg > $out/is_tmp.json 2>> $out/bench.err; line $out/is_tmp.json "14B/720p [lib=$v]" >> $out/insitu_ab.log
-        python bench.py --model 1.3B --res 480p --steps 16 --warmup 8 --no-cpu-baseline --no-vae $arg > $out/is_tmp.json 2>> $out/bench.err; line $out/is_tmp.json "1.3B/480p [lib=$v]" >> $out/insitu_ab.log
+        python bench.py --full $SHORT --profile-all $arg > $out/is_tmp.json 2>> $out/bench.err; line $out/is_tmp.json "14B/720p [lib=$v]" >> $out/insitu_ab.log
+        python bench.py --full --model 1.3B --res 480p --steps 16 --warmup 8 --no-cpu-baseline --no-vae $arg > $out/is_tmp.json 2>> $out/bench.err; line $out/is_tmp.json "1.3B/480p [lib=$v]" >> $out/insitu_ab.log
       done
       cp tools/build/libmmpl_hip_new.so mmpl_amd/lib/libmmpl_hip.so; cat $out/insitu_ab.log ;;
     attnhash)    # do two PREBUILT libraries compute the same self-attention bits (stateless launches)?
@@ -95,18 +95,18 @@ for spec in "$@"; do
       done
       python3 tools/profiles_post.py $out $tag tcc; cat $out/${tag}_pmc_gemm_l2.md ;;
     stats)       # rocprofv3 kernel stats of the bench command itself
-      timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o b -- python3 bench.py $SHORT > $out/bench_under_rocprof.json 2> $out/stats.err
+      timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o b -- python3 bench.py --full $SHORT > $out/bench_under_rocprof.json 2> $out/stats.err
       python3 tools/profiles_post.py $out $tag; head -12 $out/${tag}_kernel_stats.csv ;;
     hbm)         # FETCH_SIZE / WRITE_SIZE in separate passes over bench.py itself (MI355X_MICROARCH.md, HBM / rocprofv3 section)
       for ctr in FETCH_SIZE WRITE_SIZE; do
-        timeout -k 10 900 rocprofv3 --kernel-trace --output-format csv --pmc $ctr -d $out/hbm_$ctr -o p -- python3 bench.py --steps 4 --warmup 0 --no-cpu-baseline --no-vae --no-profile --eager > $out/hbm_$ctr.json 2> $out/hbm_$ctr.err
+        timeout -k 10 900 rocprofv3 --kernel-trace --output-format csv --pmc $ctr -d $out/hbm_$ctr -o p -- python3 bench.py --full --steps 4 --warmup 0 --no-cpu-baseline --no-vae --no-profile --eager > $out/hbm_$ctr.json 2> $out/hbm_$ctr.err
       done
       python3 tools/profiles_post.py $out $tag; cat $out/${tag}_pmc_attention_hbm.json ;;
     busy)
-      timeout -k 10 900 rocprofv3 --kernel-trace --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d $out/busy -o p -- python3 bench.py --steps 4 --warmup 0 --no-cpu-baseline --no-vae --no-profile > $out/busy_bench.json 2> $out/busy.err
+      timeout -k 10 900 rocprofv3 --kernel-trace --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d $out/busy -o p -- python3 bench.py --full --steps 4 --warmup 0 --no-cpu-baseline --no-vae --no-profile > $out/busy_bench.json 2> $out/busy.err
       python3 tools/profiles_post.py $out $tag; cat $out/${tag}_pmc_mfma_busy.md ;;
     n2)          # the default N = 2 line (measured wavefront; gloo: both ranks on this one GPU -- functional only)
-      timeout 1500 python bench.py --gpus 2 --dist-backend gloo --model 1.3B --res 480p > $out/bench_default_n2_gloo_1p3B_480p.json 2>> $out/bench.err; tail -c 1500 $out/bench_default_n2_gloo_1p3B_480p.json ;;
+      timeout 1500 python bench.py --full --gpus 2 --dist-backend gloo --model 1.3B --res 480p > $out/bench_default_n2_gloo_1p3B_480p.json 2>> $out/bench.err; tail -c 1500 $out/bench_default_n2_gloo_1p3B_480p.json ;;
     *) echo "unknown step $step" ;;
   esac
   rm -f gpucore.* core.* /tmp/gpucore.* /tmp/core.* 2>/dev/null
