@@ -219,6 +219,16 @@ int mmpl_cfg_unipc_step_table(const void* flow_cond, const void* flow_uncond, vo
                               size_t n, const MmplUniPCStep* table_dev, int* step_dev, float* timestep_dev,
                               const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream);
 
+/* Few-step (Self-Forcing / CausVid) latent update of CausalInferencePipeline.inference (pipeline/causal_inference.py:176-197):
+ * WanDiffusionWrapper._convert_flow_pred_to_x0 (utils/wan_wrapper.py:172-199) then FlowMatchScheduler.add_noise
+ * (utils/scheduler.py:160-176), per element of n bf16 values:
+ *   x0_out = bf16(float(double(x) - sigma_t * double(flow)))                       (the reference's fp64 chain)
+ *   x      = bf16(fp32(fp32(1 - sigma_next) * x0) + fp32(sigma_next * noise))    only if noise != NULL (fp32 rounding per op)
+ * flow / x / noise / x0_out: dev bf16 [n]; x0_out may point into the middle of a larger latent (any alignment: 16-byte aligned
+ * operands take the vector path).  No host read-back, no allocation: capturable. */
+int mmpl_fewstep_update(const void* flow, void* x, const void* noise, void* x0_out, size_t n, double sigma_t, float sigma_next,
+                        mmpl_stream_t stream);
+
 /* ---- Wan 3D causal VAE (wan/modules/vae.py:483-569 behind WanVAEWrapper, utils/wan_wrapper.py:54-113) ----
  * Weights: mmpl_vae_num_weights() dev pointers in the order of mmpl_vae_weight_name(i): the reference's state_dict keys, conv
  * weights repacked host-side to [Cout, taps * Cin] (tap-major, Cin contiguous; Cin 3/16 zero-padded to 32, decoder.head Cout

@@ -36,6 +36,52 @@ def load_config(path):
     return types.SimpleNamespace(**cfg)
 
 
+def is_fewstep(config) -> bool:
+    """Wan_fps_inference_1gpu.py:59-64: a config with `denoising_step_list` is a few-step (Self-Forcing / CausVid) checkpoint."""
+    return hasattr(config, "denoising_step_list")
+
+
+def pipeline_class(config):
+    """The pipeline the reference's entry script builds for `config` (Wan_fps_inference_1gpu.py:59-64)."""
+    from .pipeline import CausalFPSInferencePipeline, CausalInferencePipeline
+    return CausalInferencePipeline if is_fewstep(config) else CausalFPSInferencePipeline
+
+
+def fewstep_refusal(args, world: int):
+    """Why the few-step pipeline cannot run this command line (None = it can).  The reference's rollout loop feeds 2 overlap
+    latent frames back and trips `num_input_frames % num_frame_per_block == 0` from rollout 2 on (causal_inference.py:153);
+    its I2V image latent is 1 frame; it has no multi-rank few-step path."""
+    if args.duration > 1:
+        return (f"--duration {args.duration}: the few-step pipeline (config with denoising_step_list) generates one "
+                f"{args.num_output_frames}-latent-frame call; longer rollouts are not supported (use --duration 1)")
+    if args.i2v or args.i2v_model:
+        return "--i2v: the few-step pipeline (config with denoising_step_list) is text-to-video only"
+    if world > 1:
+        return "the few-step pipeline (config with denoising_step_list) runs on one process (WORLD_SIZE 1)"
+    return None
+
+
+def build_fewstep_pipeline(config, args, dev, geo, mcfg):
+    """WanDiffusionWrapper + CausalInferencePipeline (Wan_fps_inference_1gpu.py:61), then `independent_first_frame = False`
+    as the entry script sets it (:73)."""
+    from .pipeline import CausalInferencePipeline
+    from .wan_wrapper import SyntheticTextEncoder, WanDiffusionWrapper, WanVAEWrapper
+    kw = dict(getattr(config, "model_kwargs", {}) or {})
+    gen = WanDiffusionWrapper("Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B", **kw, is_causal=True,
+                              model_config=mcfg if args.synthetic else None, geometry=geo, device=dev)
+    enc, vae = None, None
+    if args.synthetic:
+        gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
+        enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
+        vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
+    pipe = CausalInferencePipeline(config, dev, generator=gen, text_encoder=enc, vae=vae)
+    if args.checkpoint_path:
+        from .checkpoints import read_mmpl_checkpoint
+        pipe.generator.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
+    pipe.independent_first_frame = False
+    return pipe
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", type=str)
@@ -67,6 +113,12 @@ def main(argv=None):
 
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    config = load_config(args.config_path)
+    fewstep = is_fewstep(config)
+    if fewstep:
+        why = fewstep_refusal(args, world)
+        if why is not None:
+            ap.error(why)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.dist_backend == "gloo":
         local_rank %= max(torch.cuda.device_count(), 1)
@@ -82,10 +134,11 @@ def main(argv=None):
 
     from .pipeline import CausalFPSInferencePipeline
     from .wan_wrapper import SyntheticTextEncoder, WanFPSWrapper, WanVAEWrapper
-    config = load_config(args.config_path)
-    config.sampling_steps = args.sampling_steps
     geo = Geometry(*args.latent_hw) if args.latent_hw else Geometry.named(args.resolution)
     mcfg = WAN_CONFIGS[args.model]
+    if fewstep:
+        return _main_fewstep(config, args, dev, geo, mcfg)
+    config.sampling_steps = args.sampling_steps
     clip = None
     if args.i2v_model:
         if not (args.i2v and args.image):
@@ -206,6 +259,32 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def _prompts(args):
+    if args.data_path:
+        from .utils.dataset import TextDataset
+        ds = TextDataset(args.data_path)
+        return [ds[i]["prompts"] for i in range(len(ds))]
+    return ["a cat running on the grass"]
+
+
+def _main_fewstep(config, args, dev, geo, mcfg):
+    """Wan_fps_inference_1gpu.py with a few-step config: one CausalInferencePipeline.inference per prompt."""
+    pipe = build_fewstep_pipeline(config, args, dev, geo, mcfg)
+    os.makedirs(args.output_folder, exist_ok=True)
+    shape = [1, args.num_output_frames, 16, geo.lat_h, geo.lat_w]
+    for idx, prompt in enumerate(_prompts(args)):
+        g = torch.Generator(device="cpu").manual_seed(args.seed)
+        noise = torch.randn(shape, generator=g).to(torch.bfloat16)
+        torch.manual_seed(args.seed)                         # the re-noise draws: the device generator (set_seed, :44-49)
+        video = pipe.inference(noise.to(dev), [prompt], return_latents=False)
+        out = (video * 255.0).clamp(0, 255).to(torch.uint8)[0].permute(0, 2, 3, 1).contiguous().cpu()     # [T, H, W, 3]
+        path = os.path.join(args.output_folder, f"{idx}-0.pt")
+        torch.save(out, path)
+        from .utils.video_io import write_video
+        vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)
+        print(f"[mmpl_amd.cli] few-step prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
 
 
 if __name__ == "__main__":

@@ -1,0 +1,261 @@
+"""``CausalInferencePipeline`` -- drop-in for MMPL_t2v/pipeline/causal_inference.py: few-step, block-causal inference
+(Self-Forcing / CausVid checkpoints, configs/self_forcing_{dmd,sid}.yaml) with the denoising loop on the HIP engines.
+
+Same constructor / ``inference()`` signature and attributes (``generator``, ``text_encoder``, ``vae``, ``scheduler``,
+``denoising_step_list``, ``num_frame_per_block``, ``independent_first_frame``, ``local_attn_size``, ``kv_cache1``,
+``crossattn_cache``) and the same semantics: warped step list, ``[1] + [3] * k`` block schedule, both ``initial_latent``
+branches, ``context_noise`` refresh forward, caches reset per call, ``decode_to_pixel`` then ``(x * 0.5 + 0.5).clamp(0, 1)``.
+What changed underneath:
+  * a block = ``n`` DiT forwards (``mmpl_dit_forward`` on explicit KV slots) + ``n - 1`` fused x0 / re-noise updates
+    (``mmpl_fewstep_update``) + the final x0 write into the output latent + the refresh forward, and with ``use_graphs`` all of
+    it is ONE hipGraph per block, captured on first use and replayed by every later ``inference()`` call
+    (``release_graphs()`` drops them);
+  * the re-noise draws (``torch.randn_like`` per non-final step) are drawn before the block, in the reference's order and shape,
+    into a static bank the graph reads: the same device generator state gives the reference's draws bit for bit;
+  * the literals 30 / 12 / 1560 / 32760 come from the model config and the ``Geometry``.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional
+
+import torch
+
+from ..wan_wrapper import WanDiffusionWrapper, WanTextEncoder, WanVAEWrapper
+
+
+class CausalInferencePipeline(torch.nn.Module):
+    def __init__(self, args, device, generator=None, text_encoder=None, vae=None):
+        super().__init__()
+        self.device = torch.device(device)
+        self.generator = WanDiffusionWrapper(**getattr(args, "model_kwargs", {}), is_causal=True,
+                                             device=device) if generator is None else generator
+        self.geometry = self.generator.geometry
+        self.text_encoder = WanTextEncoder(device=device) if text_encoder is None else text_encoder
+        self.vae = WanVAEWrapper(geometry=self.geometry, device=device) if vae is None else vae
+
+        self.scheduler = self.generator.get_scheduler()
+        self.denoising_step_list = torch.tensor(args.denoising_step_list, dtype=torch.long)
+        if getattr(args, "warp_denoising_step", False):                  # causal_inference.py:29-31
+            timesteps = torch.cat((self.scheduler.timesteps.cpu(), torch.tensor([0], dtype=torch.float32)))
+            self.denoising_step_list = timesteps[len(self.scheduler.timesteps) - self.denoising_step_list]
+
+        self.num_transformer_blocks = self.generator.engine.L
+        self.frame_seq_length = self.geometry.frame_seqlen
+
+        self.kv_cache1 = None
+        self.crossattn_cache = None
+        self.args = args
+        self.num_frame_per_block = getattr(args, "num_frame_per_block", 1)
+        self.independent_first_frame = getattr(args, "independent_first_frame", False)
+        self.local_attn_size = self.generator.model.local_attn_size
+        if self.num_frame_per_block > self.generator.engine.max_frames:
+            raise ValueError(f"num_frame_per_block {self.num_frame_per_block} > the engine's largest forward "
+                             f"({self.generator.engine.max_frames} frames)")
+        print(f"KV inference with {self.num_frame_per_block} frames per block")
+        if self.num_frame_per_block > 1:
+            self.generator.model.num_frame_per_block = self.num_frame_per_block
+
+        self.use_graphs = True            # one hipGraph per block (n forwards + updates + refresh), kept for the pipeline's lifetime
+        self.renoise_override: Optional[List[torch.Tensor]] = None   # tests: the re-noise draws in order, each [F, 16, h, w]
+        self.noise_generator: Optional[torch.Generator] = None       # None = the device's default generator (torch.randn_like)
+        self.graph_captures = 0           # hipGraphs constructed so far (tests: none after the first call)
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
+        self._bufs: Dict[int, dict] = {}  # static per-block buffers, by frames per block
+        self._out: Dict[int, torch.Tensor] = {}                     # static output latents, by frame count
+
+    def to(self, *args, **kwargs):
+        return self
+
+    def release_graphs(self) -> None:
+        """Drop every captured block graph (and the static buffers they read)."""
+        torch.cuda.synchronize(self.device)
+        self._graphs.clear()
+        self._bufs.clear()
+        self._out.clear()
+
+    # ------------------------------------------------------------------------------------------------------------
+    def block_schedule(self, num_frames: int, initial_latent: Optional[torch.Tensor] = None) -> List[int]:
+        """Frames per denoised block (causal_inference.py:68-79, 161-163), with the reference's assertions."""
+        F = self.num_frame_per_block
+        if not self.independent_first_frame or (self.independent_first_frame and initial_latent is not None):
+            assert num_frames % F == 0
+            num_blocks = num_frames // F
+        else:
+            assert (num_frames - 1) % F == 0
+            num_blocks = (num_frames - 1) // F
+        sched = [F] * num_blocks
+        if self.independent_first_frame and initial_latent is None:
+            sched = [1] + sched
+        return sched
+
+    def _step_scalars(self):
+        """(engine timestep, sigma of the x0 conversion, sigma of the next step's add_noise) per step, from the step list's
+        own dtype the way the reference's tensors carry it (float32 when warped, int64 otherwise)."""
+        steps = list(self.denoising_step_list)
+        t_eng = [float(t) for t in steps]
+        sig_x0 = [self.generator.sigma_x0(t) for t in steps]
+        sig_next = [self.generator.sigma_add_noise(t) for t in steps[1:]]
+        return t_eng, sig_x0, sig_next
+
+    def _block_buffers(self, F: int) -> dict:
+        b = self._bufs.get(F)
+        if b is None:
+            g, dev = self.geometry, self.device
+            n = len(self.denoising_step_list)
+            shape = (F, 16, g.lat_h, g.lat_w)
+            b = dict(x=torch.empty(shape, dtype=torch.bfloat16, device=dev), flow=torch.empty(shape, dtype=torch.bfloat16, device=dev),
+                     t=torch.empty(F, dtype=torch.float32, device=dev),
+                     bank=torch.empty((max(n - 1, 1),) + shape, dtype=torch.bfloat16, device=dev))
+            self._bufs[F] = b
+        return b
+
+    def _output(self, T: int) -> torch.Tensor:
+        o = self._out.get(T)
+        if o is None:
+            g = self.geometry
+            o = self._out[T] = torch.zeros(1, T, 16, g.lat_h, g.lat_w, dtype=torch.bfloat16, device=self.device)
+        return o
+
+    def _run_block(self, b: dict, out_blk: torch.Tensor, start: int, write, vis, scalars) -> None:
+        """One block's launches (causal_inference.py:165-211): eager, or recorded into the block's hipGraph."""
+        t_eng, sig_x0, sig_next = scalars
+        gen, kv, cross = self.generator, self.kv_cache1, self.crossattn_cache
+        n = len(t_eng)
+        for i in range(n):
+            b["t"].fill_(t_eng[i])
+            gen.flow(b["x"], b["t"], start, write, vis, kv, cross, out=b["flow"])
+            if i < n - 1:                           # x0, then add_noise(x0, randn, next t) back into the block's input
+                gen.fewstep_update(b["flow"], b["x"], b["bank"][i], out_blk, sig_x0[i], sig_next[i])
+            else:                                   # output[:, block] = denoised_pred
+                gen.fewstep_update(b["flow"], b["x"], None, out_blk, sig_x0[i])
+        b["t"].fill_(float(getattr(self.args, "context_noise", 0)))    # refresh the cache with the clean block (:199-207)
+        gen.flow(out_blk, b["t"], start, write, vis, kv, cross, out=b["flow"])
+
+    def _context_forward(self, lat: torch.Tensor, start: int) -> None:
+        """A clean-latent forward at t = 0 that only fills the cache (initial_latent, causal_inference.py:130-159)."""
+        x = lat.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        write, vis, le = self.generator.slots(self.kv_cache1, start, x.shape[0])
+        t = torch.zeros(x.shape[0], dtype=torch.float32, device=self.device)
+        self.generator.flow(x, t, start, write, vis, self.kv_cache1, self.crossattn_cache)
+        self.generator.set_cache_ends(self.kv_cache1, start + x.shape[0], le)
+
+    def inference(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
+                  return_latents: bool = False, profile: bool = False, low_memory: bool = False):
+        """noise [1, F, 16, h, w]; initial_latent [1, n, 16, h, w] or None.  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the
+        latents [1, n + F, 16, h, w]).  low_memory is accepted and has no effect (everything stays resident)."""
+        batch_size, num_frames, num_channels, height, width = noise.shape
+        assert batch_size == 1, "batch size 1 (as every reference entry point)"
+        assert (num_channels, height, width) == (16, self.geometry.lat_h, self.geometry.lat_w), tuple(noise.shape)
+        schedule = self.block_schedule(num_frames, initial_latent)
+        num_input_frames = initial_latent.shape[1] if initial_latent is not None else 0
+        num_output_frames = num_frames + num_input_frames
+        dev = self.device
+        with torch.no_grad():
+            conditional_dict = self.text_encoder(text_prompts=text_prompts)
+            if profile:
+                ev = lambda: torch.cuda.Event(enable_timing=True)
+                init_start, init_end, diffusion_start, diffusion_end, vae_start, vae_end = (ev() for _ in range(6))
+                block_times = []
+                init_start.record()
+
+            if self.kv_cache1 is None:
+                self.kv_cache1 = self.generator.new_kv_cache()
+                self.crossattn_cache = self.generator.new_crossattn_cache()
+            else:                                                             # :113-123
+                for blk in self.crossattn_cache:
+                    blk["is_init"] = False
+                self.generator.set_cache_ends(self.kv_cache1, 0, 0)
+            pe = conditional_dict["prompt_embeds"]
+            self.crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
+
+            noise_bf = noise.to(device=dev, dtype=torch.bfloat16).contiguous()
+            output = self._output(num_output_frames)
+            output.zero_()
+            current_start_frame = 0
+            if initial_latent is not None:                                    # :126-159
+                init = initial_latent.to(device=dev, dtype=torch.bfloat16)
+                F = self.num_frame_per_block
+                if self.independent_first_frame:
+                    assert (num_input_frames - 1) % F == 0
+                    num_input_blocks = (num_input_frames - 1) // F
+                    output[:, :1] = init[:, :1]
+                    self._context_forward(init[0, :1], current_start_frame)
+                    current_start_frame += 1
+                else:
+                    assert num_input_frames % F == 0
+                    num_input_blocks = num_input_frames // F
+                for _ in range(num_input_blocks):
+                    ref = init[:, current_start_frame:current_start_frame + F]
+                    output[:, current_start_frame:current_start_frame + F] = ref
+                    self._context_forward(ref[0], current_start_frame)
+                    current_start_frame += F
+
+            if profile:
+                init_end.record()
+                torch.cuda.synchronize(dev)
+                diffusion_start.record()
+
+            scalars = self._step_scalars()
+            n = len(scalars[0])
+            draws = iter(self.renoise_override) if self.renoise_override is not None else None
+            for F in schedule:
+                if profile:
+                    block_start, block_end = ev(), ev()
+                    block_start.record()
+                s = current_start_frame
+                b = self._block_buffers(F)
+                write, vis, le = self.generator.slots(self.kv_cache1, s, F)
+                b["x"].copy_(noise_bf[0, s - num_input_frames:s - num_input_frames + F])
+                for i in range(n - 1):                                        # the reference's torch.randn_like draws, in order
+                    if draws is not None:
+                        b["bank"][i].copy_(next(draws).reshape(b["bank"][i].shape))
+                    else:
+                        b["bank"][i].normal_(0.0, 1.0, generator=self.noise_generator)
+                out_blk = output[0, s:s + F]
+                key = (s, F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), num_output_frames, tuple(write),
+                       tuple(vis))
+                g = self._graphs.get(key)
+                if g is not None:
+                    g.replay()
+                else:
+                    self._run_block(b, out_blk, s, write, vis, scalars)      # first use: the real work, eagerly ...
+                    if self.use_graphs:                                       # ... then the same launches into the block's graph
+                        torch.cuda.synchronize(dev)
+                        g = torch.cuda.CUDAGraph()
+                        self.graph_captures += 1
+                        with torch.cuda.graph(g):
+                            self._run_block(b, out_blk, s, write, vis, scalars)
+                        self._graphs[key] = g
+                self.generator.set_cache_ends(self.kv_cache1, s + F, le)
+                if profile:
+                    block_end.record()
+                    torch.cuda.synchronize(dev)
+                    block_times.append(block_start.elapsed_time(block_end))
+                current_start_frame += F
+
+            if profile:
+                diffusion_end.record()
+                torch.cuda.synchronize(dev)
+                diffusion_time = diffusion_start.elapsed_time(diffusion_end)
+                init_time = init_start.elapsed_time(init_end)
+                vae_start.record()
+
+            latents = output.clone().to(noise.dtype)
+            video = self.vae.decode_to_pixel(output.clone(), use_cache=False)
+            video = (video * 0.5 + 0.5).clamp(0, 1)
+
+            if profile:
+                vae_end.record()
+                torch.cuda.synchronize(dev)
+                vae_time = vae_start.elapsed_time(vae_end)
+                total_time = init_time + diffusion_time + vae_time
+                print("Profiling results:")
+                print(f"  - Initialization/caching time: {init_time:.2f} ms ({100 * init_time / total_time:.2f}%)")
+                print(f"  - Diffusion generation time: {diffusion_time:.2f} ms ({100 * diffusion_time / total_time:.2f}%)")
+                for i, bt in enumerate(block_times):
+                    print(f"    - Block {i} generation time: {bt:.2f} ms ({100 * bt / diffusion_time:.2f}% of diffusion)")
+                print(f"  - VAE decoding time: {vae_time:.2f} ms ({100 * vae_time / total_time:.2f}%)")
+                print(f"  - Total time: {total_time:.2f} ms")
+        if return_latents:
+            return video, latents
+        return video

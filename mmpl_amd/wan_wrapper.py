@@ -21,6 +21,7 @@ from typing import Dict, List, Optional
 
 import torch
 
+from . import _lib
 from .dit import DitEngine
 from .geometry import Geometry
 from .scheduler import FlowMatchScheduler
@@ -354,3 +355,175 @@ class WanVAEWrapper(torch.nn.Module):
     def decode_to_pixel(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
         """latent [B, F, 16, h, w] -> pixel [B, T, 3, 8h, 8w] float32 clamped to [-1, 1]."""
         return torch.stack([self.model.decode(u, self.mean, self.std).float().clamp_(-1, 1) for u in latent], dim=0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Few-step (Self-Forcing / CausVid) generator: CausalWanModel behind WanDiffusionWrapper (utils/wan_wrapper.py:116-300)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+def causal_slots(start_frame: int, n_frames: int, n_slots: int, window_frames: int, local_end: int = 0, global_end: int = 0):
+    """KV slots of one CausalWanSelfAttention forward (wan/modules/causal_model.py:196-224), in frames of S tokens.
+
+    The block's frames are written at ``local_end - n_frames .. local_end - 1`` with
+    ``local_end = local_end_index + (start_frame + n_frames) - global_end_index`` (the cache's bookkeeping before the call), and
+    the attention sees ``[max(0, local_end - window_frames), local_end)``.  Returns (write_slots, visible_slots, local_end).
+    Where the reference would index past its cache (an IndexError / shape mismatch there) this raises ValueError."""
+    if n_frames < 1 or start_frame < 0:
+        raise ValueError(f"causal cache: bad block (start frame {start_frame}, {n_frames} frames)")
+    le = local_end + start_frame + n_frames - global_end
+    ls = le - n_frames
+    if ls < 0 or le > n_slots:
+        raise ValueError(f"causal cache overflow: frames {start_frame}..{start_frame + n_frames - 1} map to slots {ls}..{le - 1}, "
+                         f"the cache holds {n_slots} frame slots (allocate it with new_kv_cache(n_slots) >= {le})")
+    return list(range(ls, le)), list(range(max(0, le - window_frames), le)), le
+
+
+class _CausalModelHandle(_ModelHandle):
+    """`generator.model` of the causal wrapper: the reference's CausalWanModel attributes the pipeline reads or sets."""
+
+    def __init__(self, engine: DitEngine, local_attn_size: int, sink_size: int):
+        super().__init__(engine)
+        self.local_attn_size = local_attn_size
+        self.sink_size = sink_size
+
+
+class WanDiffusionWrapper(torch.nn.Module):
+    """utils/wan_wrapper.py:116-300 with ``is_causal=True`` (CausalWanModel, the Self-Forcing / CausVid generator) on the HIP DiT.
+
+    For inference CausalWanModel differs from CausalFPSWanModel in two places only, both host-side here:
+      * RoPE: contiguous frame ids ``current_start / S + i`` (causal_rope_apply, causal_model.py:27-57);
+      * cache indexing: the block is written at its own frames and attends to the last ``window`` frames up to its end
+        (causal_model.py:196-224; window = 21 frames when local_attn_size == -1, the reference's 32760 tokens at 480p).
+    ``forward`` returns (flow_pred, pred_x0); pred_x0 is ``_convert_flow_pred_to_x0`` on the device (mmpl_fewstep_update)."""
+
+    def __init__(self, model_name="Wan2.1-T2V-14B", timestep_shift=8.0, is_causal=False, local_attn_size=-1, sink_size=0,
+                 *, model_config: Optional[dict] = None, geometry: Optional[Geometry] = None, device="cuda:0", max_frames: int = 7):
+        super().__init__()
+        assert is_causal, "only the causal generator (CausalWanModel) is on the hot path"
+        self.geometry = geometry or Geometry.named("480p")
+        from .checkpoints import read_diffusers_dir
+        cfg = model_config
+        disk_cfg, disk_sd = read_diffusers_dir(f"{local_wan_path}/{model_name}/")    # CausalWanModel.from_pretrained (:127-128)
+        if cfg is None:
+            cfg = disk_cfg
+        if cfg is None:
+            cfg = WAN_CONFIGS["14B" if "14B" in model_name else "1.3B"]
+        self.engine = DitEngine(cfg, self.geometry.lat_h, self.geometry.lat_w, device, max_frames=max_frames)
+        if self.engine.model_type != "t2v":
+            raise ValueError("WanDiffusionWrapper: the few-step causal generator is a t2v model")
+        self.local_attn_size = int(local_attn_size)
+        self.model = _CausalModelHandle(self.engine, self.local_attn_size, sink_size)
+        if disk_sd is not None:
+            self.engine.load_state_dict(disk_sd)
+        self.model_type = "t2v"
+        self.uniform_timestep = not is_causal
+        self.scheduler = FlowMatchScheduler(shift=timestep_shift, sigma_min=0.0, extra_one_step=True)
+        self.scheduler.set_timesteps(1000, training=True)
+        self.seq_len = self.geometry.frame_seqlen * self.geometry.frames_per_chunk      # the reference's 32760
+        self._sig64 = self.scheduler.sigmas.double()
+        self._ts64 = self.scheduler.timesteps.double()
+
+    # nn.Module-compatible entry points
+    def load_state_dict(self, state_dict, strict: bool = True):
+        from .checkpoints import strip_generator_prefix
+        self.engine.load_state_dict(strip_generator_prefix(state_dict))
+        return torch.nn.modules.module._IncompatibleKeys([], [])
+
+    def to(self, *args, **kwargs):
+        return self
+
+    def get_scheduler(self) -> FlowMatchScheduler:
+        return self.scheduler
+
+    @property
+    def window_frames(self) -> int:
+        """max_attention_size in frames: 32760 tokens = 21 frames (local_attn_size == -1) or local_attn_size (causal_model.py:76)."""
+        return self.geometry.frames_per_chunk if self.local_attn_size == -1 else self.local_attn_size
+
+    def new_kv_cache(self, n_slots: Optional[int] = None) -> KVCache:
+        """The reference's kv_cache1 (causal_inference.py:278-297): local_attn_size frames, or 32760 tokens = 21 frames."""
+        return KVCache(self.engine, self.window_frames if n_slots is None else n_slots)
+
+    def new_crossattn_cache(self) -> CrossAttnCache:
+        return CrossAttnCache(self.engine)
+
+    # -- host scalars of the reference's timestep -> sigma lookups ------------------------------------------------------------
+    def sigma_x0(self, timestep) -> float:
+        """sigma_t of _convert_flow_pred_to_x0 (wan_wrapper.py:190-197): argmin over the fp64 timesteps, fp64 sigma."""
+        t = torch.as_tensor(timestep).reshape(1).double()
+        return float(self._sig64[torch.argmin((self._ts64.unsqueeze(0) - t.unsqueeze(1)).abs(), dim=1)].item())
+
+    def sigma_add_noise(self, timestep) -> float:
+        """sigma of FlowMatchScheduler.add_noise (scheduler.py:170-175) for a timestep tensor of the caller's dtype."""
+        s = self.scheduler
+        t = torch.as_tensor(timestep).reshape(1)
+        return float(s.sigmas[torch.argmin((s.timesteps.unsqueeze(0) - t.unsqueeze(1)).abs(), dim=1)].item())
+
+    # -- device pieces (capturable) ------------------------------------------------------------------------------------------
+    def slots(self, kv_cache: KVCache, start_frame: int, n_frames: int):
+        """(write_slots, visible_slots, local_end) of a forward at `start_frame` against `kv_cache`'s current bookkeeping."""
+        n_slots = kv_cache.k_all.shape[1] // self.engine.S
+        return causal_slots(start_frame, n_frames, n_slots, self.window_frames, int(kv_cache[0]["local_end_index"][0]),
+                            int(kv_cache[0]["global_end_index"][0]))
+
+    @staticmethod
+    def set_cache_ends(kv_cache: KVCache, global_end_frame: int, local_end_frame: int) -> None:
+        """global_end_index / local_end_index after a forward (causal_model.py:225-226), in tokens, on every layer's dict."""
+        S = kv_cache.engine.S
+        for blk in kv_cache:
+            blk["global_end_index"].fill_(global_end_frame * S)
+            blk["local_end_index"].fill_(local_end_frame * S)
+
+    def flow(self, x: torch.Tensor, t: torch.Tensor, start_frame: int, write_slots, visible_slots, kv_cache: KVCache,
+             crossattn_cache: CrossAttnCache, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One CausalWanModel._forward_inference on explicit slots: x [F, 16, h, w] bf16, t [F] float32 on the device.  Stateless
+        attention; the text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch)."""
+        frames = [start_frame + i for i in range(x.shape[0])]
+        return self.engine.forward(x, t, frames, write_slots, visible_slots, kv_cache.k_all, kv_cache.v_all, crossattn_cache.k_all,
+                                   crossattn_cache.v_all, out=out)
+
+    @staticmethod
+    def fewstep_update(flow: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], x0_out: torch.Tensor, sigma_t: float,
+                       sigma_next: float = 0.0) -> None:
+        """x0_out = _convert_flow_pred_to_x0(flow, x); if noise is given, x = add_noise(x0_out, noise, sigma_next) (mmpl_fewstep_update)."""
+        n = x.numel()
+        for t in (flow, x, x0_out) + ((noise,) if noise is not None else ()):
+            assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == n and t.is_cuda, (t.dtype, tuple(t.shape))
+        _lib.check(_lib.load().mmpl_fewstep_update(_lib.ptr(flow), _lib.ptr(x), _lib.ptr(noise), _lib.ptr(x0_out), n,
+                                                   float(sigma_t), float(sigma_next), _lib.stream_ptr()), "mmpl_fewstep_update")
+
+    # -- the reference's call shape ------------------------------------------------------------------------------------------
+    def forward(self, noisy_image_or_video: torch.Tensor, conditional_dict: dict, timestep: torch.Tensor,
+                kv_cache: Optional[KVCache] = None, crossattn_cache: Optional[CrossAttnCache] = None,
+                current_start: Optional[int] = None, classify_mode: Optional[bool] = False,
+                concat_time_embeddings: Optional[bool] = False, clean_x=None, aug_t=None, cache_start: Optional[int] = None):
+        """noisy_image_or_video [1, F, 16, h, w]; timestep [1, F]; current_start in tokens.  -> (flow_pred, pred_x0), both
+        [1, F, 16, h, w] bf16.  Reads the timestep on the host (one sync when it lives on the device): the pipeline's graphs use
+        `flow` / `fewstep_update` with host scalars instead."""
+        if kv_cache is None or crossattn_cache is None:
+            raise ValueError("WanDiffusionWrapper: only the KV-cached inference forward is implemented (kv_cache / crossattn_cache)")
+        if classify_mode or clean_x is not None:
+            raise ValueError("WanDiffusionWrapper: training-only forward modes (classify_mode / clean_x) are not implemented")
+        assert noisy_image_or_video.shape[0] == 1, "batch size 1 (as every reference entry point)"
+        S = self.engine.S
+        cs = int(current_start or 0)
+        if cs % S:
+            raise ValueError(f"current_start {cs} is not a multiple of the frame length {S}")
+        if not crossattn_cache.is_init:                                   # model.py:175-180
+            pe = conditional_dict["prompt_embeds"]
+            crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
+        x = noisy_image_or_video[0].to(torch.bfloat16).contiguous()
+        nF = x.shape[0]
+        ts = timestep.reshape(-1)
+        assert ts.numel() == nF, (tuple(timestep.shape), nF)
+        write, vis, le = self.slots(kv_cache, cs // S, nF)
+        flow = self.flow(x, ts.to(device=x.device, dtype=torch.float32), cs // S, write, vis, kv_cache, crossattn_cache)
+        self.set_cache_ends(kv_cache, cs // S + nF, le)
+        x0 = torch.empty_like(x)
+        sig = [self.sigma_x0(t) for t in ts.cpu()]                       # per-frame sigma (uniform_timestep = False)
+        if all(s == sig[0] for s in sig):
+            self.fewstep_update(flow, x, None, x0, sig[0])
+        else:
+            for i in range(nF):
+                self.fewstep_update(flow[i], x[i], None, x0[i], sig[i])
+        return flow.unsqueeze(0), x0.unsqueeze(0)
