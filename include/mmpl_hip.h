@@ -253,6 +253,29 @@ int mmpl_vae_decode(MmplVae* v, const void* z, int n_frames, const float* mean, 
 int mmpl_vae_encode(MmplVae* v, const void* px, int n_px_frames, const float* mean, const float* inv_std, void* out, void* workspace,
                     size_t workspace_bytes, mmpl_stream_t stream);
 
+/* ---- streaming decode: WanVAE_.cached_decode / clear_cache (wan/modules/vae.py:571-609) behind
+ * WanVAEWrapper.decode_to_pixel(use_cache=True) (utils/wan_wrapper.py:90-113) ----
+ * A MmplVaeStream is one decoded video in progress: every causal conv's feature cache (the reference's feat_map) stays in the
+ * caller's workspace between calls, the handle keeps where each cache ring stands and how many latent frames went through.
+ * The handle borrows the MmplVae it was created on (destroy the stream first) and can be created before the weights are bound. */
+typedef struct MmplVaeStream MmplVaeStream;
+int mmpl_vae_stream_create(MmplVae* v, MmplVaeStream** out);
+void mmpl_vae_stream_destroy(MmplVaeStream* s);
+/* WanVAE_.clear_cache: the next mmpl_vae_stream_decode starts a new video (and may bind another workspace).  Host-side only. */
+int mmpl_vae_stream_reset(MmplVaeStream* s);
+/* WanVAE_.cached_decode: decodes n_frames >= 1 MORE latent frames of the current video, z dev bf16 [n_frames, 16, lat_h, lat_w].
+ * Writes 1 + 4(n_frames-1) pixel frames when these are the video's first frames (after create / reset), else 4 n_frames, and
+ * reports the count in *n_px_frames_out (may be NULL).  out_format 0: dev float32 [T, 3, 8 lat_h, 8 lat_w] clamped to [-1, 1]
+ * (mmpl_vae_decode's output: a video decoded in any split is bit-identical to the one-shot decode); out_format 1: dev uint8
+ * [T, 8 lat_h, 8 lat_w, 3] (4-byte aligned) = those frames through (x * 0.5 + 0.5).clamp(0, 1) and
+ * (v * 255.0).clamp(0, 255).to(uint8) of pipeline/causal_inference.py:256 and the video writer, in the same fp32 operations.
+ * workspace: caller-owned, mmpl_vae_workspace_bytes(v, 0) bytes, holds the video's cache: it must be the SAME pointer from one
+ * reset to the next (another pointer or a smaller size is an error, never a silent restart) and nothing else may write it in
+ * between.  It is cleared (asynchronously, on `stream`) by the first decode after create / reset only.  All argument checks
+ * run before the first HIP call.  No host read-back, no allocation. */
+int mmpl_vae_stream_decode(MmplVaeStream* s, const void* z, int n_frames, const float* mean, const float* inv_std, void* out,
+                           int out_format, int* n_px_frames_out, void* workspace, size_t workspace_bytes, mmpl_stream_t stream);
+
 /* ---- umT5 text encoder (wan/modules/t5.py:267-312 behind WanTextEncoder, utils/wan_wrapper.py:15-51) ----
  * Weights (bf16 dev pointers): [token_embedding.weight, norm.weight] then per block
  * [norm1.weight, pack:attn.{q,k,v}.weight[3*dim_attn,dim], attn.o.weight, pos_embedding.embedding.weight[num_buckets,heads],

@@ -14,6 +14,7 @@ SYMBOLS = [
     "mmpl_attn_fwd", "mmpl_attn_fwd_ws", "mmpl_attn_fwd_variant", "mmpl_attn_fwd_history", "mmpl_attn_history_bytes", "mmpl_attn_workspace_bytes", "mmpl_gemm", "mmpl_gemm_tickets", "mmpl_gemm_scratch", "mmpl_gemm_scratch_bytes", "mmpl_device_xcd_round_robin", "mmpl_probe_mfma_tflops", "mmpl_layernorm", "mmpl_qknorm_rope", "mmpl_cfg_unipc_step", "mmpl_cfg_unipc_step_table", "mmpl_fewstep_update",
     "mmpl_vae_num_weights", "mmpl_vae_weight_name", "mmpl_vae_create", "mmpl_vae_destroy", "mmpl_vae_bind_weights",
     "mmpl_vae_workspace_bytes", "mmpl_vae_decode", "mmpl_vae_encode",
+    "mmpl_vae_stream_create", "mmpl_vae_stream_destroy", "mmpl_vae_stream_reset", "mmpl_vae_stream_decode",
     "mmpl_t5_num_weights", "mmpl_t5_create", "mmpl_t5_destroy", "mmpl_t5_bind_weights", "mmpl_t5_workspace_bytes", "mmpl_t5_encode",
     "mmpl_i2v_img_proj_workspace_bytes", "mmpl_i2v_img_proj", "mmpl_i2v_img_kv", "mmpl_i2v_cross_attn_workspace_bytes", "mmpl_i2v_cross_attn",
     "mmpl_profile_enable", "mmpl_profile_read", "mmpl_last_error", "mmpl_version",
@@ -137,6 +138,11 @@ def _bind_vae(lib):
     lib.mmpl_vae_workspace_bytes.restype = sz
     lib.mmpl_vae_decode.argtypes = [vp, vp, ci, fp, fp, vp, vp, sz, vp]
     lib.mmpl_vae_encode.argtypes = [vp, vp, ci, fp, fp, vp, vp, sz, vp]
+    lib.mmpl_vae_stream_create.argtypes = [vp, C.POINTER(vp)]
+    lib.mmpl_vae_stream_destroy.argtypes = [vp]
+    lib.mmpl_vae_stream_destroy.restype = None
+    lib.mmpl_vae_stream_reset.argtypes = [vp]
+    lib.mmpl_vae_stream_decode.argtypes = [vp, vp, ci, fp, fp, vp, ci, C.POINTER(ci), vp, sz, vp]
 
 
 def check(rc: int, what: str = "") -> None:

@@ -61,6 +61,15 @@ def fewstep_refusal(args, world: int):
     return None
 
 
+def stream_refusal(args, fewstep: bool):
+    """Why --stream cannot run this command line (None = it can, or it was not asked for): block-wise output exists for the
+    few-step pipeline only (CausalInferencePipeline.inference_stream)."""
+    if getattr(args, "stream", False) and not fewstep:
+        return ("--stream: block-wise output needs a few-step config (one with denoising_step_list, e.g. self_forcing_dmd.yaml); "
+                "the 50-step pipeline does not stream")
+    return None
+
+
 def build_fewstep_pipeline(config, args, dev, geo, mcfg):
     """WanDiffusionWrapper + CausalInferencePipeline (Wan_fps_inference_1gpu.py:61), then `independent_first_frame = False`
     as the entry script sets it (:73)."""
@@ -109,12 +118,18 @@ def main(argv=None):
     ap.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (one rank per GPU); gloo stages the hand-off through the host and lets several ranks "
                          "share one GPU (tests on 1-GPU boxes)")
+    ap.add_argument("--stream", action="store_true",
+                    help="few-step configs: decode and hand out the video block by block while the next block denoises "
+                         "(CausalInferencePipeline.inference_stream); prints the time to the first frames and per block")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     config = load_config(args.config_path)
     fewstep = is_fewstep(config)
+    why = stream_refusal(args, fewstep)
+    if why is not None:
+        ap.error(why)
     if fewstep:
         why = fewstep_refusal(args, world)
         if why is not None:
@@ -278,8 +293,17 @@ def _main_fewstep(config, args, dev, geo, mcfg):
         g = torch.Generator(device="cpu").manual_seed(args.seed)
         noise = torch.randn(shape, generator=g).to(torch.bfloat16)
         torch.manual_seed(args.seed)                         # the re-noise draws: the device generator (set_seed, :44-49)
-        video = pipe.inference(noise.to(dev), [prompt], return_latents=False)
-        out = (video * 255.0).clamp(0, 255).to(torch.uint8)[0].permute(0, 2, 3, 1).contiguous().cpu()     # [T, H, W, 3]
+        if args.stream:
+            import time
+            parts, t0 = [], time.perf_counter()
+            for first, frames in pipe.inference_stream(noise.to(dev), [prompt], output="uint8"):
+                print(f"[mmpl_amd.cli] few-step prompt {idx}: frames {first}..{first + frames.shape[0] - 1} after "
+                      f"{time.perf_counter() - t0:.3f} s" + (" (time to the first frames)" if not parts else ""))
+                parts.append(frames)
+            out = torch.cat(parts)                                                                             # [T, H, W, 3]
+        else:
+            video = pipe.inference(noise.to(dev), [prompt], return_latents=False)
+            out = (video * 255.0).clamp(0, 255).to(torch.uint8)[0].permute(0, 2, 3, 1).contiguous().cpu()     # [T, H, W, 3]
         path = os.path.join(args.output_folder, f"{idx}-0.pt")
         torch.save(out, path)
         from .utils.video_io import write_video

@@ -97,16 +97,38 @@ struct MmplVae {
 
 namespace {
 
-struct Ctx {
-  MmplVae* v;
+// What outlives one decoder_frame / encoder_chunk: per call of the one-shot entries, per video of a MmplVaeStream.
+struct VaeState {
   Arena ar;
-  hipStream_t s;
-  bool dry;
-  hipError_t err = hipSuccess;
-  const char* where = "";
   std::map<std::string, int> ring_base;   // temporal-cache rings: first slot of the two cached frames, per conv volume
   std::map<std::string, bool> prefilled;  // convs whose new input frames the PRODUCING conv's epilogue already normalised into their ring slots
-  size_t plain_elems;
+  long frames_done = 0;                   // latent frames decoded so far in this video (0: the next one is the "first frame")
+};
+
+}  // namespace
+
+// A decoded video in progress (WanVAE_'s feat_map between cached_decode calls): where every conv's ring stands, how many latent
+// frames went through, and the workspace all of it lives in.
+struct MmplVaeStream {
+  MmplVae* v = nullptr;
+  VaeState st;
+  size_t need = 0;        // mmpl_vae_workspace_bytes(v, 0)
+  void* ws = nullptr;     // the workspace this video is bound to; null = none yet (after create / reset)
+};
+
+namespace {
+
+struct Ctx {
+  MmplVae* v;
+  Arena& ar;
+  hipStream_t s;
+  bool dry;
+  std::map<std::string, int>& ring_base;
+  std::map<std::string, bool>& prefilled;
+  hipError_t err = hipSuccess;
+  const char* where = "";
+  size_t plain_elems = 0;
+  Ctx(MmplVae* v_, VaeState& st, hipStream_t s_, bool dry_) : v(v_), ar(st.ar), s(s_), dry(dry_), ring_base(st.ring_base), prefilled(st.prefilled) {}
   bf16_t* plain(int i) { return ar.get("plain" + std::to_string(i), plain_elems); }
   void chk(hipError_t e, const char* w) { if (e != hipSuccess && err == hipSuccess) { err = e; where = w; } }
 };
@@ -263,10 +285,12 @@ void attn_block(Ctx& c, const std::string& pre, const bf16_t* x, bf16_t* out, in
 }
 
 // ------------------------------------------------------------------------------------------------ decoder
-// one latent frame (vae.py:423-472).  Returns the number of pixel frames produced (1 for the first latent, else 4).
-int decoder_frame(Ctx& c, const bf16_t* z_all, int F, int fi, const float* mean, const float* inv_std, float* out, int t_out) {
+// one latent frame (vae.py:423-472): frame fi of this call's z; `first` = it is the VIDEO's first latent frame (nothing cached yet).
+// Returns the number of pixel frames produced (1 for the first latent, else 4), written at frame t_out of out in out_format
+// (0: float32 [T,3,H,W], 1: uint8 [T,H,W,3]).
+int decoder_frame(Ctx& c, const bf16_t* z_all, int fi, bool first, const float* mean, const float* inv_std, void* out, int out_format,
+                  int t_out) {
   MmplVae* v = c.v;
-  const bool first = fi == 0;
   int H = v->lat_h, W = v->lat_w, T = 1;
   bf16_t *a = c.plain(0), *b = c.plain(1), *t1 = c.plain(2), *t2 = c.plain(3);
   {  // z prep + conv2 -> decoder.conv1's padded volume, then conv1
@@ -346,7 +370,10 @@ int decoder_frame(Ctx& c, const bf16_t* z_all, int F, int fi, const float* mean,
   }
   // head: RMS_norm + SiLU + conv(96 -> 3 padded to 4)
   cached_conv3(c, "decoder.head.2", x, v->W("decoder.head.0.gamma"), T, tmax, H, W, 96, 4, y, nullptr);
-  if (!c.dry) c.chk(vae_launch_px_out(y, out, T, H, W, t_out, c.s), "px_out");
+  if (!c.dry) {
+    if (out_format == 1) c.chk(vae_launch_px_out_u8(y, (unsigned char*)out, T, H, W, t_out, c.s), "px_out_u8");
+    else c.chk(vae_launch_px_out(y, (float*)out, T, H, W, t_out, c.s), "px_out");
+  }
   return T;
 }
 
@@ -417,6 +444,18 @@ void encoder_chunk(Ctx& c, const bf16_t* px, int Ttot, int t0, int T, bool first
 
 size_t plain_elems_for(const MmplVae* v) { return (size_t)4 * (v->lat_h * 8) * (v->lat_w * 8) * 96; }
 
+// The decoder's workspace layout: a dry pass over the video's first frame and one later frame, in the order a decode meets them
+// (the first frame skips the time_conv volumes; a one-shot decode lays its arena out in the same order as it goes).  A stream
+// keeps this layout for its lifetime, so a call that begins in the middle of a video finds every volume where the calls before
+// it left it.
+void decoder_layout(MmplVae* v, VaeState& st) {
+  Ctx c(v, st, nullptr, true);
+  c.plain_elems = plain_elems_for(v);
+  float dummy[16] = {0};
+  decoder_frame(c, nullptr, 0, true, dummy, dummy, nullptr, 0, 0);
+  decoder_frame(c, nullptr, 1, false, dummy, dummy, nullptr, 0, 1);
+}
+
 }  // namespace
 
 extern "C" {
@@ -452,17 +491,18 @@ int mmpl_vae_bind_weights(MmplVae* v, const void* const* ptrs, int n) {
 }
 
 size_t mmpl_vae_workspace_bytes(MmplVae* v, int mode) {
-  Ctx c{v, Arena(), nullptr, true};
-  c.plain_elems = plain_elems_for(v);
-  float dummy[16] = {0};
+  if (!v) return 0;
+  VaeState st;
   if (mode == 0) {
-    decoder_frame(c, nullptr, 2, 0, dummy, dummy, nullptr, 0);
-    decoder_frame(c, nullptr, 2, 1, dummy, dummy, nullptr, 1);
+    decoder_layout(v, st);
   } else {
+    Ctx c(v, st, nullptr, true);
+    c.plain_elems = plain_elems_for(v);
+    float dummy[16] = {0};
     encoder_chunk(c, nullptr, 5, 0, 1, true, dummy, dummy, nullptr, 0);
     encoder_chunk(c, nullptr, 5, 1, 4, false, dummy, dummy, nullptr, 1);
   }
-  return c.ar.off;
+  return st.ar.off;
 }
 
 int mmpl_vae_decode(MmplVae* v, const void* z, int n_frames, const float* mean, const float* inv_std, void* out, void* ws,
@@ -471,12 +511,13 @@ int mmpl_vae_decode(MmplVae* v, const void* z, int n_frames, const float* mean, 
   if (n_frames < 1) return mmpl_set_error("mmpl_vae_decode", "n_frames < 1");
   const size_t need = mmpl_vae_workspace_bytes(v, 0);
   if (ws_bytes < need) return mmpl_set_error("mmpl_vae_decode", "workspace too small");
-  Ctx c{v, Arena(), (hipStream_t)stream, false};
+  VaeState st;
+  Ctx c(v, st, (hipStream_t)stream, false);
   c.ar.base = (char*)ws;
   c.plain_elems = plain_elems_for(v);
   if (hipMemsetAsync(ws, 0, need, c.s) != hipSuccess) return mmpl_set_error("mmpl_vae_decode", "memset failed");  // clear_cache()
   int t_out = 0;
-  for (int i = 0; i < n_frames; ++i) t_out += decoder_frame(c, (const bf16_t*)z, n_frames, i, mean, inv_std, (float*)out, t_out);
+  for (int i = 0; i < n_frames; ++i) t_out += decoder_frame(c, (const bf16_t*)z, i, i == 0, mean, inv_std, out, 0, t_out);
   if (c.err != hipSuccess) return mmpl_set_error(c.where, hipGetErrorString(c.err));
   return 0;
 }
@@ -487,13 +528,64 @@ int mmpl_vae_encode(MmplVae* v, const void* px, int n_px_frames, const float* me
   if (n_px_frames < 1 || (n_px_frames - 1) % 4) return mmpl_set_error("mmpl_vae_encode", "pixel frames must be 1 + 4k");
   const size_t need = mmpl_vae_workspace_bytes(v, 1);
   if (ws_bytes < need) return mmpl_set_error("mmpl_vae_encode", "workspace too small");
-  Ctx c{v, Arena(), (hipStream_t)stream, false};
+  VaeState st;
+  Ctx c(v, st, (hipStream_t)stream, false);
   c.ar.base = (char*)ws;
   c.plain_elems = plain_elems_for(v);
   if (hipMemsetAsync(ws, 0, need, c.s) != hipSuccess) return mmpl_set_error("mmpl_vae_encode", "memset failed");
   const int iters = 1 + (n_px_frames - 1) / 4;
   for (int i = 0; i < iters; ++i)
     encoder_chunk(c, (const bf16_t*)px, n_px_frames, i == 0 ? 0 : 1 + 4 * (i - 1), i == 0 ? 1 : 4, i == 0, mean, inv_std, (float*)out, i);
+  if (c.err != hipSuccess) return mmpl_set_error(c.where, hipGetErrorString(c.err));
+  return 0;
+}
+
+int mmpl_vae_stream_create(MmplVae* v, MmplVaeStream** out) {
+  if (!v || !out) return mmpl_set_error("mmpl_vae_stream_create", "null argument");
+  MmplVaeStream* s = new MmplVaeStream();
+  s->v = v;
+  decoder_layout(v, s->st);
+  s->need = s->st.ar.off;
+  *out = s;
+  return 0;
+}
+
+void mmpl_vae_stream_destroy(MmplVaeStream* s) { delete s; }
+
+int mmpl_vae_stream_reset(MmplVaeStream* s) {
+  if (!s) return mmpl_set_error("mmpl_vae_stream_reset", "null argument");
+  s->st.ring_base.clear();
+  s->st.prefilled.clear();
+  s->st.frames_done = 0;
+  s->ws = nullptr;          // the next decode binds a workspace again and clears it
+  return 0;
+}
+
+int mmpl_vae_stream_decode(MmplVaeStream* s, const void* z, int n_frames, const float* mean, const float* inv_std, void* out,
+                           int out_format, int* n_px_frames_out, void* ws, size_t ws_bytes, mmpl_stream_t stream) {
+  if (!s) return mmpl_set_error("mmpl_vae_stream_decode", "null argument");
+  MmplVae* v = s->v;
+  if (!v || v->w.empty()) return mmpl_set_error("mmpl_vae_stream_decode", "weights not bound");
+  if (n_frames < 1) return mmpl_set_error("mmpl_vae_stream_decode", "n_frames < 1");
+  if (out_format != 0 && out_format != 1) return mmpl_set_error("mmpl_vae_stream_decode", "unknown out_format");
+  if (!z || !mean || !inv_std || !out) return mmpl_set_error("mmpl_vae_stream_decode", "null argument");
+  if (out_format == 1 && ((uintptr_t)out & 3)) return mmpl_set_error("mmpl_vae_stream_decode", "uint8 output must be 4-byte aligned");
+  if (!ws || ws_bytes < s->need) return mmpl_set_error("mmpl_vae_stream_decode", "workspace too small");
+  if (s->ws && s->ws != ws)
+    return mmpl_set_error("mmpl_vae_stream_decode", "workspace differs from the one this video's cache lives in (reset first)");
+  Ctx c(v, s->st, (hipStream_t)stream, false);
+  c.ar.base = (char*)ws;
+  c.plain_elems = plain_elems_for(v);
+  if (!s->ws) {             // first call of a video: clear_cache()
+    if (hipMemsetAsync(ws, 0, s->need, c.s) != hipSuccess) return mmpl_set_error("mmpl_vae_stream_decode", "memset failed");
+    s->ws = ws;
+  }
+  int t_out = 0;
+  for (int i = 0; i < n_frames; ++i) {
+    t_out += decoder_frame(c, (const bf16_t*)z, i, s->st.frames_done == 0, mean, inv_std, out, out_format, t_out);
+    ++s->st.frames_done;
+  }
+  if (n_px_frames_out) *n_px_frames_out = t_out;
   if (c.err != hipSuccess) return mmpl_set_error(c.where, hipGetErrorString(c.err));
   return 0;
 }

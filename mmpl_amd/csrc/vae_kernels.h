@@ -64,6 +64,7 @@ struct ZPrepArgs {
 };
 hipError_t vae_launch_zprep(const ZPrepArgs& a, hipStream_t s);
 hipError_t vae_launch_px_out(const bf16_t* src, float* out, int T, int H, int W, int t_out, hipStream_t s);
+hipError_t vae_launch_px_out_u8(const bf16_t* src, unsigned char* out, int T, int H, int W, int t_out, hipStream_t s);
 hipError_t vae_launch_px_in(const bf16_t* px, bf16_t* dst, int Ttot, int t0, int T, int H, int W, int dt0, hipStream_t s);
 struct MuArgs {
   const bf16_t* enc;   // [F*h*w, 32] encoder head output

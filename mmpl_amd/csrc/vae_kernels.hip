@@ -490,6 +490,40 @@ __global__ void px_out_kernel(const bf16_t* src, float* out, int T, int H, int W
   }
 }
 
+// ---- head output [T,H,W,4] bf16 -> uint8 [T,H,W,3] (frame offset t_out): the float path's clamp(-1,1), then what the pipeline and
+// the CLI do to those frames in PyTorch, (x * 0.5 + 0.5).clamp(0, 1) and (v * 255.0).clamp(0, 255).to(uint8), in the same fp32
+// operations, order and rounding (multiply and add kept apart), truncated.  One lane = 4 consecutive pixels: two 16-byte loads, 12
+// bytes out as three dwords (W is a multiple of 8, so a group never straddles a row and starts 4-byte aligned).
+__device__ __forceinline__ uint32_t px_u8(uint32_t bits) {
+#pragma clang fp contract(off)
+  float v = fminf(1.f, fmaxf(-1.f, bf2f(bits)));
+  v = v * 0.5f;
+  v = v + 0.5f;
+  v = fminf(1.f, fmaxf(0.f, v));
+  v = v * 255.0f;
+  v = fminf(255.f, fmaxf(0.f, v));
+  return (uint32_t)v;
+}
+
+__global__ void px_out_u8_kernel(const bf16_t* src, unsigned char* out, int T, int H, int W, int t_out) {
+  const long hw = (long)H * W;
+  const long groups = (long)T * hw / 4;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(out + (size_t)t_out * hw * 3);
+  for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long)gridDim.x * blockDim.x) {
+    const u32x4 a = *reinterpret_cast<const u32x4*>(src + g * 16);
+    const u32x4 b = *reinterpret_cast<const u32x4*>(src + g * 16 + 8);
+    // pixel j = channels (lo, hi) of word 2j and lo of word 2j + 1
+    const uint32_t r0 = px_u8(a.x & 0xffff), g0 = px_u8(a.x >> 16), b0 = px_u8(a.y & 0xffff);
+    const uint32_t r1 = px_u8(a.z & 0xffff), g1 = px_u8(a.z >> 16), b1 = px_u8(a.w & 0xffff);
+    const uint32_t r2 = px_u8(b.x & 0xffff), g2 = px_u8(b.x >> 16), b2 = px_u8(b.y & 0xffff);
+    const uint32_t r3 = px_u8(b.z & 0xffff), g3 = px_u8(b.z >> 16), b3 = px_u8(b.w & 0xffff);
+    uint32_t* d = dst + g * 3;
+    d[0] = r0 | (g0 << 8) | (b0 << 16) | (r1 << 24);
+    d[1] = g1 | (b1 << 8) | (r2 << 16) | (g2 << 24);
+    d[2] = b2 | (r3 << 8) | (g3 << 16) | (b3 << 24);
+  }
+}
+
 // ---- pixels [3,Ttot,H,W] bf16 (frames t0..t0+T) -> padded channels-last volume [.., H+2, W+2, 32] (c >= 3 zero)
 __global__ void px_in_kernel(const bf16_t* px, bf16_t* dst, int Ttot, int t0, int T, int H, int W, int dt0) {
   const long total = (long)T * H * W;
@@ -630,6 +664,11 @@ hipError_t vae_launch_zprep(const ZPrepArgs& a, hipStream_t s) {
 }
 hipError_t vae_launch_px_out(const bf16_t* src, float* out, int T, int H, int W, int t_out, hipStream_t s) {
   hipLaunchKernelGGL(px_out_kernel, dim3(grid_for((long)T * H * W)), dim3(256), 0, s, src, out, T, H, W, t_out);
+  return hipGetLastError();
+}
+hipError_t vae_launch_px_out_u8(const bf16_t* src, unsigned char* out, int T, int H, int W, int t_out, hipStream_t s) {
+  if (W % 4 || ((uintptr_t)out & 3)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(px_out_u8_kernel, dim3(grid_for((long)T * H * W / 4)), dim3(256), 0, s, src, out, T, H, W, t_out);
   return hipGetLastError();
 }
 hipError_t vae_launch_px_in(const bf16_t* px, bf16_t* dst, int Ttot, int t0, int T, int H, int W, int dt0, hipStream_t s) {

@@ -12,7 +12,9 @@ What changed underneath:
     (``release_graphs()`` drops them);
   * the re-noise draws (``torch.randn_like`` per non-final step) are drawn before the block, in the reference's order and shape,
     into a static bank the graph reads: the same device generator state gives the reference's draws bit for bit;
-  * the literals 30 / 12 / 1560 / 32760 come from the model config and the ``Geometry``.
+  * the literals 30 / 12 / 1560 / 32760 come from the model config and the ``Geometry``;
+  * ``inference_stream()`` (no counterpart in the reference) runs the same loop and hands the video out block by block: each
+    block is decoded by the VAE's cached decode (``decode_to_pixel(use_cache=True)``'s engine) while the next one denoises.
 """
 from __future__ import annotations
 
@@ -62,13 +64,15 @@ class CausalInferencePipeline(torch.nn.Module):
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._bufs: Dict[int, dict] = {}  # static per-block buffers, by frames per block
         self._out: Dict[int, torch.Tensor] = {}                     # static output latents, by frame count
+        self._side: Optional[torch.cuda.Stream] = None              # inference_stream: the decode stream
+        self._stage: Optional[torch.Tensor] = None                  # inference_stream: pinned uint8 staging, [2, frames, H, W, 3]
 
     def to(self, *args, **kwargs):
         return self
 
     def release_graphs(self) -> None:
         """Drop every captured block graph (and the static buffers they read)."""
-        torch.cuda.synchronize(self.device)
+        torch.cuda.synchronize(self.device)                           # the decode stream of inference_stream included
         self._graphs.clear()
         self._bufs.clear()
         self._out.clear()
@@ -139,10 +143,12 @@ class CausalInferencePipeline(torch.nn.Module):
         self.generator.flow(x, t, start, write, vis, self.kv_cache1, self.crossattn_cache)
         self.generator.set_cache_ends(self.kv_cache1, start + x.shape[0], le)
 
-    def inference(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
-                  return_latents: bool = False, profile: bool = False, low_memory: bool = False):
-        """noise [1, F, 16, h, w]; initial_latent [1, n, 16, h, w] or None.  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the
-        latents [1, n + F, 16, h, w]).  low_memory is accepted and has no effect (everything stays resident)."""
+    def _blocks(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None):
+        """The denoising loop ``inference()`` and ``inference_stream()`` share (causal_inference.py:82-211), as a generator over
+        its hand-over points: yields ``(start_frame, n_frames, output)`` once after the ``initial_latent`` frames are in the
+        static output latent and the cache (``n_frames`` = 0 without one), then after every block's launches -- the block's
+        frames ``output[0, start:start + n_frames]`` are complete in stream order on the current stream.  The caller holds
+        ``torch.no_grad()`` around every resumption."""
         batch_size, num_frames, num_channels, height, width = noise.shape
         assert batch_size == 1, "batch size 1 (as every reference entry point)"
         assert (num_channels, height, width) == (16, self.geometry.lat_h, self.geometry.lat_w), tuple(noise.shape)
@@ -150,88 +156,103 @@ class CausalInferencePipeline(torch.nn.Module):
         num_input_frames = initial_latent.shape[1] if initial_latent is not None else 0
         num_output_frames = num_frames + num_input_frames
         dev = self.device
+        conditional_dict = self.text_encoder(text_prompts=text_prompts)
+
+        if self.kv_cache1 is None:
+            self.kv_cache1 = self.generator.new_kv_cache()
+            self.crossattn_cache = self.generator.new_crossattn_cache()
+        else:                                                             # :113-123
+            for blk in self.crossattn_cache:
+                blk["is_init"] = False
+            self.generator.set_cache_ends(self.kv_cache1, 0, 0)
+        pe = conditional_dict["prompt_embeds"]
+        self.crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
+
+        noise_bf = noise.to(device=dev, dtype=torch.bfloat16).contiguous()
+        output = self._output(num_output_frames)
+        output.zero_()
+        current_start_frame = 0
+        if initial_latent is not None:                                    # :126-159
+            init = initial_latent.to(device=dev, dtype=torch.bfloat16)
+            F = self.num_frame_per_block
+            if self.independent_first_frame:
+                assert (num_input_frames - 1) % F == 0
+                num_input_blocks = (num_input_frames - 1) // F
+                output[:, :1] = init[:, :1]
+                self._context_forward(init[0, :1], current_start_frame)
+                current_start_frame += 1
+            else:
+                assert num_input_frames % F == 0
+                num_input_blocks = num_input_frames // F
+            for _ in range(num_input_blocks):
+                ref = init[:, current_start_frame:current_start_frame + F]
+                output[:, current_start_frame:current_start_frame + F] = ref
+                self._context_forward(ref[0], current_start_frame)
+                current_start_frame += F
+        yield 0, current_start_frame, output
+
+        scalars = self._step_scalars()
+        n = len(scalars[0])
+        draws = iter(self.renoise_override) if self.renoise_override is not None else None
+        for F in schedule:
+            s = current_start_frame
+            b = self._block_buffers(F)
+            write, vis, le = self.generator.slots(self.kv_cache1, s, F)
+            b["x"].copy_(noise_bf[0, s - num_input_frames:s - num_input_frames + F])
+            for i in range(n - 1):                                        # the reference's torch.randn_like draws, in order
+                if draws is not None:
+                    b["bank"][i].copy_(next(draws).reshape(b["bank"][i].shape))
+                else:
+                    b["bank"][i].normal_(0.0, 1.0, generator=self.noise_generator)
+            out_blk = output[0, s:s + F]
+            key = (s, F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), num_output_frames, tuple(write),
+                   tuple(vis))
+            g = self._graphs.get(key)
+            if g is not None:
+                g.replay()
+            else:
+                self._run_block(b, out_blk, s, write, vis, scalars)      # first use: the real work, eagerly ...
+                if self.use_graphs:                                       # ... then the same launches into the block's graph
+                    torch.cuda.synchronize(dev)
+                    g = torch.cuda.CUDAGraph()
+                    self.graph_captures += 1
+                    with torch.cuda.graph(g):
+                        self._run_block(b, out_blk, s, write, vis, scalars)
+                    self._graphs[key] = g
+            self.generator.set_cache_ends(self.kv_cache1, s + F, le)
+            current_start_frame += F
+            yield s, F, output
+
+    def inference(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
+                  return_latents: bool = False, profile: bool = False, low_memory: bool = False):
+        """noise [1, F, 16, h, w]; initial_latent [1, n, 16, h, w] or None.  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the
+        latents [1, n + F, 16, h, w]).  low_memory is accepted and has no effect (everything stays resident)."""
+        dev = self.device
         with torch.no_grad():
-            conditional_dict = self.text_encoder(text_prompts=text_prompts)
             if profile:
                 ev = lambda: torch.cuda.Event(enable_timing=True)
                 init_start, init_end, diffusion_start, diffusion_end, vae_start, vae_end = (ev() for _ in range(6))
                 block_times = []
                 init_start.record()
 
-            if self.kv_cache1 is None:
-                self.kv_cache1 = self.generator.new_kv_cache()
-                self.crossattn_cache = self.generator.new_crossattn_cache()
-            else:                                                             # :113-123
-                for blk in self.crossattn_cache:
-                    blk["is_init"] = False
-                self.generator.set_cache_ends(self.kv_cache1, 0, 0)
-            pe = conditional_dict["prompt_embeds"]
-            self.crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
-
-            noise_bf = noise.to(device=dev, dtype=torch.bfloat16).contiguous()
-            output = self._output(num_output_frames)
-            output.zero_()
-            current_start_frame = 0
-            if initial_latent is not None:                                    # :126-159
-                init = initial_latent.to(device=dev, dtype=torch.bfloat16)
-                F = self.num_frame_per_block
-                if self.independent_first_frame:
-                    assert (num_input_frames - 1) % F == 0
-                    num_input_blocks = (num_input_frames - 1) // F
-                    output[:, :1] = init[:, :1]
-                    self._context_forward(init[0, :1], current_start_frame)
-                    current_start_frame += 1
-                else:
-                    assert num_input_frames % F == 0
-                    num_input_blocks = num_input_frames // F
-                for _ in range(num_input_blocks):
-                    ref = init[:, current_start_frame:current_start_frame + F]
-                    output[:, current_start_frame:current_start_frame + F] = ref
-                    self._context_forward(ref[0], current_start_frame)
-                    current_start_frame += F
+            blocks = self._blocks(noise, text_prompts, initial_latent)
+            _, _, output = next(blocks)                                   # text encoder, caches, the initial_latent forwards
 
             if profile:
                 init_end.record()
                 torch.cuda.synchronize(dev)
                 diffusion_start.record()
+                block_start = ev()
+                block_start.record()
 
-            scalars = self._step_scalars()
-            n = len(scalars[0])
-            draws = iter(self.renoise_override) if self.renoise_override is not None else None
-            for F in schedule:
+            for _ in blocks:
                 if profile:
-                    block_start, block_end = ev(), ev()
-                    block_start.record()
-                s = current_start_frame
-                b = self._block_buffers(F)
-                write, vis, le = self.generator.slots(self.kv_cache1, s, F)
-                b["x"].copy_(noise_bf[0, s - num_input_frames:s - num_input_frames + F])
-                for i in range(n - 1):                                        # the reference's torch.randn_like draws, in order
-                    if draws is not None:
-                        b["bank"][i].copy_(next(draws).reshape(b["bank"][i].shape))
-                    else:
-                        b["bank"][i].normal_(0.0, 1.0, generator=self.noise_generator)
-                out_blk = output[0, s:s + F]
-                key = (s, F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), num_output_frames, tuple(write),
-                       tuple(vis))
-                g = self._graphs.get(key)
-                if g is not None:
-                    g.replay()
-                else:
-                    self._run_block(b, out_blk, s, write, vis, scalars)      # first use: the real work, eagerly ...
-                    if self.use_graphs:                                       # ... then the same launches into the block's graph
-                        torch.cuda.synchronize(dev)
-                        g = torch.cuda.CUDAGraph()
-                        self.graph_captures += 1
-                        with torch.cuda.graph(g):
-                            self._run_block(b, out_blk, s, write, vis, scalars)
-                        self._graphs[key] = g
-                self.generator.set_cache_ends(self.kv_cache1, s + F, le)
-                if profile:
+                    block_end = ev()
                     block_end.record()
                     torch.cuda.synchronize(dev)
                     block_times.append(block_start.elapsed_time(block_end))
-                current_start_frame += F
+                    block_start = ev()
+                    block_start.record()
 
             if profile:
                 diffusion_end.record()
@@ -259,3 +280,85 @@ class CausalInferencePipeline(torch.nn.Module):
         if return_latents:
             return video, latents
         return video
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _staging(self, n_frames: int) -> torch.Tensor:
+        """Two pinned host buffers of n_frames uint8 frames each, used alternately by consecutive yields of inference_stream."""
+        g = self.geometry
+        st = self._stage
+        if st is None or st.shape[1] < n_frames:
+            st = self._stage = torch.empty(2, n_frames, 8 * g.lat_h, 8 * g.lat_w, 3, dtype=torch.uint8, pin_memory=True)
+        return st
+
+    def _decode_block(self, out_blk: torch.Tensor, fmt: str, compute, side, slot: int, max_frames: int):
+        """Queue the streamed decode of one block's latent frames on ``side`` behind everything ``compute`` holds now; returns
+        (frames, ready event).  uint8 frames land in pinned staging buffer ``slot``; float frames stay on the device."""
+        if side is not compute:
+            # Everything that writes out_blk is on `compute` before this event.  The launches that follow it there (block k+1, the
+            # next call's setup excepted: the generator drains `side` before it ends) write OTHER frame slices of the static
+            # output latent and never this one, so `side` may read it while `compute` runs on.
+            done = torch.cuda.Event()
+            done.record(compute)
+            side.wait_event(done)
+        with torch.cuda.stream(side):
+            px = self.vae.model.decode_stream(out_blk, self.vae.mean, self.vae.std, out_format=fmt)
+            if fmt == "uint8":
+                frames = self._staging(max_frames)[slot, :px.shape[0]]
+                frames.copy_(px, non_blocking=True)
+            else:
+                frames = (px * 0.5 + 0.5).clamp(0, 1)                     # what inference() does to the decoded video
+                frames.record_stream(compute)                             # the consumer uses it there
+            ready = torch.cuda.Event()
+            ready.record(side)
+        return frames, ready
+
+    def inference_stream(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
+                         output: str = "uint8", overlap: bool = True):
+        """``inference()`` handing the video out block by block: a generator of ``(first_pixel_frame_index, frames)``, once for
+        the ``initial_latent`` frames (if any) and once per denoised block, as soon as that block's pixels exist.
+
+        ``output="uint8"``: frames are host uint8 [T, 8h, 8w, 3] (the video writer's layout, the caller's to keep);
+        ``"float"``: device float32 [T, 3, 8h, 8w] in [0, 1].  Concatenated they are ``inference()``'s video bit for bit (for
+        uint8: its ``(video * 255.0).clamp(0, 255).to(torch.uint8)`` conversion).  Same block graphs, buffers, re-noise bank and
+        cache bookkeeping as ``inference()``; each block is decoded by the VAE's cached decode (``VaeEngine.decode_stream``),
+        eagerly.  ``overlap=True`` decodes block k on a second stream while the first one denoises block k + 1 and yields block
+        k once block k + 1 is queued; ``overlap=False`` runs the same work on the current stream, in order.  A call starts a
+        new decoded video (``vae.model.clear_cache()``); the generator drains the decode stream when it finishes or is closed."""
+        if output not in ("uint8", "float"):
+            raise ValueError(f"output {output!r}: 'uint8' or 'float'")
+        compute = torch.cuda.current_stream(self.device)
+        if overlap and self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        side = self._side if overlap else compute
+        max_frames = 4 * max(self.num_frame_per_block, initial_latent.shape[1] if initial_latent is not None else 1)
+        self.vae.model.clear_cache()
+
+        def finish(first_px, frames, ready):
+            ready.synchronize()                                           # this block's event only, never the device
+            return first_px, (frames.clone() if output == "uint8" else frames)
+
+        blocks = self._blocks(noise, text_prompts, initial_latent)
+        pending, k = None, 0
+        try:
+            while True:
+                with torch.no_grad():
+                    step = next(blocks, None)                             # queues block k (or the initial frames) on `compute`
+                    if step is None:
+                        break
+                    s, F, lat = step
+                    if F == 0:                                            # no initial_latent
+                        continue
+                    cur = (0 if s == 0 else 1 + 4 * (s - 1),) + self._decode_block(lat[0, s:s + F], output, compute, side, k & 1,
+                                                                                  max_frames)
+                    k += 1
+                if not overlap:
+                    yield finish(*cur)
+                    continue
+                if pending is not None:                                   # block k is queued behind it: hand out block k - 1
+                    yield finish(*pending)
+                pending = cur
+            if pending is not None:
+                yield finish(*pending)
+        finally:
+            blocks.close()
+            side.synchronize()                                            # the static output latent is the next call's too

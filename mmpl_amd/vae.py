@@ -24,9 +24,15 @@ class VaeEngine:
         self._h = h
         self._weights: List[torch.Tensor] = []
         self._ws: Dict[int, torch.Tensor] = {}
+        # the streamed video (decode_stream): its own handle and its own workspace, which decode / encode never touch
+        self._stream = None
+        self._stream_ws: Optional[torch.Tensor] = None
 
     def __del__(self):
         try:
+            if getattr(self, "_stream", None):
+                self._lib.mmpl_vae_stream_destroy(self._stream)
+                self._stream = None
             if getattr(self, "_h", None):
                 self._lib.mmpl_vae_destroy(self._h)
                 self._h = None
@@ -34,7 +40,41 @@ class VaeEngine:
             pass
 
     def clear_cache(self):
-        """API parity with WanVAE_.clear_cache (vae.py:602-609): every decode/encode call starts from a cleared cache."""
+        """WanVAE_.clear_cache (vae.py:602-609): ends the streamed video, the next ``decode_stream`` call decodes a first frame.
+        The one-shot ``decode`` / ``encode`` start from a cleared cache of their own on every call and do not need it."""
+        if self._stream is not None:
+            _lib.check(self._lib.mmpl_vae_stream_reset(self._stream), "mmpl_vae_stream_reset")
+
+    def decode_stream(self, latent: torch.Tensor, mean, std, out_format: str = "float") -> torch.Tensor:
+        """WanVAE_.cached_decode (vae.py:571-593): latent [F, 16, h, w] = the NEXT F latent frames of the streamed video ->
+        1 + 4(F-1) pixel frames if they are the video's first (after ``clear_cache()``), else 4F, on the current stream.
+        out_format "float": float32 [T, 3, 8h, 8w] in [-1, 1], bit-identical to the same frames of a one-shot ``decode``;
+        "uint8": [T, 8h, 8w, 3], the video writer's layout."""
+        if out_format not in ("float", "uint8"):
+            raise ValueError(f"out_format {out_format!r}: 'float' or 'uint8'")
+        z = latent.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        F = z.shape[0]
+        assert F >= 1 and z.shape[1:] == (16, self.lat_h, self.lat_w)
+        if self._stream is None:
+            h = C.c_void_p()
+            _lib.check(self._lib.mmpl_vae_stream_create(self._h, C.byref(h)), "mmpl_vae_stream_create")
+            self._stream = h
+        if self._stream_ws is None:
+            self._stream_ws = torch.empty(self._lib.mmpl_vae_workspace_bytes(self._h, 0), dtype=torch.uint8, device=self.device)
+        ws = self._stream_ws
+        H, W = 8 * self.lat_h, 8 * self.lat_w
+        # room for the most this call can produce; the library reports what it wrote (a video's first latent yields 1 frame, not 4)
+        if out_format == "uint8":
+            out = torch.empty(4 * F, H, W, 3, dtype=torch.uint8, device=self.device)
+        else:
+            out = torch.empty(4 * F, 3, H, W, dtype=torch.float32, device=self.device)
+        m, inv = self._scales(mean, std)
+        n_out = C.c_int(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mmpl_vae_stream_decode(self._stream, _lib.ptr(z), F, m, inv, _lib.ptr(out), int(out_format == "uint8"),
+                                                        C.byref(n_out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "mmpl_vae_stream_decode")
+        return out[:n_out.value]
 
     @staticmethod
     def _repack(name: str, t: torch.Tensor) -> torch.Tensor:

@@ -350,10 +350,20 @@ class WanVAEWrapper(torch.nn.Module):
 
     def encode_to_latent(self, pixel: torch.Tensor) -> torch.Tensor:
         """pixel [B, 3, T, H, W] in [-1, 1] -> latent [B, F, 16, h, w] float32 (normalised mu)."""
+        self.model.clear_cache()                                     # WanVAE_.encode ends with clear_cache() (vae.py:542)
         return torch.stack([self.model.encode(u, self.mean, self.std).float() for u in pixel], dim=0)
 
     def decode_to_pixel(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
-        """latent [B, F, 16, h, w] -> pixel [B, T, 3, 8h, 8w] float32 clamped to [-1, 1]."""
+        """latent [B, F, 16, h, w] -> pixel [B, T, 3, 8h, 8w] float32 clamped to [-1, 1].
+
+        ``use_cache=True`` (WanVAE_.cached_decode, batch 1): the latent frames CONTINUE the video of the earlier cached calls --
+        every one of them yields 4 pixel frames unless it is the first since ``self.model.clear_cache()``.  ``use_cache=False``
+        decodes a whole video and, as the reference's ``decode`` clears the cache before and after (vae.py:546, 568), ends a
+        cached one."""
+        if use_cache:
+            assert latent.shape[0] == 1, "Batch size must be 1 when using cache"
+            return self.model.decode_stream(latent[0], self.mean, self.std).float().clamp_(-1, 1).unsqueeze(0)
+        self.model.clear_cache()
         return torch.stack([self.model.decode(u, self.mean, self.std).float().clamp_(-1, 1) for u in latent], dim=0)
 
 
