@@ -276,6 +276,37 @@ int mmpl_vae_stream_reset(MmplVaeStream* s);
 int mmpl_vae_stream_decode(MmplVaeStream* s, const void* z, int n_frames, const float* mean, const float* inv_std, void* out,
                            int out_format, int* n_px_frames_out, void* workspace, size_t workspace_bytes, mmpl_stream_t stream);
 
+/* ---- TAEHV preview decoder: the decoder half of demo_utils/taehv.py (TAEHV.decode_video, checkpoint taew2_1.pth), the cheap
+ * decoder for block-wise few-step output ----
+ * Weights: mmpl_taehv_num_weights() dev pointers in the order of mmpl_taehv_weight_name(i) = exactly the reference's
+ * "decoder.*" state-dict keys.  Every "*.weight" is bound in the fragment-major packing described above for "<conv>.weight.frag"
+ * (Cin 16 zero-padded to 32 for decoder.1, Cout 3 zero-padded to 16 for decoder.22; a MemBlock's first conv keeps the reference's
+ * input-channel order [x, past]); biases are bf16 [Cout] (decoder.22.bias zero-padded to 4).  mmpl_amd/taehv.py is the
+ * reference packer.  mmpl_taehv_create and mmpl_taehv_workspace_bytes make no HIP call.
+ * mmpl_taehv_decode CONTINUES the current video: z dev bf16 [n_frames, 16, lat_h, lat_w] in the pipeline's normalised latent space
+ * (no mean / std) are its NEXT n_frames >= 1 latent frames; the first call after create / reset treats its first latent as the
+ * video's first (zero memories).  Every call writes 4 n_frames pixel frames -- untrimmed, like the reference's decode_video -- and
+ * reports the count in *n_px_frames_out (may be NULL).  out_format 0: dev float32 [T, 3, 8 lat_h, 8 lat_w], the network's raw
+ * output (nominally [0, 1], unclamped, bf16-rounded); out_format 1: dev uint8 [T, 8 lat_h, 8 lat_w, 3] = (x.clamp(0, 1) * 255)
+ * truncated, from the same bf16 value.  A video decoded in any split is bit-identical to the one-shot decode.
+ * workspace: caller-owned, mmpl_taehv_workspace_bytes(v) bytes, holds the nine MemBlock memories: it must be the SAME pointer
+ * from one reset to the next (another pointer or a smaller size is an error, never a silent restart) and nothing else may write
+ * it in between.  It is cleared (asynchronously, on `stream`) by the first decode after create / reset only.  All argument
+ * checks run before the first HIP call.  Everything is queued on `stream`: no host synchronisation, no read-back, no allocation,
+ * and the launch sequence and every address are the same from call to call, so a call (not a video's first) can be captured
+ * into a hipGraph and replayed as "the next latent frames". */
+typedef struct MmplTaehv MmplTaehv;
+int mmpl_taehv_num_weights(void);
+const char* mmpl_taehv_weight_name(int i);
+int mmpl_taehv_create(int lat_h, int lat_w, MmplTaehv** out);
+void mmpl_taehv_destroy(MmplTaehv* v);
+int mmpl_taehv_bind_weights(MmplTaehv* v, const void* const* dev_ptrs, int n);
+size_t mmpl_taehv_workspace_bytes(MmplTaehv* v);
+/* The next mmpl_taehv_decode starts a new video (and may bind another workspace).  Host-side only. */
+int mmpl_taehv_reset(MmplTaehv* v);
+int mmpl_taehv_decode(MmplTaehv* v, const void* z, int n_frames, void* out, int out_format, int* n_px_frames_out, void* workspace,
+                      size_t workspace_bytes, mmpl_stream_t stream);
+
 /* ---- umT5 text encoder (wan/modules/t5.py:267-312 behind WanTextEncoder, utils/wan_wrapper.py:15-51) ----
  * Weights (bf16 dev pointers): [token_embedding.weight, norm.weight] then per block
  * [norm1.weight, pack:attn.{q,k,v}.weight[3*dim_attn,dim], attn.o.weight, pos_embedding.embedding.weight[num_buckets,heads],

@@ -15,6 +15,8 @@ SYMBOLS = [
     "mmpl_vae_num_weights", "mmpl_vae_weight_name", "mmpl_vae_create", "mmpl_vae_destroy", "mmpl_vae_bind_weights",
     "mmpl_vae_workspace_bytes", "mmpl_vae_decode", "mmpl_vae_encode",
     "mmpl_vae_stream_create", "mmpl_vae_stream_destroy", "mmpl_vae_stream_reset", "mmpl_vae_stream_decode",
+    "mmpl_taehv_num_weights", "mmpl_taehv_weight_name", "mmpl_taehv_create", "mmpl_taehv_destroy", "mmpl_taehv_bind_weights",
+    "mmpl_taehv_workspace_bytes", "mmpl_taehv_reset", "mmpl_taehv_decode",
     "mmpl_t5_num_weights", "mmpl_t5_create", "mmpl_t5_destroy", "mmpl_t5_bind_weights", "mmpl_t5_workspace_bytes", "mmpl_t5_encode",
     "mmpl_i2v_img_proj_workspace_bytes", "mmpl_i2v_img_proj", "mmpl_i2v_img_kv", "mmpl_i2v_cross_attn_workspace_bytes", "mmpl_i2v_cross_attn",
     "mmpl_profile_enable", "mmpl_profile_read", "mmpl_last_error", "mmpl_version",
@@ -143,6 +145,16 @@ def _bind_vae(lib):
     lib.mmpl_vae_stream_destroy.restype = None
     lib.mmpl_vae_stream_reset.argtypes = [vp]
     lib.mmpl_vae_stream_decode.argtypes = [vp, vp, ci, fp, fp, vp, ci, C.POINTER(ci), vp, sz, vp]
+    lib.mmpl_taehv_weight_name.argtypes = [ci]
+    lib.mmpl_taehv_weight_name.restype = C.c_char_p
+    lib.mmpl_taehv_create.argtypes = [ci, ci, C.POINTER(vp)]
+    lib.mmpl_taehv_destroy.argtypes = [vp]
+    lib.mmpl_taehv_destroy.restype = None
+    lib.mmpl_taehv_bind_weights.argtypes = [vp, C.POINTER(vp), ci]
+    lib.mmpl_taehv_workspace_bytes.argtypes = [vp]
+    lib.mmpl_taehv_workspace_bytes.restype = sz
+    lib.mmpl_taehv_reset.argtypes = [vp]
+    lib.mmpl_taehv_decode.argtypes = [vp, vp, ci, vp, ci, C.POINTER(ci), vp, sz, vp]
 
 
 def check(rc: int, what: str = "") -> None:

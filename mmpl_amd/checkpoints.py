@@ -6,6 +6,8 @@
     (Wan_fps_inference_1gpu.py:66-68)
   * ``Wan2.1_VAE.pth`` (wan/modules/vae.py:628-634) and ``models_t5_umt5-xxl-enc-bf16.pth`` (utils/wan_wrapper.py:25-28):
     plain pickled state dicts
+  * ``taew2_1.pth`` (demo_utils/taehv.py:191-193): the TAEHV preview autoencoder, a plain pickled state dict with
+    ``encoder.N...`` / ``decoder.N...`` keys
 
 Everything returns CPU tensors keyed like the reference modules' ``state_dict()``; the engines repack them for the HIP kernels.
 """
@@ -96,6 +98,17 @@ def read_state_dict(path: str) -> Dict[str, torch.Tensor]:
     if not isinstance(sd, dict) or not all(isinstance(v, torch.Tensor) for v in sd.values()):
         raise ValueError(f"{path}: not a flat state dict")
     return sd
+
+
+def read_taehv(path: str) -> Dict[str, torch.Tensor]:
+    """The DECODER of a ``taew2_1.pth``-style file: its ``decoder.*`` tensors under their own keys (what ``TaehvEngine.load_state_dict``
+    takes; the encoder half is not used on the streaming path).  TGrow weights are left as stored: the engine applies the
+    reference's ``patch_tgrow_layers`` rule when it binds them."""
+    sd = read_state_dict(path)
+    out = {k: v for k, v in sd.items() if k.startswith("decoder.")}
+    if not out:
+        raise ValueError(f"{path}: no 'decoder.*' tensors (not a TAEHV checkpoint)")
+    return out
 
 
 def infer_t5_config(sd: Dict[str, torch.Tensor]) -> dict:

@@ -70,6 +70,30 @@ def stream_refusal(args, fewstep: bool):
     return None
 
 
+def preview_refusal(args):
+    """Why --preview_vae cannot run this command line (None = it can, or it was not asked for): the tiny TAEHV decoder serves the
+    block-wise output only (CausalInferencePipeline.inference_stream(decoder="preview")); a whole video is decoded by the Wan VAE."""
+    if getattr(args, "preview_vae", None) is not None and not getattr(args, "stream", False):
+        return ("--preview_vae: the tiny preview decoder (TAEHV, taew2_1.pth) decodes the live frames of --stream only; "
+                "add --stream, or drop --preview_vae to decode with the Wan VAE")
+    return None
+
+
+def build_preview_vae(args, dev, geo):
+    """TAEHVWrapper for --preview_vae [PATH]: the checkpoint at PATH (default ../wan_models/taew2_1.pth), or seeded weights with --synthetic."""
+    from .wan_wrapper import TAEHVWrapper
+    if args.synthetic:
+        from .synthetic import taehv_state_dict
+        return TAEHVWrapper(geometry=geo, device=dev, state_dict=taehv_state_dict(seed=4))
+    path = args.preview_vae or None
+    if path is not None and not os.path.exists(path):
+        raise SystemExit(f"--preview_vae {path}: no such file")
+    w = TAEHVWrapper(geometry=geo, device=dev, pretrained_path=path)
+    if not w.model._weights:
+        raise SystemExit("--preview_vae: no TAEHV checkpoint found (pass its path, e.g. --preview_vae ../wan_models/taew2_1.pth)")
+    return w
+
+
 def build_fewstep_pipeline(config, args, dev, geo, mcfg):
     """WanDiffusionWrapper + CausalInferencePipeline (Wan_fps_inference_1gpu.py:61), then `independent_first_frame = False`
     as the entry script sets it (:73)."""
@@ -83,7 +107,8 @@ def build_fewstep_pipeline(config, args, dev, geo, mcfg):
         gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
         enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
         vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
-    pipe = CausalInferencePipeline(config, dev, generator=gen, text_encoder=enc, vae=vae)
+    preview = build_preview_vae(args, dev, geo) if getattr(args, "preview_vae", None) is not None else None
+    pipe = CausalInferencePipeline(config, dev, generator=gen, text_encoder=enc, vae=vae, preview_vae=preview)
     if args.checkpoint_path:
         from .checkpoints import read_mmpl_checkpoint
         pipe.generator.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
@@ -121,6 +146,9 @@ def main(argv=None):
     ap.add_argument("--stream", action="store_true",
                     help="few-step configs: decode and hand out the video block by block while the next block denoises "
                          "(CausalInferencePipeline.inference_stream); prints the time to the first frames and per block")
+    ap.add_argument("--preview_vae", type=str, nargs="?", const="", default=None, metavar="PATH",
+                    help="with --stream: decode the live frames with the tiny TAEHV preview decoder (taew2_1.pth at PATH, default "
+                         "../wan_models/taew2_1.pth; seeded weights with --synthetic) instead of the Wan VAE")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -128,6 +156,9 @@ def main(argv=None):
     config = load_config(args.config_path)
     fewstep = is_fewstep(config)
     why = stream_refusal(args, fewstep)
+    if why is not None:
+        ap.error(why)
+    why = preview_refusal(args)
     if why is not None:
         ap.error(why)
     if fewstep:
@@ -296,7 +327,8 @@ def _main_fewstep(config, args, dev, geo, mcfg):
         if args.stream:
             import time
             parts, t0 = [], time.perf_counter()
-            for first, frames in pipe.inference_stream(noise.to(dev), [prompt], output="uint8"):
+            decoder = "preview" if pipe.preview_vae is not None else "vae"
+            for first, frames in pipe.inference_stream(noise.to(dev), [prompt], output="uint8", decoder=decoder):
                 print(f"[mmpl_amd.cli] few-step prompt {idx}: frames {first}..{first + frames.shape[0] - 1} after "
                       f"{time.perf_counter() - t0:.3f} s" + (" (time to the first frames)" if not parts else ""))
                 parts.append(frames)

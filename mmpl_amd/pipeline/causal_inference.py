@@ -14,7 +14,8 @@ What changed underneath:
     into a static bank the graph reads: the same device generator state gives the reference's draws bit for bit;
   * the literals 30 / 12 / 1560 / 32760 come from the model config and the ``Geometry``;
   * ``inference_stream()`` (no counterpart in the reference) runs the same loop and hands the video out block by block: each
-    block is decoded by the VAE's cached decode (``decode_to_pixel(use_cache=True)``'s engine) while the next one denoises.
+    block is decoded by the VAE's cached decode (``decode_to_pixel(use_cache=True)``'s engine) while the next one denoises --
+    or, with ``decoder="preview"``, by the tiny TAEHV decoder handed in as ``preview_vae`` (``TAEHVWrapper``).
 """
 from __future__ import annotations
 
@@ -26,7 +27,7 @@ from ..wan_wrapper import WanDiffusionWrapper, WanTextEncoder, WanVAEWrapper
 
 
 class CausalInferencePipeline(torch.nn.Module):
-    def __init__(self, args, device, generator=None, text_encoder=None, vae=None):
+    def __init__(self, args, device, generator=None, text_encoder=None, vae=None, preview_vae=None):
         super().__init__()
         self.device = torch.device(device)
         self.generator = WanDiffusionWrapper(**getattr(args, "model_kwargs", {}), is_causal=True,
@@ -34,6 +35,7 @@ class CausalInferencePipeline(torch.nn.Module):
         self.geometry = self.generator.geometry
         self.text_encoder = WanTextEncoder(device=device) if text_encoder is None else text_encoder
         self.vae = WanVAEWrapper(geometry=self.geometry, device=device) if vae is None else vae
+        self.preview_vae = preview_vae    # optional TAEHVWrapper: inference_stream(decoder="preview")
 
         self.scheduler = self.generator.get_scheduler()
         self.denoising_step_list = torch.tensor(args.denoising_step_list, dtype=torch.long)
@@ -290,9 +292,10 @@ class CausalInferencePipeline(torch.nn.Module):
             st = self._stage = torch.empty(2, n_frames, 8 * g.lat_h, 8 * g.lat_w, 3, dtype=torch.uint8, pin_memory=True)
         return st
 
-    def _decode_block(self, out_blk: torch.Tensor, fmt: str, compute, side, slot: int, max_frames: int):
+    def _decode_block(self, out_blk: torch.Tensor, fmt: str, compute, side, slot: int, max_frames: int, preview: bool = False):
         """Queue the streamed decode of one block's latent frames on ``side`` behind everything ``compute`` holds now; returns
-        (frames, ready event).  uint8 frames land in pinned staging buffer ``slot``; float frames stay on the device."""
+        (frames, ready event).  uint8 frames land in pinned staging buffer ``slot``; float frames stay on the device.
+        ``preview``: the tiny decoder, whose output is in [0, 1] already and is handed out as it is (clamped)."""
         if side is not compute:
             # Everything that writes out_blk is on `compute` before this event.  The launches that follow it there (block k+1, the
             # next call's setup excepted: the generator drains `side` before it ends) write OTHER frame slices of the static
@@ -301,19 +304,23 @@ class CausalInferencePipeline(torch.nn.Module):
             done.record(compute)
             side.wait_event(done)
         with torch.cuda.stream(side):
-            px = self.vae.model.decode_stream(out_blk, self.vae.mean, self.vae.std, out_format=fmt)
+            if preview:
+                px = self.preview_vae.decode_stream(out_blk, out_format=fmt)
+            else:
+                px = self.vae.model.decode_stream(out_blk, self.vae.mean, self.vae.std, out_format=fmt)
             if fmt == "uint8":
                 frames = self._staging(max_frames)[slot, :px.shape[0]]
                 frames.copy_(px, non_blocking=True)
             else:
-                frames = (px * 0.5 + 0.5).clamp(0, 1)                     # what inference() does to the decoded video
+                # the Wan VAE: what inference() does to the decoded video; the preview decoder's [0, 1] output needs the clamp only
+                frames = px.clamp(0, 1) if preview else (px * 0.5 + 0.5).clamp(0, 1)
                 frames.record_stream(compute)                             # the consumer uses it there
             ready = torch.cuda.Event()
             ready.record(side)
         return frames, ready
 
     def inference_stream(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
-                         output: str = "uint8", overlap: bool = True):
+                         output: str = "uint8", overlap: bool = True, decoder: str = "vae"):
         """``inference()`` handing the video out block by block: a generator of ``(first_pixel_frame_index, frames)``, once for
         the ``initial_latent`` frames (if any) and once per denoised block, as soon as that block's pixels exist.
 
@@ -323,15 +330,24 @@ class CausalInferencePipeline(torch.nn.Module):
         cache bookkeeping as ``inference()``; each block is decoded by the VAE's cached decode (``VaeEngine.decode_stream``),
         eagerly.  ``overlap=True`` decodes block k on a second stream while the first one denoises block k + 1 and yields block
         k once block k + 1 is queued; ``overlap=False`` runs the same work on the current stream, in order.  A call starts a
-        new decoded video (``vae.model.clear_cache()``); the generator drains the decode stream when it finishes or is closed."""
+        new decoded video (``vae.model.clear_cache()``); the generator drains the decode stream when it finishes or is closed.
+
+        ``decoder="preview"`` decodes the blocks with ``preview_vae`` (the tiny TAEHV decoder, ``TAEHVWrapper``) instead: same
+        frame indices and counts, its own pixels -- the frames are that decoder's output clamped to [0, 1] (uint8: ``* 255``
+        truncated), not ``inference()``'s video.  The latents are the same either way."""
         if output not in ("uint8", "float"):
             raise ValueError(f"output {output!r}: 'uint8' or 'float'")
+        if decoder not in ("vae", "preview"):
+            raise ValueError(f"decoder {decoder!r}: 'vae' or 'preview'")
+        preview = decoder == "preview"
+        if preview and self.preview_vae is None:
+            raise ValueError("decoder='preview' needs a preview decoder: CausalInferencePipeline(..., preview_vae=TAEHVWrapper(...))")
         compute = torch.cuda.current_stream(self.device)
         if overlap and self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
         side = self._side if overlap else compute
         max_frames = 4 * max(self.num_frame_per_block, initial_latent.shape[1] if initial_latent is not None else 1)
-        self.vae.model.clear_cache()
+        (self.preview_vae if preview else self.vae).model.clear_cache()
 
         def finish(first_px, frames, ready):
             ready.synchronize()                                           # this block's event only, never the device
@@ -349,7 +365,7 @@ class CausalInferencePipeline(torch.nn.Module):
                     if F == 0:                                            # no initial_latent
                         continue
                     cur = (0 if s == 0 else 1 + 4 * (s - 1),) + self._decode_block(lat[0, s:s + F], output, compute, side, k & 1,
-                                                                                  max_frames)
+                                                                                  max_frames, preview)
                     k += 1
                 if not overlap:
                     yield finish(*cur)

@@ -223,6 +223,55 @@ def vae_state_dict(seed: int = 0, dtype=torch.bfloat16, device="cpu") -> "Ordere
     return sd
 
 
+# ---------------------------------------------------------------------------------------------- TAEHV preview-decoder weights
+TAEHV_CH, TAEHV_GROW = [256, 128, 64, 64], [1, 2, 2]
+
+
+def taehv_layout():
+    """(key, shape, kind) of every tensor of the TAEHV DECODER (demo_utils/taehv.py, ``TAEHV.decoder``: an nn.Sequential, so the
+    keys are its indices), in state_dict order.  kind: 'conv' | 'last' (a MemBlock's third conv) | 'grow' (TGrow's 1x1) | 'head' |
+    'bias' | 'head_bias'."""
+    out = [("decoder.1.weight", (TAEHV_CH[0], 16, 3, 3), "conv"), ("decoder.1.bias", (TAEHV_CH[0],), "bias")]
+    i = 3
+    for lvl in range(3):
+        c, cn, s = TAEHV_CH[lvl], TAEHV_CH[lvl + 1], TAEHV_GROW[lvl]
+        for _ in range(3):
+            for j, (cin, kind) in enumerate([(2 * c, "conv"), (c, "conv"), (c, "last")]):
+                out.append((f"decoder.{i}.conv.{2 * j}.weight", (c, cin, 3, 3), kind))
+                out.append((f"decoder.{i}.conv.{2 * j}.bias", (c,), "bias"))
+            i += 1
+        i += 1                                                           # nn.Upsample has no tensors
+        out.append((f"decoder.{i}.conv.weight", (c * s, c, 1, 1), "grow"))
+        out.append((f"decoder.{i + 1}.weight", (cn, c, 3, 3), "conv"))
+        i += 2
+    out += [("decoder.22.weight", (3, TAEHV_CH[3], 3, 3), "head"), ("decoder.22.bias", (3,), "head_bias")]
+    return out
+
+
+def taehv_state_dict(seed: int = 0, dtype=torch.bfloat16, device="cpu") -> "OrderedDict[str, torch.Tensor]":
+    """Seeded decoder weights in the reference's key layout.  PyTorch's default init leaves the output at std 0.02 and He init on
+    every conv drives it to std 4; this one keeps activations O(1) through all 35 convolutions and lands the output mostly inside
+    (0, 1): 3x3 convs std sqrt(2 / fan_in), a MemBlock's last conv sqrt(0.5 / fan_in) (it is added to the skip), TGrow's 1x1
+    sqrt(1 / fan_in), biases std 0.1, the head std 0.15 / sqrt(fan_in) around a bias of 0.5."""
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape, kind in taehv_layout():
+        fan_in = 1
+        for s in shape[1:]:
+            fan_in *= s
+        t = torch.randn(*shape, generator=g, device=device)
+        if kind == "bias":
+            t = 0.1 * t
+        elif kind == "head_bias":
+            t = 0.5 + 0.0 * t
+        else:
+            t = t * {"conv": math.sqrt(2.0 / fan_in), "last": math.sqrt(0.5 / fan_in), "grow": math.sqrt(1.0 / fan_in),
+                     "head": 0.15 / math.sqrt(fan_in)}[kind]
+        sd[name] = t.to(dtype)
+    return sd
+
+
 # ---------------------------------------------------------------------------------------------- umT5 encoder weights
 T5_CONFIGS = {
     "umt5-xxl": dict(vocab=256384, dim=4096, dim_attn=4096, dim_ffn=10240, num_heads=64, num_layers=24, num_buckets=32),

@@ -1,0 +1,117 @@
+"""Host-side handle of the HIP TAEHV preview decoder (libmmpl_hip.so: mmpl_taehv_*), the engine behind ``TAEHVWrapper``.
+
+The "Tiny AutoEncoder" of the reference's demo (demo_utils/taehv.py, checkpoint ``taew2_1.pth`` for Wan 2.1), decoder half: 35
+plain 2-D convolutions, causal in time with one frame of memory per MemBlock.  Takes the reference's state dict as it is
+(``decoder.N...`` keys; encoder keys are ignored), repacks the conv weights once into the kernels' fragment-major layout and
+keeps them on the GPU.  Latents are the pipeline's normalised latents (no mean / std); the output is the network's, nominally
+[0, 1], and UNTRIMMED like this reference's ``decode_video``: 4 frames per latent frame (``TAEHVWrapper`` drops the first 3).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional
+
+import torch
+
+from . import _lib
+from .vae import VaeEngine
+
+# nn.Sequential indices of the decoder's TGrow layers -> rows the model keeps (channels * stride)
+TGROW_ROWS = {"decoder.7.conv.weight": 256 * 1, "decoder.13.conv.weight": 128 * 2, "decoder.19.conv.weight": 64 * 2}
+
+
+def patch_tgrow_layers(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A checkpoint trained with a larger temporal stride has more TGrow output rows than the model: the model keeps the LAST
+    ``channels * stride`` of them (the last time steps), as the reference's loader does."""
+    out = dict(sd)
+    for key, rows in TGROW_ROWS.items():
+        if key in out and out[key].shape[0] > rows:
+            out[key] = out[key][-rows:]
+    return out
+
+
+class TaehvEngine:
+    def __init__(self, lat_h: int, lat_w: int, device="cuda:0"):
+        self.lat_h, self.lat_w = lat_h, lat_w
+        self.device = torch.device(device)
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._lib.mmpl_taehv_create(lat_h, lat_w, C.byref(h)), "mmpl_taehv_create")
+        self._h = h
+        self._weights: List[torch.Tensor] = []
+        self._ws: Optional[torch.Tensor] = None
+        self.latents_done = 0                                        # latent frames decoded since clear_cache()
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.mmpl_taehv_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @staticmethod
+    def weight_names() -> List[str]:
+        lib = _lib.load()
+        return [lib.mmpl_taehv_weight_name(i).decode() for i in range(lib.mmpl_taehv_num_weights())]
+
+    @staticmethod
+    def _repack(name: str, t: torch.Tensor) -> torch.Tensor:
+        t = t.to(torch.bfloat16)
+        if name.endswith(".bias"):
+            t = t.reshape(-1)
+            return torch.cat([t, t.new_zeros(-t.numel() % 4)])
+        cout, cin = t.shape[0], t.shape[1]
+        t = t.permute(0, 2, 3, 1).reshape(cout, -1, cin)                 # [Cout, taps, Cin]
+        cin_pad = (cin + 31) // 32 * 32
+        if cin_pad != cin:
+            t = torch.cat([t, t.new_zeros(cout, t.shape[1], cin_pad - cin)], dim=2)
+        return VaeEngine._frag_pack(t.reshape(cout, -1), cin_pad)
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        sd = patch_tgrow_layers(sd)
+        names = self.weight_names()
+        missing = [n for n in names if n not in sd]
+        if missing:
+            raise KeyError(f"TAEHV state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}")
+        ws = [self._repack(n, sd[n]).contiguous().to(self.device) for n in names]
+        arr = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+        _lib.check(self._lib.mmpl_taehv_bind_weights(self._h, arr, len(ws)), "mmpl_taehv_bind_weights")
+        self._weights = ws
+
+    def clear_cache(self) -> None:
+        """Ends the streamed video: the next ``decode_stream`` call starts from zero memories."""
+        _lib.check(self._lib.mmpl_taehv_reset(self._h), "mmpl_taehv_reset")
+        self.latents_done = 0
+
+    def decode_stream(self, latent: torch.Tensor, mean=None, std=None, out_format: str = "float") -> torch.Tensor:
+        """latent [F, 16, h, w] = the NEXT F latent frames of the streamed video -> 4F frames on the current stream.
+        "float": float32 [4F, 3, 8h, 8w], the network's output (nominally [0, 1], unclamped); "uint8": [4F, 8h, 8w, 3] =
+        ``(x.clamp(0, 1) * 255)`` truncated.  ``mean`` / ``std`` are accepted for call compatibility with ``VaeEngine`` and
+        ignored: this decoder reads the normalised latent."""
+        if out_format not in ("float", "uint8"):
+            raise ValueError(f"out_format {out_format!r}: 'float' or 'uint8'")
+        z = latent.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        F = z.shape[0]
+        assert F >= 1 and z.shape[1:] == (16, self.lat_h, self.lat_w)
+        if self._ws is None:
+            self._ws = torch.empty(self._lib.mmpl_taehv_workspace_bytes(self._h), dtype=torch.uint8, device=self.device)
+        ws = self._ws
+        H, W = 8 * self.lat_h, 8 * self.lat_w
+        if out_format == "uint8":
+            out = torch.empty(4 * F, H, W, 3, dtype=torch.uint8, device=self.device)
+        else:
+            out = torch.empty(4 * F, 3, H, W, dtype=torch.float32, device=self.device)
+        n_out = C.c_int(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mmpl_taehv_decode(self._h, _lib.ptr(z), F, _lib.ptr(out), int(out_format == "uint8"), C.byref(n_out),
+                                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "mmpl_taehv_decode")
+        self.latents_done += F
+        return out[:n_out.value]
+
+    def decode(self, latent: torch.Tensor, out_format: str = "float") -> torch.Tensor:
+        """One-shot: a whole video [F, 16, h, w] from zero memories -> 4F frames (see ``decode_stream``)."""
+        if out_format not in ("float", "uint8"):
+            raise ValueError(f"out_format {out_format!r}: 'float' or 'uint8'")
+        self.clear_cache()
+        return self.decode_stream(latent, out_format=out_format)

@@ -367,6 +367,53 @@ class WanVAEWrapper(torch.nn.Module):
         return torch.stack([self.model.decode(u, self.mean, self.std).float().clamp_(-1, 1) for u in latent], dim=0)
 
 
+class TAEHVWrapper(torch.nn.Module):
+    """The tiny preview decoder (demo_utils/taehv.py, ``taew2_1.pth``) behind ``WanVAEWrapper``'s DECODE contract, on the HIP
+    engine of mmpl_amd/taehv.py: ``decode_to_pixel`` (frames in [-1, 1]), ``model.clear_cache()``, ``model.decode_stream(...)``.
+    Decoder only: there is no ``encode_to_latent``.
+
+    The engine, like this reference's ``decode_video``, returns 4 frames per latent frame; the wrapper drops the first 3 frames of
+    a VIDEO (where upstream put the trim), so frame counts equal the Wan VAE's -- ``1 + 4(F - 1)`` for a video's first call, ``4F``
+    after -- and the two decoders are interchangeable."""
+
+    TRIM = 3
+
+    def __init__(self, geometry: Optional[Geometry] = None, device="cuda:0", state_dict: Optional[dict] = None,
+                 pretrained_path: Optional[str] = None):
+        super().__init__()
+        from .taehv import TaehvEngine
+        self.geometry = geometry or Geometry.named("480p")
+        self.model = TaehvEngine(self.geometry.lat_h, self.geometry.lat_w, device)
+        self.mean, self.std = None, None                             # the decoder reads the normalised latent
+        path = pretrained_path or f"{local_wan_path}/taew2_1.pth"
+        if state_dict is None and os.path.exists(path):
+            from .checkpoints import read_taehv
+            state_dict = read_taehv(path)
+        if state_dict is not None:
+            self.model.load_state_dict(state_dict)
+
+    def to(self, *args, **kwargs):
+        return self
+
+    def decode_stream(self, latent: torch.Tensor, out_format: str = "float") -> torch.Tensor:
+        """The engine's ``decode_stream`` ([F, 16, h, w] -> frames in the network's [0, 1] scale, "float" unclamped) minus the
+        video's first 3 frames."""
+        first = self.model.latents_done == 0                         # since ``model.clear_cache()``
+        px = self.model.decode_stream(latent, out_format=out_format)
+        return px[self.TRIM:] if first else px
+
+    def decode_to_pixel(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
+        """latent [1, F, 16, h, w] -> pixel [1, T, 3, 8h, 8w] float32 in [-1, 1] (``x * 2 - 1``, clamped).  ``use_cache=True``
+        continues the video of the earlier cached calls; ``use_cache=False`` decodes a whole video and ends a cached one."""
+        assert latent.shape[0] == 1, "Batch size must be 1"
+        if not use_cache:
+            self.model.clear_cache()
+        px = self.decode_stream(latent[0])
+        if not use_cache:
+            self.model.clear_cache()
+        return (px * 2 - 1).clamp_(-1, 1).unsqueeze(0)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Few-step (Self-Forcing / CausVid) generator: CausalWanModel behind WanDiffusionWrapper (utils/wan_wrapper.py:116-300)
 # ---------------------------------------------------------------------------------------------------------------------------------

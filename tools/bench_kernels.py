@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the two MFMA kernels on the 14B/720p shapes (dev tool).
-    python tools/bench_kernels.py attn|gemm|all|gemmref|attnref|elem|cross [--iters N]"""
+    python tools/bench_kernels.py attn|gemm|all|gemmref|attnref|elem|cross [--iters N]
+    python tools/bench_kernels.py taehv [--iters N] [--out FILE]     # the TAEHV preview decoder against the Wan VAE's streamed decode"""
 import ctypes as C
 import math
 import os
@@ -231,6 +232,70 @@ def bench_cross(iters):
                   f"{4.0 * Lq * keys * d / ms / 1e9:7.1f} TFLOP/s  sha {h}", flush=True)
 
 
+def taehv_macs_per_latent(h, w):
+    """Multiply-accumulates of the TAEHV decoder per latent frame (= 4 pixel frames), from the layer shapes as the engine runs them
+    (TGrow's 1x1 at the low resolution; the 3-channel head counted as 3 channels, not the 16 the tile computes)."""
+    ch, grow = [256, 128, 64, 64], [1, 2, 2]
+    macs, px, t = h * w * 9 * 16 * ch[0], h * w, 1
+    for lvl in range(3):
+        c = ch[lvl]
+        macs += 3 * t * px * 9 * (2 * c * c + c * c + c * c)                 # 3 MemBlocks: conv 2C->C, C->C, C->C
+        macs += t * px * c * c * grow[lvl]                                   # TGrow 1x1
+        t, px = t * grow[lvl], px * 4
+        macs += t * px * 9 * c * ch[lvl + 1]                                 # the up-sampling 3x3 conv
+    return macs + t * px * 9 * ch[3] * 3                                     # head
+
+
+def bench_taehv(iters, out_path=None):
+    """Same process, alternating, warm, event-timed: the streamed decode of one 3-latent block (not the video's first) and the
+    one-shot 21-latent decode, by mmpl_vae_stream_decode / mmpl_vae_decode and by the TAEHV engine, at 480p and 720p."""
+    from mmpl_amd.synthetic import taehv_state_dict, vae_state_dict
+    from mmpl_amd.taehv import TaehvEngine
+    from mmpl_amd.vae import VaeEngine
+    from mmpl_amd.wan_wrapper import WanVAEWrapper
+    mean, std = WanVAEWrapper.mean, WanVAEWrapper.std
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"# tools/bench_kernels.py taehv --iters {iters}: min of 3 windows of {iters} calls each, hipEvent-timed, alternating decoders")
+    for name, (h, w) in (("480p", (60, 104)), ("720p", (90, 160))):
+        vae, tiny = VaeEngine(h, w, dev), TaehvEngine(h, w, dev)
+        vae.load_state_dict(vae_state_dict(seed=2))
+        tiny.load_state_dict(taehv_state_dict(seed=4))
+        g = torch.Generator(device=dev).manual_seed(3)
+        z = torch.randn(21, 16, h, w, generator=g, device=dev).bfloat16()
+        gmac = taehv_macs_per_latent(h, w) / 1e9
+        say(f"{name} ({h} x {w} latents): TAEHV {gmac:.1f} GMAC = {2 * gmac / 1e3:.3f} TFLOP per latent frame")
+        for fmt in ("uint8",):
+            vae.clear_cache(); tiny.clear_cache()
+            vae.decode_stream(z[:3], mean, std, out_format=fmt); tiny.decode_stream(z[:3], out_format=fmt)      # the videos' first blocks
+            fv = lambda: vae.decode_stream(z[3:6], mean, std, out_format=fmt)
+            ft = lambda: tiny.decode_stream(z[3:6], out_format=fmt)
+            tv, tt = [], []
+            for _ in range(3):
+                tv.append(timeit(fv, iters)); tt.append(timeit(ft, iters))
+            v, t = min(tv), min(tt)
+            say(f"{name} streamed block of 3 latents ({fmt}, not the first): wan_vae {v:8.3f} ms   taehv {t:8.3f} ms   ratio {v / t:5.2f}x   "
+                f"taehv {3 * 2 * gmac / t:6.1f} TFLOP/s   (windows: vae {' '.join(f'{x:.3f}' for x in tv)} | taehv {' '.join(f'{x:.3f}' for x in tt)})")
+        fv = lambda: vae.decode(z, mean, std)
+        ft = lambda: tiny.decode(z)
+        n1 = max(1, iters // 4)
+        tv, tt = [], []
+        for _ in range(2):
+            tv.append(timeit(fv, n1)); tt.append(timeit(ft, n1))
+        v, t = min(tv), min(tt)
+        say(f"{name} one-shot 21 latents (float): wan_vae {v:8.2f} ms ({1 + 4 * 20} frames)   taehv {t:8.2f} ms ({4 * 21} frames)   ratio {v / t:5.2f}x   "
+            f"taehv {21 * 2 * gmac / t:6.1f} TFLOP/s")
+        del vae, tiny
+        torch.cuda.empty_cache()
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     iters = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 5
@@ -249,3 +314,5 @@ if __name__ == "__main__":
         bench_elem(iters)
     if what == "cross":
         bench_cross(iters)
+    if what == "taehv":
+        bench_taehv(iters, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
