@@ -354,6 +354,74 @@ int mmpl_clip_visual(const void* patches, int n_patch, int pk, int dim, int mlp_
                      const void* const* gw, const void* const* lw, float eps, void* out, void* workspace, size_t workspace_bytes,
                      mmpl_stream_t stream);
 
+/* ---- Kernel-level entry points of the VAE / TAEHV kernels, for kernel-level tests and tools (tests/test_vae_kernels_gpu.py,
+ * tests/test_taehv_kernels_gpu.py) ----
+ * One launch of vae_kernels.hip / taehv_kernels.hip on plain arguments, as mmpl_gemm / mmpl_layernorm are for the DiT kernels.  The
+ * product never calls them (mmpl_vae_* / mmpl_taehv_* drive the same launchers); they add no arithmetic.  All pointers are device
+ * bf16 unless stated.  Every argument check runs before the first HIP call and a rejected call launches nothing: null pointers,
+ * non-positive sizes, more than 2^31 - 1 pixels in one launch (mmpl_vae_conv / _norm / _upsample / _zprep / _mu_out; mmpl_taehv_prep: 2^25 - 1),
+ * misaligned pointers (the kernels move 8 / 16 bytes per access), more than 8 ring or norm frames, and whatever the launcher itself
+ * rejects.  The checks bound what a kernel reaches by the sizes stated in the call; "reach" below is how large
+ * each buffer must then be.
+ *
+ * mmpl_vae_conv: one CausalConv3d / Conv2d as vae.hip's conv() / cached_conv3() launch it.  tap (a, b, d) reads the padded source
+ * pixel (t * st + a, y * sy + b, x * sx + d) of output pixel (t, y, x): the caller has applied the zero padding.
+ *   src     [Tp, Hp, Wp, Cin], Tp = (To - 1) * st + kt frames; required (Ho - 1) * sy + kh <= Hp, (Wo - 1) * sx + kw <= Wp, Cin % 32 == 0.
+ *   frames  NULL, or a host array of n_frames = To + kt - 1 <= 8 pointers: source frame j is frames[j] ([Hp, Wp, Cin]) instead of
+ *           src + j * Hp * Wp * Cin (src may then be NULL).  Only conv_halo_kernel reads ring slots: any other shape is rejected.
+ *   W       [N, kt * kh * kw * Cin] (tap-major, Cin contiguous), always required.  N % 4 == 0.
+ *   Wfrag   NULL or the fragment-major packing of W (see "<conv>.weight.frag" above): Cin / 32 * ntaps * ceil(N / 16) * 16 * 32
+ *           elements, i.e. the rows are zero-padded to a multiple of 16.  With it, a 3x3(x3 | x1) stride-1 conv out of a source padded
+ *           by one pixel (Hp == Ho + 2, Wp == Wo + 2) with N % 96 == 0 or N <= 16 takes conv_halo_kernel.
+ *   bias    [N]; read four values at a time (N % 4 == 0: the decoder head's three channels are padded to four in W, Wfrag and bias).
+ *   dst     [>= dt0 + To, Hd, Wd, ldd]: output (t, y, x, n) -> (t + dt0, y + dy0, x + dx0, n); required dy0 + Ho <= Hd, dx0 + Wo <= Wd,
+ *           ldd >= N, ldd % 4 == 0.  Nothing else of dst is written.  NULL only with ngamma.
+ *   res     NULL or plain [To * Ho * Wo, ldres], ldres >= N: out = bf16(bf16(acc + bias) + res).
+ *   ngamma  NULL or [96]: the consumer's RMS_norm * nscale * gamma + SiLU of the bf16 output, written to the interior of
+ *           nframes[t] ([Ho + 2, Wo + 2, 96], t < To <= 8, host array of device pointers).  conv_halo_kernel<6> at N == 96 only.
+ *   kernel_out (host, may be NULL): the kernel the launcher chose, 1 conv_igemm_kernel<3>, 2 conv_igemm_kernel<4>,
+ *           3 conv_halo_kernel<6>, 4 conv_halo_kernel<1>; 0 when the call was rejected. */
+int mmpl_vae_conv(const void* src, const void* const* frames, int n_frames, int Cin, int Hp, int Wp, int st, int sy, int sx, int kt,
+                  int kh, int kw, const void* W, const void* Wfrag, const void* bias, int To, int Ho, int Wo, int N, void* dst, int Hd,
+                  int Wd, int ldd, int dt0, int dy0, int dx0, const void* res, int ldres, const void* ngamma, float nscale,
+                  void* const* nframes, int* kernel_out, mmpl_stream_t stream);
+/* norm_act_pad_kernel: src plain [T * H * W, C] (C % 8 == 0, C <= 1024) -> dst [>= dt0 + T, Hd, Wd, ldd] at (t + dt0, y + dy0, x + dx0),
+ * channels [0, C) (ldd >= C, ldd % 8 == 0).  gamma NULL: a copy; else [C]: RMS_norm (x / bf16(||x||), * scale, * gamma, each rounded
+ * to bf16), then SiLU if silu. */
+int mmpl_vae_norm(const void* src, int T, int H, int W, int C, const void* gamma, float scale, int silu, void* dst, int Hd, int Wd,
+                  int ldd, int dt0, int dy0, int dx0, mmpl_stream_t stream);
+/* upsample_pad_kernel: src [Ts, H, W, lds] -> nearest x2 into the interior of dst [To, Hd = 2H + 2, Wd = 2W + 2, C].  interleave 0:
+ * Ts = To, lds >= C; 1: Ts = To / 2, lds >= 2C and output frame T takes channels [(T & 1) * C, +C) of source frame T / 2. */
+int mmpl_vae_upsample(const void* src, int lds, int C, int H, int W, int To, int interleave, void* dst, int Hd, int Wd,
+                      mmpl_stream_t stream);
+/* softmax_rows_kernel: scores dev float32 [rows, ld] (cols valid) -> p bf16 [rows, ldp], columns [cols, ldp) zeroed. */
+int mmpl_vae_softmax(const void* scores, int ld, void* p, int ldp, int rows, int cols, mmpl_stream_t stream);
+/* transpose_kernel: v [rows, C] (row stride ld >= C) -> vt [C, ldt], ldt >= rows, columns [rows, ldt) zeroed. */
+int mmpl_vae_transpose(const void* v, int ld, void* vt, int ldt, int rows, int C, mmpl_stream_t stream);
+/* z_prep_kernel: z [F, 16, h, w] -> bf16(bf16(z / inv_std) + mean) -> 1x1x1 conv w2 [16, 16] + b2 [16] -> channels [0, 16) of the
+ * interior of dst [>= dt0 + F, h + 2, w + 2, 32] at frame f + dt0.  mean / inv_std: host float[16]. */
+int mmpl_vae_zprep(const void* z, int F, int h, int w, const float* mean, const float* inv_std, const void* w2, const void* b2, void* dst,
+                   int dt0, mmpl_stream_t stream);
+/* mu_out_kernel: enc [F * h * w, 32] -> rows [0, 16) of the 1x1x1 conv w1 [32, 32] + b1 [32] -> (mu - mean) * inv_std ->
+ * out dev float32 [>= f_out + F, 16, h, w] at frame f + f_out.  mean / inv_std: host float[16]. */
+int mmpl_vae_mu_out(const void* enc, const void* w1, const void* b1, const float* mean, const float* inv_std, void* out, int F,
+                    int f_out, int h, int w, mmpl_stream_t stream);
+/* taehv_conv_kernel, TaehvConvArgs (taehv_kernels.h) field for field: a 3x3 (ntaps 9) or 1x1 (ntaps 1) conv over padded frames
+ * [Ho + 2, Wo + 2, C] with a zero border, out = bf16(relu?(acc + bias? + skip?)).
+ *   src0 / src1  output frame f reads src0 + f * fs0 (C0 channels) and, when C1 > 0, src1 + f * fs1 (C1 channels) as one K axis
+ *           (elements; fs % 8 == 0).  up = 1: the source frames are [Ho / 2 + 2, Wo / 2 + 2, C] and nearest x2 is folded in.
+ *   Wfrag   the fragment-major packing of [Nw, ntaps * (C0 + C1)]: (C0 + C1) / 32 * ntaps * Nw * 32 elements, Nw % 64 == 0 or % 16.
+ *   bias    NULL or [N rounded up to 4].  N <= Nw channels are stored per pixel (N % 4 == 0).
+ *   dst     T * (Nw / Nsplit) frames [Ho + 2, Wo + 2, ldd] of stride fsd: channel n of frame f -> frame f * (Nw / Nsplit) + n / Nsplit,
+ *           channel n % Nsplit; interiors only.  ldd >= min(N, Nsplit).
+ *   skip    NULL or T frames [Ho + 2, Wo + 2, Nw] of stride fss (N == Nw); keep: NULL or one such frame, receives the interior of
+ *           the skip of frame T - 1. */
+int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long fs1, int C0, int C1, int up, int ntaps,
+                    const void* Wfrag, const void* bias, int Nw, int N, int T, int Ho, int Wo, void* dst, long long fsd, int ldd,
+                    int Nsplit, int relu, const void* skip, long long fss, void* keep, mmpl_stream_t stream);
+/* taehv_prep_kernel: z [16, h, w] -> bf16(tanh(z / 3) * 3) -> channels [0, 16) of the interior of dst [h + 2, w + 2, 32] (16-byte aligned). */
+int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream);
+
 /* Optional per-kernel-class hipEvent timing (bench.py's live roofline numbers; off by default, not thread-safe).
  * kinds: 0 gemm, 1 self-attention, 2 cross-attention, 3 layernorm, 4 qk-norm/rope/kv-write, 5 elementwise, 6 cfg+unipc,
  * 7 vae.  on = 0 off, 1 every kind, > 1: only the kinds in the bit mask (on >> 1) (e.g. 2 << 1 | ... ; bench.py times the

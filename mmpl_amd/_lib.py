@@ -17,6 +17,8 @@ SYMBOLS = [
     "mmpl_vae_stream_create", "mmpl_vae_stream_destroy", "mmpl_vae_stream_reset", "mmpl_vae_stream_decode",
     "mmpl_taehv_num_weights", "mmpl_taehv_weight_name", "mmpl_taehv_create", "mmpl_taehv_destroy", "mmpl_taehv_bind_weights",
     "mmpl_taehv_workspace_bytes", "mmpl_taehv_reset", "mmpl_taehv_decode",
+    "mmpl_vae_conv", "mmpl_vae_norm", "mmpl_vae_upsample", "mmpl_vae_softmax", "mmpl_vae_transpose", "mmpl_vae_zprep", "mmpl_vae_mu_out",
+    "mmpl_taehv_conv", "mmpl_taehv_prep",
     "mmpl_t5_num_weights", "mmpl_t5_create", "mmpl_t5_destroy", "mmpl_t5_bind_weights", "mmpl_t5_workspace_bytes", "mmpl_t5_encode",
     "mmpl_i2v_img_proj_workspace_bytes", "mmpl_i2v_img_proj", "mmpl_i2v_img_kv", "mmpl_i2v_cross_attn_workspace_bytes", "mmpl_i2v_cross_attn",
     "mmpl_profile_enable", "mmpl_profile_read", "mmpl_last_error", "mmpl_version",
@@ -155,6 +157,18 @@ def _bind_vae(lib):
     lib.mmpl_taehv_workspace_bytes.restype = sz
     lib.mmpl_taehv_reset.argtypes = [vp]
     lib.mmpl_taehv_decode.argtypes = [vp, vp, ci, vp, ci, C.POINTER(ci), vp, sz, vp]
+    # kernel-level entry points (tests and tools): one launch each
+    cf, ll = C.c_float, C.c_longlong
+    lib.mmpl_vae_conv.argtypes = [vp, C.POINTER(vp), ci] + [ci] * 9 + [vp, vp, vp] + [ci] * 4 + [vp] + [ci] * 6 + [vp, ci, vp, cf,
+                                  C.POINTER(vp), C.POINTER(ci), vp]
+    lib.mmpl_vae_norm.argtypes = [vp, ci, ci, ci, ci, vp, cf, ci, vp, ci, ci, ci, ci, ci, ci, vp]
+    lib.mmpl_vae_upsample.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp]
+    lib.mmpl_vae_softmax.argtypes = [vp, ci, vp, ci, ci, ci, vp]
+    lib.mmpl_vae_transpose.argtypes = [vp, ci, vp, ci, ci, ci, vp]
+    lib.mmpl_vae_zprep.argtypes = [vp, ci, ci, ci, fp, fp, vp, vp, vp, ci, vp]
+    lib.mmpl_vae_mu_out.argtypes = [vp, vp, vp, fp, fp, vp, ci, ci, ci, ci, vp]
+    lib.mmpl_taehv_conv.argtypes = [vp, vp, ll, ll, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, ll, ci, ci, ci, vp, ll, vp, vp]
+    lib.mmpl_taehv_prep.argtypes = [vp, vp, ci, ci, vp]
 
 
 def check(rc: int, what: str = "") -> None:

@@ -1,0 +1,193 @@
+// Kernel-level entry points of the VAE / TAEHV launchers (include/mmpl_hip.h, "kernel-level entry points for tests and tools"):
+// one launch of vae_kernels.hip / taehv_kernels.hip on plain arguments, the way mmpl_gemm / mmpl_layernorm expose the DiT kernels.
+// They fill the launchers' argument structs and do no arithmetic of their own.  Every check below runs before the first HIP call:
+// a rejected call launches nothing.  The checks bound what a kernel can reach by the sizes the caller states (the header says,
+// per entry, how large each buffer must be for them); alignment is checked because the kernels move 8 or 16 bytes per access.
+#include <stdint.h>
+
+#include "../../include/mmpl_hip.h"
+#include "taehv_kernels.h"
+#include "vae_kernels.h"
+
+extern int mmpl_set_error(const char* where, const char* what);  // api.hip
+
+namespace {
+inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+// a * b * c pixels (each factor >= 1) past what an int holds: the kernels walk pixels in a long and split them into int coordinates
+inline bool too_many(long a, long b, long c) { return a * b > 0x7fffffffL || a * b * c > 0x7fffffffL; }
+}  // namespace
+
+#define REJECT(cond, where, what) \
+  do { if (cond) return mmpl_set_error(where, what); } while (0)
+#define LAUNCH(expr, where)                                                       \
+  do {                                                                            \
+    hipError_t e__ = (expr);                                                      \
+    if (e__ != hipSuccess) return mmpl_set_error(where, hipGetErrorString(e__));  \
+    return 0;                                                                     \
+  } while (0)
+
+extern "C" {
+
+int mmpl_vae_conv(const void* src, const void* const* frames, int n_frames, int Cin, int Hp, int Wp, int st, int sy, int sx, int kt,
+                  int kh, int kw, const void* W, const void* Wfrag, const void* bias, int To, int Ho, int Wo, int N, void* dst, int Hd,
+                  int Wd, int ldd, int dt0, int dy0, int dx0, const void* res, int ldres, const void* ngamma, float nscale,
+                  void* const* nframes, int* kernel_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_conv";
+  if (kernel_out) *kernel_out = 0;
+  REJECT(!W || !bias || (!src && !frames), me, "null argument");
+  REJECT(Cin < 32 || Hp < 1 || Wp < 1 || To < 1 || Ho < 1 || Wo < 1 || N < 4, me, "non-positive size");
+  REJECT(st < 1 || sy < 1 || sx < 1 || kt < 1 || kt > 3 || kh < 1 || kh > 3 || kw < 1 || kw > 3, me, "stride / filter extent out of range");
+  REJECT(Cin % 32 || N % 4, me, "Cin % 32 or N % 4");
+  REJECT((long)(Ho - 1) * sy + kh > Hp || (long)(Wo - 1) * sx + kw > Wp, me, "the taps leave the padded source frame");
+  REJECT(too_many(To, Ho, Wo), me, "too many output pixels");
+  REJECT(misaligned(src, 16) || misaligned(W, 16) || misaligned(Wfrag, 16) || misaligned(bias, 8) || misaligned(dst, 8) ||
+         misaligned(res, 8) || misaligned(ngamma, 8), me, "misaligned pointer");
+  REJECT(!dst && !ngamma, me, "null destination");
+  if (dst) {
+    REJECT(Hd < 1 || Wd < 1 || dt0 < 0 || dy0 < 0 || dx0 < 0 || dy0 + Ho > Hd || dx0 + Wo > Wd, me, "the output leaves the destination frame");
+    REJECT(ldd < N || ldd % 4, me, "ldd < N or ldd % 4");
+  }
+  REJECT(res && (ldres < N || ldres % 4), me, "ldres < N or ldres % 4");
+  ConvArgs g = {};
+  if (frames) {
+    REJECT(n_frames < 1 || n_frames > 8, me, "more than 8 ring frames");
+    REJECT(n_frames != To + kt - 1, me, "a ring needs To + kt - 1 frames");
+    for (int j = 0; j < n_frames; ++j) {
+      REJECT(!frames[j] || misaligned(frames[j], 16), me, "null or misaligned ring frame");
+      g.frame[j] = (const bf16_t*)frames[j];
+    }
+  }
+  g.src = (const bf16_t*)src; g.Cin = Cin; g.Hp = Hp; g.Wp = Wp; g.st = st; g.sy = sy; g.sx = sx; g.ntaps = kt * kh * kw;
+  g.kt = kt; g.kh = kh; g.kw = kw;
+  int k = 0;
+  for (int a = 0; a < kt; ++a)
+    for (int b = 0; b < kh; ++b)
+      for (int d = 0; d < kw; ++d) g.tap_off[k++] = (a * Hp + b) * Wp + d;
+  g.W = (const bf16_t*)W; g.Wfrag = (const bf16_t*)Wfrag; g.bias = (const bf16_t*)bias;
+  g.M = To * Ho * Wo; g.N = N; g.Ho = Ho; g.Wo = Wo;
+  g.dst = (bf16_t*)dst; g.Hd = Hd; g.Wd = Wd; g.ldd = ldd; g.dt0 = dt0; g.dy0 = dy0; g.dx0 = dx0; g.dc0 = 0;
+  g.res = (const bf16_t*)res; g.ldres = ldres;
+  const VaeConvKernel which = vae_conv_kernel(g);
+  REJECT(which == VAE_CONV_NONE, me, "invalid argument");          // the launcher's own rejections (ring frames on a non-halo shape, ...)
+  if (ngamma) {
+    REJECT(which != VAE_CONV_HALO6 || N != 96, me, "the fused norm epilogue exists for conv_halo_kernel<6> at N == 96 only");
+    REJECT(!nframes || To > 8, me, "more than 8 norm frames");
+    g.ngamma = (const bf16_t*)ngamma; g.nscale = nscale;
+    for (int t = 0; t < To; ++t) {
+      REJECT(!nframes[t] || misaligned(nframes[t], 8), me, "null or misaligned norm frame");
+      g.nframe[t] = (bf16_t*)nframes[t];
+    }
+  }
+  if (kernel_out) *kernel_out = (int)which;
+  LAUNCH(vae_launch_conv(g, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_norm(const void* src, int T, int H, int W, int C, const void* gamma, float scale, int silu, void* dst, int Hd, int Wd,
+                  int ldd, int dt0, int dy0, int dx0, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_norm";
+  REJECT(!src || !dst, me, "null argument");
+  REJECT(T < 1 || H < 1 || W < 1 || C < 8, me, "non-positive size");
+  REJECT(C % 8 || C > 1024, me, "C % 8 or C > 1024");
+  REJECT(too_many(T, H, W), me, "too many pixels");
+  REJECT(ldd < C || ldd % 8, me, "ldd < C or ldd % 8");
+  REJECT(Hd < 1 || Wd < 1 || dt0 < 0 || dy0 < 0 || dx0 < 0 || dy0 + H > Hd || dx0 + W > Wd, me, "the output leaves the destination frame");
+  REJECT(misaligned(src, 16) || misaligned(gamma, 16) || misaligned(dst, 16), me, "misaligned pointer");
+  NormArgs a{(const bf16_t*)src, (long)T * H * W, C, H, W, (const bf16_t*)gamma, scale, silu ? 1 : 0, (bf16_t*)dst, Hd, Wd, ldd, dt0, dy0, dx0};
+  LAUNCH(vae_launch_norm(a, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_upsample(const void* src, int lds, int C, int H, int W, int To, int interleave, void* dst, int Hd, int Wd,
+                      mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_upsample";
+  REJECT(!src || !dst, me, "null argument");
+  REJECT(C < 8 || H < 1 || W < 1 || To < 1, me, "non-positive size");
+  REJECT(C % 8 || lds % 8 || lds < (interleave ? 2 * C : C), me, "C % 8, lds % 8 or lds too small");
+  REJECT(interleave && (To & 1), me, "interleave needs an even To");
+  REJECT(H > 0x3fffffff || W > 0x3fffffff || too_many(To, 2L * H, 2L * W), me, "too many output pixels");
+  REJECT(Hd != 2 * H + 2 || Wd != 2 * W + 2, me, "the destination frame is [2H + 2, 2W + 2]");
+  REJECT(misaligned(src, 16) || misaligned(dst, 16), me, "misaligned pointer");
+  UpArgs a{(const bf16_t*)src, lds, C, H, W, To, interleave ? 1 : 0, (bf16_t*)dst, Hd, Wd};
+  LAUNCH(vae_launch_upsample(a, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_softmax(const void* scores, int ld, void* p, int ldp, int rows, int cols, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_softmax";
+  REJECT(!scores || !p, me, "null argument");
+  REJECT(rows < 1 || cols < 1, me, "non-positive size");
+  REJECT(ld < cols || ldp < cols, me, "ld < cols or ldp < cols");
+  REJECT(misaligned(scores, 4) || misaligned(p, 2), me, "misaligned pointer");
+  LAUNCH(vae_launch_softmax((const float*)scores, ld, (bf16_t*)p, ldp, rows, cols, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_transpose(const void* v, int ld, void* vt, int ldt, int rows, int C, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_transpose";
+  REJECT(!v || !vt, me, "null argument");
+  REJECT(rows < 1 || C < 1, me, "non-positive size");
+  REJECT(ld < C || ldt < rows, me, "ld < C or ldt < rows");
+  REJECT(C > 65535 * 32, me, "C too large");
+  REJECT(misaligned(v, 2) || misaligned(vt, 2), me, "misaligned pointer");
+  LAUNCH(vae_launch_transpose((const bf16_t*)v, ld, (bf16_t*)vt, ldt, rows, C, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_zprep(const void* z, int F, int h, int w, const float* mean, const float* inv_std, const void* w2, const void* b2, void* dst,
+                   int dt0, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_zprep";
+  REJECT(!z || !mean || !inv_std || !w2 || !b2 || !dst, me, "null argument");
+  REJECT(F < 1 || h < 1 || w < 1 || dt0 < 0, me, "non-positive size");
+  REJECT(too_many(F, h, w), me, "too many pixels");
+  REJECT(misaligned(z, 2) || misaligned(w2, 2) || misaligned(b2, 2) || misaligned(dst, 2), me, "misaligned pointer");
+  ZPrepArgs a = {};
+  a.z = (const bf16_t*)z; a.F = F; a.h = h; a.w = w;
+  for (int i = 0; i < 16; ++i) { a.mean[i] = mean[i]; a.inv_std[i] = inv_std[i]; }
+  a.w2 = (const bf16_t*)w2; a.b2 = (const bf16_t*)b2; a.dst = (bf16_t*)dst; a.dt0 = dt0;
+  LAUNCH(vae_launch_zprep(a, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_mu_out(const void* enc, const void* w1, const void* b1, const float* mean, const float* inv_std, void* out, int F,
+                    int f_out, int h, int w, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_mu_out";
+  REJECT(!enc || !w1 || !b1 || !mean || !inv_std || !out, me, "null argument");
+  REJECT(F < 1 || h < 1 || w < 1 || f_out < 0, me, "non-positive size");
+  REJECT(too_many(F, h, w), me, "too many pixels");
+  REJECT(misaligned(enc, 2) || misaligned(w1, 2) || misaligned(b1, 2) || misaligned(out, 4), me, "misaligned pointer");
+  MuArgs a = {};
+  a.enc = (const bf16_t*)enc; a.w1 = (const bf16_t*)w1; a.b1 = (const bf16_t*)b1; a.out = (float*)out;
+  for (int i = 0; i < 16; ++i) { a.mean[i] = mean[i]; a.inv_std[i] = inv_std[i]; }
+  a.F = F; a.f_out = f_out; a.h = h; a.w = w;
+  LAUNCH(vae_launch_mu_out(a, (hipStream_t)stream), me);
+}
+
+int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long fs1, int C0, int C1, int up, int ntaps,
+                    const void* Wfrag, const void* bias, int Nw, int N, int T, int Ho, int Wo, void* dst, long long fsd, int ldd,
+                    int Nsplit, int relu, const void* skip, long long fss, void* keep, mmpl_stream_t stream) {
+  const char* me = "mmpl_taehv_conv";
+  REJECT(!src0 || !Wfrag || !dst || (C1 > 0 && !src1), me, "null argument");
+  REJECT(T < 1 || Ho < 1 || Wo < 1 || C0 < 32 || C1 < 0 || Nw < 16 || N < 4 || Nsplit < 16 || ldd < 4, me, "non-positive size");
+  REJECT(fs0 < 0 || fs1 < 0 || fsd < 0 || fss < 0, me, "negative frame stride");
+  REJECT(fs0 % 8 || fs1 % 8 || fsd % 4 || fss % 4, me, "frame stride not a multiple of the access width");
+  REJECT(keep && !skip, me, "keep without skip");
+  const int BN = Nw % 64 == 0 ? 64 : 16;
+  // the launcher's own rejections, repeated here so that nothing below divides by a bad Nsplit
+  REJECT((ntaps != 9 && ntaps != 1) || C0 % 32 || C1 % 32 || Nw % BN || Nsplit % BN || Nw % Nsplit || N % 4 || N > Nw || ldd % 4 ||
+         (up && ((Ho | Wo) & 1)) || (skip && N != Nw), me, "invalid argument");
+  REJECT(Nsplit != Nw && N != Nw, me, "a frame split stores every channel (N == Nw)");
+  REJECT(ldd < (N < Nsplit ? N : Nsplit), me, "ldd smaller than the channels stored per pixel");
+  REJECT(misaligned(src0, 16) || misaligned(src1, 16) || misaligned(Wfrag, 16) || misaligned(bias, 8) || misaligned(dst, 8) ||
+         misaligned(skip, 8) || misaligned(keep, 8), me, "misaligned pointer");
+  TaehvConvArgs g = {};
+  g.src0 = (const bf16_t*)src0; g.src1 = (const bf16_t*)src1; g.fs0 = (long)fs0; g.fs1 = (long)fs1; g.C0 = C0; g.C1 = C1; g.up = up ? 1 : 0;
+  g.ntaps = ntaps; g.Wfrag = (const bf16_t*)Wfrag; g.bias = (const bf16_t*)bias; g.Nw = Nw; g.N = N; g.T = T; g.Ho = Ho; g.Wo = Wo;
+  g.dst = (bf16_t*)dst; g.fsd = (long)fsd; g.ldd = ldd; g.Nsplit = Nsplit; g.relu = relu ? 1 : 0;
+  g.skip = (const bf16_t*)skip; g.fss = (long)fss; g.keep = (bf16_t*)keep;
+  LAUNCH(taehv_launch_conv(g, (hipStream_t)stream), me);
+}
+
+int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream) {
+  const char* me = "mmpl_taehv_prep";
+  REJECT(!z || !dst, me, "null argument");
+  REJECT(h < 1 || w < 1 || (long)h * w > 0x7fffffffL / 64, me, "non-positive size");
+  REJECT(misaligned(z, 2) || misaligned(dst, 16), me, "misaligned pointer");
+  LAUNCH(taehv_launch_prep((const bf16_t*)z, (bf16_t*)dst, h, w, (hipStream_t)stream), me);
+}
+
+}  // extern "C"

@@ -31,6 +31,9 @@ struct ConvArgs {
 };
 hipError_t vae_launch_conv(const ConvArgs& g, hipStream_t s);
 bool vae_conv_uses_halo(const ConvArgs& g);   // will vae_launch_conv take conv_halo_kernel (the only one that understands ConvArgs.frame)?
+// the kernel vae_launch_conv launches for g (its own dispatch: the launcher switches on this), VAE_CONV_NONE = it rejects g
+enum VaeConvKernel { VAE_CONV_NONE = 0, VAE_CONV_IGEMM3 = 1, VAE_CONV_IGEMM4 = 2, VAE_CONV_HALO6 = 3, VAE_CONV_HALO1 = 4 };
+VaeConvKernel vae_conv_kernel(const ConvArgs& g);
 
 struct NormArgs {
   const bf16_t* src;   // plain [npix, C]

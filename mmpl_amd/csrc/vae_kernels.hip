@@ -626,24 +626,31 @@ bool vae_conv_uses_halo(const ConvArgs& g) {
          g.sx == 1 && g.Hp == g.Ho + 2 && g.Wp == g.Wo + 2 && g.M > 0 && g.M % (g.Ho * g.Wo) == 0 && g.Cin % 32 == 0 && (g.N % 96 == 0 || g.N <= 16);
 }
 
-hipError_t vae_launch_conv(const ConvArgs& g, hipStream_t s) {
-  if (g.M <= 0) return hipSuccess;
-  if (g.Cin % 32 || g.N % 4 || g.ntaps < 1 || g.ntaps > 27) return hipErrorInvalidValue;
-  if (g.frame[0] != nullptr && !vae_conv_uses_halo(g)) return hipErrorInvalidValue;      // only conv_halo_kernel reads ring slots
+VaeConvKernel vae_conv_kernel(const ConvArgs& g) {
+  if (g.Cin % 32 || g.N % 4 || g.ntaps < 1 || g.ntaps > 27) return VAE_CONV_NONE;
+  if (g.frame[0] != nullptr && !vae_conv_uses_halo(g)) return VAE_CONV_NONE;              // only conv_halo_kernel reads ring slots
   if (vae_conv_uses_halo(g)) {
-    if (g.N % 96 == 0) return launch_halo<6>(g, s);           // 96, 192, 384: every ResidualBlock / upsampler conv of the Wan VAE
-    if (g.N <= 16) return launch_halo<1>(g, s);               // the decoder head (96 -> 3, padded to 4): one 16-column fragment
+    if (g.N % 96 == 0) return VAE_CONV_HALO6;                 // 96, 192, 384: every ResidualBlock / upsampler conv of the Wan VAE
+    if (g.N <= 16) return VAE_CONV_HALO1;                     // the decoder head (96 -> 3, padded to 4): one 16-column fragment
     // (a 128-wide variant spills 18 registers and a 32-wide one does not fit hipcc's allocator at all: the remaining
     // widths -- the encoder head's N = 32 -- stay on the plain kernel; 0.1 % of the FLOPs)
   }
-  if (g.N % 96 == 0 && g.N % 128 != 0) {                     // 96, 288, ...: no padding columns with the 96-wide tile
-    const int tiles = ((g.M + BM - 1) / BM) * (g.N / 96);
-    hipLaunchKernelGGL(conv_igemm_kernel<3>, dim3(tiles), dim3(256), 0, s, g);
-  } else {
-    const int tiles = ((g.M + BM - 1) / BM) * ((g.N + 127) / 128);
-    hipLaunchKernelGGL(conv_igemm_kernel<4>, dim3(tiles), dim3(256), 0, s, g);
+  return (g.N % 96 == 0 && g.N % 128 != 0) ? VAE_CONV_IGEMM3 : VAE_CONV_IGEMM4;   // 96, 288, ...: no padding columns with the 96-wide tile
+}
+
+hipError_t vae_launch_conv(const ConvArgs& g, hipStream_t s) {
+  if (g.M <= 0) return hipSuccess;
+  switch (vae_conv_kernel(g)) {
+    case VAE_CONV_HALO6: return launch_halo<6>(g, s);
+    case VAE_CONV_HALO1: return launch_halo<1>(g, s);
+    case VAE_CONV_IGEMM3:
+      hipLaunchKernelGGL(conv_igemm_kernel<3>, dim3(((g.M + BM - 1) / BM) * (g.N / 96)), dim3(256), 0, s, g);
+      return hipGetLastError();
+    case VAE_CONV_IGEMM4:
+      hipLaunchKernelGGL(conv_igemm_kernel<4>, dim3(((g.M + BM - 1) / BM) * ((g.N + 127) / 128)), dim3(256), 0, s, g);
+      return hipGetLastError();
+    default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 hipError_t vae_launch_norm(const NormArgs& a, hipStream_t s) {
   if (a.npix <= 0) return hipSuccess;

@@ -1,0 +1,126 @@
+"""Argument checks of the kernel-level VAE / TAEHV entry points (include/mmpl_hip.h): every rejection happens before the first HIP
+call, so this file needs no GPU and no real buffer -- the pointers below are made-up, aligned addresses that nothing dereferences.
+Each call is wrong in exactly one way and is matched against the message of the check that must catch it."""
+import ctypes as C
+
+import pytest
+
+from mmpl_amd import _lib
+
+P = 0x100000                       # a made-up 16-byte aligned "device pointer"
+VP = C.c_void_p
+
+
+def _err(rc):
+    assert rc != 0
+    return _lib.load().mmpl_last_error().decode()
+
+
+def _conv(**kw):
+    """mmpl_vae_conv on a valid 96 -> 96 3x3x3 halo call (To = 2, 6 x 10), with overrides."""
+    a = dict(src=P, frames=None, n_frames=0, Cin=96, Hp=8, Wp=12, st=1, sy=1, sx=1, kt=3, kh=3, kw=3, W=P, Wfrag=P, bias=P, To=2, Ho=6,
+             Wo=10, N=96, dst=P, Hd=6, Wd=10, ldd=96, dt0=0, dy0=0, dx0=0, res=None, ldres=0, ngamma=None, nscale=1.0, nframes=None)
+    a.update(kw)
+    k = C.c_int(-1)
+    rc = _lib.load().mmpl_vae_conv(*a.values(), C.byref(k), None)
+    return _err(rc), k.value
+
+
+def _frames(n, bad=None):
+    return (VP * n)(*[0 if i == bad else P + 0x1000 * i for i in range(n)])
+
+
+CONV_REJECTS = [
+    (dict(W=None), "null argument"), (dict(bias=None), "null argument"), (dict(src=None), "null argument"),
+    (dict(dst=None), "null destination"),
+    (dict(To=0), "non-positive size"), (dict(Ho=-1), "non-positive size"), (dict(Cin=0), "non-positive size"), (dict(N=0), "non-positive size"),
+    (dict(kt=4), "out of range"), (dict(sy=0), "out of range"),
+    (dict(Cin=48), "Cin % 32"), (dict(N=98), "N % 4"),
+    (dict(Hp=7), "leave the padded source frame"), (dict(Wp=11), "leave the padded source frame"), (dict(sx=2), "leave the padded source frame"),
+    (dict(To=2, Ho=1 << 16, Wo=1 << 14, Hp=(1 << 16) + 2, Wp=(1 << 14) + 2, Hd=1 << 16, Wd=1 << 14), "too many output pixels"),
+    (dict(src=P + 8), "misaligned"), (dict(bias=P + 2), "misaligned"), (dict(dst=P + 4), "misaligned"),
+    (dict(Hd=5), "leaves the destination frame"), (dict(dx0=1), "leaves the destination frame"), (dict(dt0=-1), "leaves the destination frame"),
+    (dict(ldd=92), "ldd < N"), (dict(ldd=98), "ldd % 4"),
+    (dict(res=P, ldres=64), "ldres < N"),
+    (dict(frames=_frames(9), n_frames=9, To=7), "more than 8 ring frames"),
+    (dict(frames=_frames(3), n_frames=3), "To + kt - 1 frames"),
+    (dict(frames=_frames(4, bad=2), n_frames=4), "null or misaligned ring frame"),
+    (dict(frames=_frames(4), n_frames=4, Wfrag=None), "invalid argument"),          # the launcher's own: ring slots need conv_halo_kernel
+    (dict(ngamma=P, nframes=_frames(2), N=192, ldd=192), "N == 96 only"),
+    (dict(ngamma=P, nframes=_frames(2), Wfrag=None), "N == 96 only"),               # conv_igemm_kernel has no fused epilogue
+    (dict(ngamma=P, nframes=None), "norm frames"),
+    (dict(ngamma=P, nframes=_frames(2, bad=1), dst=None), "null or misaligned norm frame"),
+    (dict(ngamma=P, nframes=_frames(8), frames=None, To=9, Hd=6), "norm frames"),
+]
+
+
+@pytest.mark.parametrize("kw,msg", CONV_REJECTS, ids=[f"{i}-{m[:18]}" for i, (_, m) in enumerate(CONV_REJECTS)])
+def test_vae_conv_rejects(kw, msg):
+    text, kernel = _conv(**kw)
+    assert text.startswith("mmpl_vae_conv:") and msg in text, text
+    assert kernel == 0                                             # nothing was chosen, nothing was launched
+
+
+def test_vae_pass_entry_points_reject():
+    lib = _lib.load()
+    e = lambda rc: _err(rc)
+    assert "null argument" in e(lib.mmpl_vae_norm(None, 1, 3, 3, 96, None, 1.0, 0, P, 3, 3, 96, 0, 0, 0, None))
+    assert "non-positive" in e(lib.mmpl_vae_norm(P, 0, 3, 3, 96, None, 1.0, 0, P, 3, 3, 96, 0, 0, 0, None))
+    assert "C % 8" in e(lib.mmpl_vae_norm(P, 1, 3, 3, 100, None, 1.0, 0, P, 3, 3, 104, 0, 0, 0, None))
+    assert "C % 8" in e(lib.mmpl_vae_norm(P, 1, 3, 3, 1032, None, 1.0, 0, P, 3, 3, 1032, 0, 0, 0, None))
+    assert "ldd < C" in e(lib.mmpl_vae_norm(P, 1, 3, 3, 96, None, 1.0, 0, P, 3, 3, 88, 0, 0, 0, None))
+    assert "leaves the destination" in e(lib.mmpl_vae_norm(P, 1, 3, 3, 96, None, 1.0, 0, P, 4, 4, 96, 0, 2, 0, None))
+    assert "misaligned" in e(lib.mmpl_vae_norm(P, 1, 3, 3, 96, P + 8, 1.0, 0, P, 3, 3, 96, 0, 0, 0, None))
+    assert "too many pixels" in e(lib.mmpl_vae_norm(P, 2, 1 << 16, 1 << 14, 96, None, 1.0, 0, P, 1 << 16, 1 << 14, 96, 0, 0, 0, None))
+    assert "too many pixels" in e(lib.mmpl_vae_norm(P, 1 << 30, 1 << 30, 1 << 30, 96, None, 1.0, 0, P, 1 << 30, 1 << 30, 96, 0, 0, 0, None))
+    assert "null argument" in e(lib.mmpl_vae_upsample(P, 192, 192, 3, 5, 2, 0, None, 8, 12, None))
+    assert "non-positive" in e(lib.mmpl_vae_upsample(P, 192, 192, 3, 0, 2, 0, P, 8, 2, None))
+    assert "lds too small" in e(lib.mmpl_vae_upsample(P, 192, 192, 3, 5, 2, 1, P, 8, 12, None))
+    assert "even To" in e(lib.mmpl_vae_upsample(P, 384, 192, 3, 5, 3, 1, P, 8, 12, None))
+    assert "[2H + 2, 2W + 2]" in e(lib.mmpl_vae_upsample(P, 192, 192, 3, 5, 2, 0, P, 8, 11, None))
+    assert "too many output pixels" in e(lib.mmpl_vae_upsample(P, 192, 192, 1 << 14, 1 << 14, 2, 0, P, (1 << 15) + 2, (1 << 15) + 2, None))
+    assert "null argument" in e(lib.mmpl_vae_softmax(None, 64, P, 64, 4, 60, None))
+    assert "non-positive" in e(lib.mmpl_vae_softmax(P, 64, P, 64, 0, 60, None))
+    assert "ldp < cols" in e(lib.mmpl_vae_softmax(P, 64, P, 32, 4, 60, None))
+    assert "null argument" in e(lib.mmpl_vae_transpose(P, 288, None, 64, 60, 96, None))
+    assert "ldt < rows" in e(lib.mmpl_vae_transpose(P, 288, P, 32, 60, 96, None))
+    assert "ld < C" in e(lib.mmpl_vae_transpose(P, 64, P, 64, 60, 96, None))
+    f16 = (C.c_float * 16)()
+    assert "null argument" in e(lib.mmpl_vae_zprep(P, 1, 4, 4, None, f16, P, P, P, 0, None))
+    assert "non-positive" in e(lib.mmpl_vae_zprep(P, 1, 4, 4, f16, f16, P, P, P, -1, None))
+    assert "too many pixels" in e(lib.mmpl_vae_zprep(P, 2, 1 << 16, 1 << 14, f16, f16, P, P, P, 0, None))
+    assert "null argument" in e(lib.mmpl_vae_mu_out(P, P, None, f16, f16, P, 1, 0, 4, 4, None))
+    assert "non-positive" in e(lib.mmpl_vae_mu_out(P, P, P, f16, f16, P, 0, 0, 4, 4, None))
+    assert "too many pixels" in e(lib.mmpl_vae_mu_out(P, P, P, f16, f16, P, 2, 0, 1 << 16, 1 << 14, None))
+    assert "null argument" in e(lib.mmpl_taehv_prep(None, P, 4, 4, None))
+    assert "non-positive" in e(lib.mmpl_taehv_prep(P, P, 0, 4, None))
+    assert "misaligned" in e(lib.mmpl_taehv_prep(P, P + 8, 4, 4, None))
+
+
+def _taehv(**kw):
+    """mmpl_taehv_conv on a valid MemBlock first conv (64 + 64 -> 64, T = 2, 6 x 10), with overrides."""
+    fs = 8 * 12 * 64
+    a = dict(src0=P + 2 * fs, src1=P, fs0=fs, fs1=fs, C0=64, C1=64, up=0, ntaps=9, Wfrag=P, bias=P, Nw=64, N=64, T=2, Ho=6, Wo=10, dst=P,
+             fsd=fs, ldd=64, Nsplit=64, relu=1, skip=None, fss=0, keep=None)
+    a.update(kw)
+    return _err(_lib.load().mmpl_taehv_conv(*a.values(), None))
+
+
+TAEHV_REJECTS = [
+    (dict(src0=None), "null argument"), (dict(Wfrag=None), "null argument"), (dict(dst=None), "null argument"), (dict(src1=None), "null argument"),
+    (dict(T=0), "non-positive size"), (dict(Wo=0), "non-positive size"), (dict(C0=0), "non-positive size"), (dict(Nsplit=0), "non-positive size"),
+    (dict(fs0=-8), "negative frame stride"), (dict(fs1=12), "multiple of the access width"),
+    (dict(keep=P), "keep without skip"),
+    (dict(ntaps=3), "invalid argument"), (dict(C0=48), "invalid argument"), (dict(Nw=72, N=72, ldd=72, Nsplit=72), "invalid argument"),
+    (dict(Nw=128, N=128, Nsplit=96, ldd=128), "invalid argument"), (dict(N=66), "invalid argument"), (dict(N=128, ldd=128), "invalid argument"),
+    (dict(up=1, Ho=7), "invalid argument"), (dict(skip=P, fss=8 * 12 * 64, N=32), "invalid argument"),
+    (dict(Nw=128, N=64, Nsplit=64), "N == Nw"),
+    (dict(ldd=32), "ldd smaller"),
+    (dict(bias=P + 4), "misaligned"), (dict(src1=P + 8), "misaligned"),
+]
+
+
+@pytest.mark.parametrize("kw,msg", TAEHV_REJECTS, ids=[f"{i}-{m[:18]}" for i, (_, m) in enumerate(TAEHV_REJECTS)])
+def test_taehv_conv_rejects(kw, msg):
+    text = _taehv(**kw)
+    assert text.startswith("mmpl_taehv_conv:") and msg in text, text
