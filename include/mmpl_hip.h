@@ -116,6 +116,18 @@ int mmpl_dit_forward(MmplDit* h, const void* x_in, const float* t_dev, int n_fra
                      const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
                      int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
                      void* attn_history, void* out, void* workspace, size_t workspace_bytes, mmpl_stream_t stream);
+/* mmpl_dit_forward with the RoPE position base as DEVICE data.  frame_base_dev: dev, one int (NULL = mmpl_dit_forward, bit for
+ * bit); `frame_ids` are then RELATIVE to it: frame i is rotated at temporal position frame_ids[i] + *frame_base_dev.  The int is
+ * read by the device when the forward EXECUTES, not when it is launched or captured: a forward captured into a hipGraph is
+ * replayed at another position in time by writing the int in stream order before the replay -- the slots, shapes and every other
+ * argument of the launch stay what was captured.  The host cannot see the base at replay time, so keeping frame_ids[i] + base
+ * inside the RoPE tables (0 .. 1023) is the caller's job; the kernel clamps the sum to that range, so a stale base rotates with
+ * the wrong angle but reads nothing outside the tables. */
+int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const int* frame_ids,
+                        const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
+                        int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
+                        void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                        mmpl_stream_t stream);
 size_t mmpl_dit_attn_history_bytes(const MmplDit* h, int n_frames);
 /* MMPL_CHECK_SHARE=1: number of share_in forwards (eager or replayed) since the last call whose layer-0 K / V fingerprint differed
  * from their share_out forward's; synchronises `stream` and resets the count.  0 when the switch is off. */
@@ -200,6 +212,11 @@ int mmpl_layernorm(const void* x, int ldx, void* y, int ldy, int rows, int d, fl
 int mmpl_qknorm_rope(MmplDit* h, void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* wq,
                      const void* wk, int n_frames, const int* frame_ids, void* const* k_dst, void* const* v_dst,
                      mmpl_stream_t stream);
+/* Same, with the temporal position of frame i = frame_ids[i] + *frame_base_dev (dev, one int, read when the kernel runs; the sum
+ * is clamped to 0 .. 1023; NULL = mmpl_qknorm_rope, bit for bit).  See mmpl_dit_forward_at. */
+int mmpl_qknorm_rope_at(MmplDit* h, void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* wq,
+                        const void* wk, int n_frames, const int* frame_ids, void* const* k_dst, void* const* v_dst,
+                        const int* frame_base_dev, mmpl_stream_t stream);
 
 /* CFG combine + FlowUniPCMultistepScheduler.step (casual_fps_inference.py:366-374, fm_solvers_unipc.py:655-739) */
 typedef struct MmplUniPCStep {

@@ -10,8 +10,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmmpl_hip.so")
 # every symbol include/mmpl_hip.h declares (tests/test_abi.py checks this list against the header and the .so)
 SYMBOLS = [
     "mmpl_dit_num_weights", "mmpl_dit_weight_name", "mmpl_dit_create", "mmpl_dit_destroy", "mmpl_dit_bind_weights",
-    "mmpl_dit_workspace_bytes", "mmpl_dit_context_workspace_bytes", "mmpl_dit_precompute_context", "mmpl_dit_forward", "mmpl_dit_attn_history_bytes", "mmpl_dit_share_check_failures", "mmpl_dit_set_attn_stats", "mmpl_dit_set_image_kv", "mmpl_clip_visual", "mmpl_clip_visual_workspace_bytes",
-    "mmpl_attn_fwd", "mmpl_attn_fwd_ws", "mmpl_attn_fwd_variant", "mmpl_attn_fwd_history", "mmpl_attn_history_bytes", "mmpl_attn_workspace_bytes", "mmpl_gemm", "mmpl_gemm_tickets", "mmpl_gemm_scratch", "mmpl_gemm_scratch_bytes", "mmpl_device_xcd_round_robin", "mmpl_probe_mfma_tflops", "mmpl_layernorm", "mmpl_qknorm_rope", "mmpl_cfg_unipc_step", "mmpl_cfg_unipc_step_table", "mmpl_fewstep_update",
+    "mmpl_dit_workspace_bytes", "mmpl_dit_context_workspace_bytes", "mmpl_dit_precompute_context", "mmpl_dit_forward", "mmpl_dit_forward_at", "mmpl_dit_attn_history_bytes", "mmpl_dit_share_check_failures", "mmpl_dit_set_attn_stats", "mmpl_dit_set_image_kv", "mmpl_clip_visual", "mmpl_clip_visual_workspace_bytes",
+    "mmpl_attn_fwd", "mmpl_attn_fwd_ws", "mmpl_attn_fwd_variant", "mmpl_attn_fwd_history", "mmpl_attn_history_bytes", "mmpl_attn_workspace_bytes", "mmpl_gemm", "mmpl_gemm_tickets", "mmpl_gemm_scratch", "mmpl_gemm_scratch_bytes", "mmpl_device_xcd_round_robin", "mmpl_probe_mfma_tflops", "mmpl_layernorm", "mmpl_qknorm_rope", "mmpl_qknorm_rope_at", "mmpl_cfg_unipc_step", "mmpl_cfg_unipc_step_table", "mmpl_fewstep_update",
     "mmpl_vae_num_weights", "mmpl_vae_weight_name", "mmpl_vae_create", "mmpl_vae_destroy", "mmpl_vae_bind_weights",
     "mmpl_vae_workspace_bytes", "mmpl_vae_decode", "mmpl_vae_encode",
     "mmpl_vae_stream_create", "mmpl_vae_stream_destroy", "mmpl_vae_stream_reset", "mmpl_vae_stream_decode",
@@ -77,6 +77,7 @@ def load() -> C.CDLL:
     lib.mmpl_dit_precompute_context.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(ci), vp]
     lib.mmpl_dit_forward.argtypes = [vp, vp, vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, vp, vp, ci, vp, vp,
                                      ci, vp, vp, vp, vp, vp, sz, vp]
+    lib.mmpl_dit_forward_at.argtypes = lib.mmpl_dit_forward.argtypes[:-1] + [vp, vp]
     lib.mmpl_dit_attn_history_bytes.argtypes = [vp, ci]
     lib.mmpl_dit_attn_history_bytes.restype = sz
     lib.mmpl_dit_share_check_failures.argtypes = [vp, C.POINTER(C.c_longlong), vp]
@@ -98,6 +99,7 @@ def load() -> C.CDLL:
     lib.mmpl_gemm_scratch_bytes.restype = sz
     lib.mmpl_layernorm.argtypes = [vp, ci, vp, ci, ci, ci, cf, vp, vp, ci, ci, vp, vp, vp]
     lib.mmpl_qknorm_rope.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, ci, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp), vp]
+    lib.mmpl_qknorm_rope_at.argtypes = lib.mmpl_qknorm_rope.argtypes[:-1] + [vp, vp]
     lib.mmpl_cfg_unipc_step.argtypes = [vp, vp, vp, vp, vp, vp, sz, C.POINTER(MmplUniPCStep), vp]
     lib.mmpl_fewstep_update.argtypes = [vp, vp, vp, vp, sz, C.c_double, cf, vp]
     lib.mmpl_profile_enable.argtypes = [ci]

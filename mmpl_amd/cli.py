@@ -50,8 +50,9 @@ def pipeline_class(config):
 def fewstep_refusal(args, world: int):
     """Why the few-step pipeline cannot run this command line (None = it can).  The reference's rollout loop feeds 2 overlap
     latent frames back and trips `num_input_frames % num_frame_per_block == 0` from rollout 2 on (causal_inference.py:153);
-    its I2V image latent is 1 frame; it has no multi-rank few-step path."""
-    if args.duration > 1:
+    its I2V image latent is 1 frame; it has no multi-rank few-step path.  With --rolling (the rolling KV window, which the
+    reference does not have) --duration N is ONE call of N * num_output_frames latent frames instead."""
+    if args.duration > 1 and not getattr(args, "rolling", False):
         return (f"--duration {args.duration}: the few-step pipeline (config with denoising_step_list) generates one "
                 f"{args.num_output_frames}-latent-frame call; longer rollouts are not supported (use --duration 1)")
     if args.i2v or args.i2v_model:
@@ -67,6 +68,15 @@ def stream_refusal(args, fewstep: bool):
     if getattr(args, "stream", False) and not fewstep:
         return ("--stream: block-wise output needs a few-step config (one with denoising_step_list, e.g. self_forcing_dmd.yaml); "
                 "the 50-step pipeline does not stream")
+    return None
+
+
+def rolling_refusal(args, fewstep: bool):
+    """Why --rolling cannot run this command line (None = it can, or it was not asked for): the rolling KV window belongs to the
+    few-step pipeline (CausalInferencePipeline, args.rolling_kv); the 50-step pipeline rolls over chunks by itself."""
+    if getattr(args, "rolling", False) and not fewstep:
+        return ("--rolling: the rolling KV window needs a few-step config (one with denoising_step_list, e.g. self_forcing_dmd.yaml); "
+                "the 50-step pipeline generates --duration chunks without it")
     return None
 
 
@@ -100,6 +110,10 @@ def build_fewstep_pipeline(config, args, dev, geo, mcfg):
     from .pipeline import CausalInferencePipeline
     from .wan_wrapper import SyntheticTextEncoder, WanDiffusionWrapper, WanVAEWrapper
     kw = dict(getattr(config, "model_kwargs", {}) or {})
+    for name in ("local_attn_size", "sink_size"):                        # --local_attn_size / --sink_size override the config's
+        if getattr(args, name, None) is not None:
+            kw[name] = getattr(args, name)
+    config.rolling_kv = bool(getattr(args, "rolling", False))
     gen = WanDiffusionWrapper("Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B", **kw, is_causal=True,
                               model_config=mcfg if args.synthetic else None, geometry=geo, device=dev)
     enc, vae = None, None
@@ -149,6 +163,13 @@ def main(argv=None):
     ap.add_argument("--preview_vae", type=str, nargs="?", const="", default=None, metavar="PATH",
                     help="with --stream: decode the live frames with the tiny TAEHV preview decoder (taew2_1.pth at PATH, default "
                          "../wan_models/taew2_1.pth; seeded weights with --synthetic) instead of the Wan VAE")
+    ap.add_argument("--rolling", action="store_true",
+                    help="few-step configs: rolling KV window (evict the oldest frame that is not a sink frame), so that "
+                         "--duration N generates N * num_output_frames latent frames in ONE call, with --stream as well")
+    ap.add_argument("--local_attn_size", type=int, default=None, help="few-step configs: override model_kwargs.local_attn_size "
+                    "(the KV window in latent frames; -1 = 21)")
+    ap.add_argument("--sink_size", type=int, default=None, help="few-step configs: override model_kwargs.sink_size (the first "
+                    "frames of the video that --rolling never evicts)")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -159,6 +180,9 @@ def main(argv=None):
     if why is not None:
         ap.error(why)
     why = preview_refusal(args)
+    if why is not None:
+        ap.error(why)
+    why = rolling_refusal(args, fewstep)
     if why is not None:
         ap.error(why)
     if fewstep:
@@ -316,10 +340,11 @@ def _prompts(args):
 
 
 def _main_fewstep(config, args, dev, geo, mcfg):
-    """Wan_fps_inference_1gpu.py with a few-step config: one CausalInferencePipeline.inference per prompt."""
+    """Wan_fps_inference_1gpu.py with a few-step config: one CausalInferencePipeline.inference per prompt (--rolling: of
+    --duration * num_output_frames latent frames; fewstep_refusal keeps --duration at 1 otherwise)."""
     pipe = build_fewstep_pipeline(config, args, dev, geo, mcfg)
     os.makedirs(args.output_folder, exist_ok=True)
-    shape = [1, args.num_output_frames, 16, geo.lat_h, geo.lat_w]
+    shape = [1, args.num_output_frames * args.duration, 16, geo.lat_h, geo.lat_w]
     for idx, prompt in enumerate(_prompts(args)):
         g = torch.Generator(device="cpu").manual_seed(args.seed)
         noise = torch.randn(shape, generator=g).to(torch.bfloat16)

@@ -341,6 +341,15 @@ int mmpl_dit_forward(MmplDit* h, const void* x_in, const float* t_dev, int nF, c
                      const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
                      int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
                      void* attn_history, void* out, void* workspace, size_t workspace_bytes, mmpl_stream_t stream) {
+  return mmpl_dit_forward_at(h, x_in, t_dev, nF, frame_ids, write_slots, visible_slots, n_visible, k_cache, v_cache, n_slots, cross_k,
+                             cross_v, cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
+}
+
+int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF, const int* frame_ids,
+                        const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
+                        int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
+                        void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                        mmpl_stream_t stream) {
   if (!h || h->w.empty()) return fail("mmpl_dit_forward", "weights not bound");
   const MmplDitConfig& c = h->cfg;
   if (nF < 1 || nF > c.max_frames) return fail("mmpl_dit_forward", "n_frames out of range");
@@ -440,10 +449,11 @@ int mmpl_dit_forward(MmplDit* h, const void* x_in, const float* t_dev, int nF, c
         a.q_scale = prescale_q ? scale * 1.4426950408889634f : 0.f;
         a.cos_tab = h->cos_tab; a.sin_tab = h->sin_tab; a.rows_per_frame = S; a.grid_w = h->gw;
         for (int i = 0; i < nF; ++i) {
-          a.frame_ids[i] = frame_ids[i];
+          a.frame_ids[i] = frame_ids[i];                     // relative to *frame_base_dev, which the kernel reads when it runs
           a.k_dst[i] = persist ? kc + (size_t)write_slots[i] * S * d : w.ksc + (size_t)i * S * d;
           a.v_dst[i] = persist ? vc + (size_t)write_slots[i] * S * d : w.vsc + (size_t)i * S * d;
         }
+        a.frame_base = frame_base_dev;
         ProfScope ps(K_QKNORM, 0, s);
         HIP_TRY(mmpl_launch_qknorm(a, s), "qk norm + rope + kv write");
       }
@@ -661,6 +671,12 @@ int mmpl_layernorm(const void* x, int ldx, void* y, int ldy, int rows, int d, fl
 int mmpl_qknorm_rope(MmplDit* h, void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* wq,
                      const void* wk, int n_frames, const int* frame_ids, void* const* k_dst, void* const* v_dst,
                      mmpl_stream_t stream) {
+  return mmpl_qknorm_rope_at(h, q, ldq, k, ldk, v, ldv, wq, wk, n_frames, frame_ids, k_dst, v_dst, nullptr, stream);
+}
+
+int mmpl_qknorm_rope_at(MmplDit* h, void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* wq,
+                        const void* wk, int n_frames, const int* frame_ids, void* const* k_dst, void* const* v_dst,
+                        const int* frame_base_dev, mmpl_stream_t stream) {
   if (!h) return fail("mmpl_qknorm_rope", "null handle");
   if (n_frames < 1 || n_frames > 8) return fail("mmpl_qknorm_rope", "n_frames out of range");
   QkNormArgs a = {};
@@ -668,6 +684,7 @@ int mmpl_qknorm_rope(MmplDit* h, void* q, int ldq, const void* k, int ldk, const
   a.wq = (const bf16_t*)wq; a.wk = (const bf16_t*)wk; a.rows = n_frames * h->S; a.d = h->cfg.dim; a.eps = h->cfg.eps; a.rope = 1;
   a.cos_tab = h->cos_tab; a.sin_tab = h->sin_tab; a.rows_per_frame = h->S; a.grid_w = h->gw;
   for (int i = 0; i < n_frames; ++i) { a.frame_ids[i] = frame_ids[i]; a.k_dst[i] = (bf16_t*)k_dst[i]; a.v_dst[i] = (bf16_t*)v_dst[i]; }
+  a.frame_base = frame_base_dev;
   HIP_TRY(mmpl_launch_qknorm(a, (hipStream_t)stream), "mmpl_qknorm_rope");
   return 0;
 }

@@ -201,11 +201,15 @@ __global__ __launch_bounds__(256) void layernorm_pipelined_kernel(LnArgs a, int 
 }
 
 struct RopeRow { float cs[4], sn[4]; int lf, tok; };
-MMPL_DEV void rope_row(const QkNormArgs& a, int row, int lane, bool live, RopeRow& r) {
+MMPL_DEV void rope_row(const QkNormArgs& a, int fbase, int row, int lane, bool live, RopeRow& r) {
   r.lf = a.rope ? row / a.rows_per_frame : 0;                     // local frame
   r.tok = a.rope ? row - r.lf * a.rows_per_frame : row;           // token inside the frame
   if (a.rope && live) {
-    const int gy = r.tok / a.grid_w, gx = r.tok - gy * a.grid_w, ft = a.frame_ids[r.lf];
+    const int gy = r.tok / a.grid_w, gx = r.tok - gy * a.grid_w;
+    // clamped to the tables' 0..1023: a stale base cannot index outside them.  Two scalar ops, written as asm so that the known range
+    // does not change how the table addresses below are formed (min/max in C++ cost 2 VGPRs and a wave of occupancy at NIT 3 and 6)
+    int ft = a.frame_ids[r.lf] + fbase;
+    asm("s_max_i32 %0, %0, 0\n\ts_min_i32 %0, %0, 0x3ff" : "+s"(ft) : : "scc");
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int p = 4 * (lane & 15) + j;                          // rotary pair index inside the head, 0..63
@@ -284,14 +288,16 @@ __global__ __launch_bounds__(256) void qknorm_kernel(QkNormArgs a, int groups_pe
   const float qs = (which == 0 && a.q_scale != 0.f) ? a.q_scale : 1.0f;   // softmax scale folded into q while it is still fp32 (attn_w64.hip)
   uint4 cur[NIT], nxt[NIT];
   RopeRow rc, rn;
-  rope_row(a, 4 * g + wv, lane, FULL || 4 * g + wv < a.rows, rc);
+  // the position base is device data: read once, ahead of every store of this kernel, from a kernel-argument address -- a scalar load
+  const int fbase = a.frame_base ? *a.frame_base : 0;
+  rope_row(a, fbase, 4 * g + wv, lane, FULL || 4 * g + wv < a.rows, rc);
   load_row<NIT, FULL>(cur, base + (size_t)(4 * g + wv) * ld, lane, nchunk, 4 * g + wv < a.rows);
   __syncthreads();
   for (;; ++g) {
     const int row = 4 * g + wv;
     const bool more = g + 1 < g_end;                              // block-uniform
     if (more) {
-      rope_row(a, row + 4, lane, FULL || row + 4 < a.rows, rn);   // older than the row's loads: back first
+      rope_row(a, fbase, row + 4, lane, FULL || row + 4 < a.rows, rn);   // older than the row's loads: back first
       load_row<NIT, FULL>(nxt, base + (size_t)(row + 4) * ld, lane, nchunk, row + 4 < a.rows);
     }
     asm volatile("" ::: "memory");                                // the prefetch is issued here, not where it is consumed

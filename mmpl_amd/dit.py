@@ -260,7 +260,8 @@ class DitEngine:
                 visible_slots: Sequence[int], k_cache: torch.Tensor, v_cache: torch.Tensor, cross_k: torch.Tensor,
                 cross_v: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                 cross_rows: Optional[int] = None, share_out: Optional[torch.Tensor] = None,
-                share_in: Optional[torch.Tensor] = None, attn_history: Optional[torch.Tensor] = None) -> torch.Tensor:
+                share_in: Optional[torch.Tensor] = None, attn_history: Optional[torch.Tensor] = None,
+                frame_base: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x: [nF, in_dim, lat_h, lat_w] bf16 (i2v: x and y concatenated on the channel axis); t: [nF] float32 (device).
         Returns the flow prediction [nF, 16, lat_h, lat_w].
         `cross_rows`: the `CrossKV.rows` that belongs to the CONTENTS of cross_k / cross_v (rows cross_rows .. text_len-1 repeat one
@@ -272,7 +273,10 @@ class DitEngine:
         branch, stage); blocks whose FAST pass failed then start in the GENERAL pass.  The output bits then depend on the forwards
         before (include/mmpl_hip.h); None = stateless.
         `workspace`: a private scratch buffer (>= workspace_bytes(nF)) for a forward that runs concurrently with another
-        one on a different stream (cond / uncond); default: the engine's own."""
+        one on a different stream (cond / uncond); default: the engine's own.
+        `frame_base`: an int32 device scalar; `frame_ids` are then relative to it (RoPE position = frame_ids[i] + its value WHEN THE
+        KERNELS RUN, clamped to the tables' 0..1023): a forward captured into a hipGraph is replayed at another position in time by
+        writing the scalar in stream order before the replay (mmpl_dit_forward_at).  None = absolute frame_ids."""
         nF = x.shape[0]
         assert x.is_contiguous() and x.dtype == torch.bfloat16 and x.shape[1:] == (self.in_dim, self.lat_h, self.lat_w)
         assert t.dtype == torch.float32 and t.numel() == nF and t.is_cuda
@@ -283,18 +287,21 @@ class DitEngine:
         if attn_history is not None:
             need = self._lib.mmpl_dit_attn_history_bytes(self._h, nF)
             assert attn_history.dtype == torch.uint8 and attn_history.is_contiguous() and attn_history.numel() >= need and attn_history.device == x.device
+        if frame_base is not None:
+            assert frame_base.dtype == torch.int32 and frame_base.numel() == 1 and frame_base.device == x.device, (frame_base.dtype, tuple(frame_base.shape))
         if out is None:
             out = torch.empty(nF, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=x.device)
         ws = self.workspace(nF) if workspace is None else workspace
         n_slots = k_cache.shape[1] // self.S
         ia = lambda v: (C.c_int * len(v))(*[int(i) for i in v])
         with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
-            _lib.check(self._lib.mmpl_dit_forward(
+            _lib.check(self._lib.mmpl_dit_forward_at(
                 self._h, _lib.ptr(x), _lib.ptr(t), nF, ia(frame_ids), ia(write_slots), ia(visible_slots), len(visible_slots),
                 _lib.ptr(k_cache), _lib.ptr(v_cache), n_slots, _lib.ptr(cross_k), _lib.ptr(cross_v),
                 self.text_len if cross_rows is None else int(cross_rows),
                 None if share_out is None else _lib.ptr(share_out), None if share_in is None else _lib.ptr(share_in),
-                None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "mmpl_dit_forward")
+                None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base),
+                _lib.stream_ptr()), "mmpl_dit_forward")
         return out
 
     # ------------------------------------------------------------------ hipGraph

@@ -15,7 +15,13 @@ What changed underneath:
   * the literals 30 / 12 / 1560 / 32760 come from the model config and the ``Geometry``;
   * ``inference_stream()`` (no counterpart in the reference) runs the same loop and hands the video out block by block: each
     block is decoded by the VAE's cached decode (``decode_to_pixel(use_cache=True)``'s engine) while the next one denoises --
-    or, with ``decoder="preview"``, by the tiny TAEHV decoder handed in as ``preview_vae`` (``TAEHVWrapper``).
+    or, with ``decoder="preview"``, by the tiny TAEHV decoder handed in as ``preview_vae`` (``TAEHVWrapper``);
+  * ``args.rolling_kv`` (no counterpart that runs in the reference, whose ``sink_size`` knob has nothing behind it): the KV cache
+    becomes a rolling window -- ``generator.model.sink_size`` sink frames kept, the oldest other frame evicted
+    (``wan_wrapper.rolling_slots``) -- so a call may generate more frames than the window holds.  Blocks past the window run on
+    frame ids relative to a device scalar (``DitEngine.forward(frame_base=...)``) and write their x0 into a static buffer that is
+    then copied into the output latent, so their graphs depend on the slot pattern only, not on the position in time: the
+    number of hipGraphs is bounded whatever the video length.
 """
 from __future__ import annotations
 
@@ -52,6 +58,7 @@ class CausalInferencePipeline(torch.nn.Module):
         self.num_frame_per_block = getattr(args, "num_frame_per_block", 1)
         self.independent_first_frame = getattr(args, "independent_first_frame", False)
         self.local_attn_size = self.generator.model.local_attn_size
+        self.rolling_kv = bool(getattr(args, "rolling_kv", False))       # rolling KV window with generator.model.sink_size sink frames
         if self.num_frame_per_block > self.generator.engine.max_frames:
             raise ValueError(f"num_frame_per_block {self.num_frame_per_block} > the engine's largest forward "
                              f"({self.generator.engine.max_frames} frames)")
@@ -66,6 +73,8 @@ class CausalInferencePipeline(torch.nn.Module):
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._bufs: Dict[int, dict] = {}  # static per-block buffers, by frames per block
         self._out: Dict[int, torch.Tensor] = {}                     # static output latents, by frame count
+        self._roll_bufs: Dict[tuple, torch.Tensor] = {}             # rolling blocks past the window: static x0, by graph key
+        self._frame_base: Optional[torch.Tensor] = None             # ... and the int32 device scalar their RoPE positions start from
         self._side: Optional[torch.cuda.Stream] = None              # inference_stream: the decode stream
         self._stage: Optional[torch.Tensor] = None                  # inference_stream: pinned uint8 staging, [2, frames, H, W, 3]
 
@@ -78,6 +87,8 @@ class CausalInferencePipeline(torch.nn.Module):
         self._graphs.clear()
         self._bufs.clear()
         self._out.clear()
+        self._roll_bufs.clear()
+        self._frame_base = None
 
     # ------------------------------------------------------------------------------------------------------------
     def block_schedule(self, num_frames: int, initial_latent: Optional[torch.Tensor] = None) -> List[int]:
@@ -122,25 +133,26 @@ class CausalInferencePipeline(torch.nn.Module):
             o = self._out[T] = torch.zeros(1, T, 16, g.lat_h, g.lat_w, dtype=torch.bfloat16, device=self.device)
         return o
 
-    def _run_block(self, b: dict, out_blk: torch.Tensor, start: int, write, vis, scalars) -> None:
-        """One block's launches (causal_inference.py:165-211): eager, or recorded into the block's hipGraph."""
+    def _run_block(self, b: dict, out_blk: torch.Tensor, start: int, write, vis, scalars, frame_base=None) -> None:
+        """One block's launches (causal_inference.py:165-211): eager, or recorded into the block's hipGraph.  ``frame_base``: the
+        device scalar `start` is relative to (a rolling block past the window: `start` is 0 and `out_blk` a static buffer)."""
         t_eng, sig_x0, sig_next = scalars
         gen, kv, cross = self.generator, self.kv_cache1, self.crossattn_cache
         n = len(t_eng)
         for i in range(n):
             b["t"].fill_(t_eng[i])
-            gen.flow(b["x"], b["t"], start, write, vis, kv, cross, out=b["flow"])
+            gen.flow(b["x"], b["t"], start, write, vis, kv, cross, out=b["flow"], frame_base=frame_base)
             if i < n - 1:                           # x0, then add_noise(x0, randn, next t) back into the block's input
                 gen.fewstep_update(b["flow"], b["x"], b["bank"][i], out_blk, sig_x0[i], sig_next[i])
             else:                                   # output[:, block] = denoised_pred
                 gen.fewstep_update(b["flow"], b["x"], None, out_blk, sig_x0[i])
         b["t"].fill_(float(getattr(self.args, "context_noise", 0)))    # refresh the cache with the clean block (:199-207)
-        gen.flow(out_blk, b["t"], start, write, vis, kv, cross, out=b["flow"])
+        gen.flow(out_blk, b["t"], start, write, vis, kv, cross, out=b["flow"], frame_base=frame_base)
 
     def _context_forward(self, lat: torch.Tensor, start: int) -> None:
         """A clean-latent forward at t = 0 that only fills the cache (initial_latent, causal_inference.py:130-159)."""
         x = lat.to(device=self.device, dtype=torch.bfloat16).contiguous()
-        write, vis, le = self.generator.slots(self.kv_cache1, start, x.shape[0])
+        write, vis, le = self.generator.slots(self.kv_cache1, start, x.shape[0], rolling=self.rolling_kv)
         t = torch.zeros(x.shape[0], dtype=torch.float32, device=self.device)
         self.generator.flow(x, t, start, write, vis, self.kv_cache1, self.crossattn_cache)
         self.generator.set_cache_ends(self.kv_cache1, start + x.shape[0], le)
@@ -158,6 +170,14 @@ class CausalInferencePipeline(torch.nn.Module):
         num_input_frames = initial_latent.shape[1] if initial_latent is not None else 0
         num_output_frames = num_frames + num_input_frames
         dev = self.device
+        W = self.generator.window_frames
+        if self.rolling_kv:
+            from ..wan_wrapper import ROPE_POSITIONS, rolling_slots
+            if num_output_frames > ROPE_POSITIONS:                        # the last block would fail: say so before anything runs
+                raise ValueError(f"rolling KV window: {num_output_frames} frames end past the RoPE tables' last position "
+                                 f"({ROPE_POSITIONS - 1})")
+            for F in set(schedule) | ({self.num_frame_per_block} if num_input_frames else set()):
+                rolling_slots(0, F, W, int(self.generator.model.sink_size))   # sink_size / block size against the window
         conditional_dict = self.text_encoder(text_prompts=text_prompts)
 
         if self.kv_cache1 is None:
@@ -199,28 +219,43 @@ class CausalInferencePipeline(torch.nn.Module):
         for F in schedule:
             s = current_start_frame
             b = self._block_buffers(F)
-            write, vis, le = self.generator.slots(self.kv_cache1, s, F)
+            write, vis, le = self.generator.slots(self.kv_cache1, s, F, rolling=self.rolling_kv)   # (rolling: checks the RoPE range)
             b["x"].copy_(noise_bf[0, s - num_input_frames:s - num_input_frames + F])
             for i in range(n - 1):                                        # the reference's torch.randn_like draws, in order
                 if draws is not None:
                     b["bank"][i].copy_(next(draws).reshape(b["bank"][i].shape))
                 else:
                     b["bank"][i].normal_(0.0, 1.0, generator=self.noise_generator)
-            out_blk = output[0, s:s + F]
-            key = (s, F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), num_output_frames, tuple(write),
-                   tuple(vis))
+            rolled = self.rolling_kv and s + F > W                        # a frame at or past the window: position-free launches
+            if not rolled:
+                out_blk, rel, base = output[0, s:s + F], s, None
+                key = (s, F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), num_output_frames, tuple(write),
+                       tuple(vis))
+            else:
+                # the slots say WHERE in the ring the block sits, and that repeats; WHEN it sits there is the device scalar, and
+                # its x0 goes to a buffer of the pattern's own: neither the start frame nor an address of `output` is in the launches
+                key = ("rolling", F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), tuple(write), tuple(vis))
+                if self._frame_base is None:
+                    self._frame_base = torch.zeros((), dtype=torch.int32, device=dev)
+                out_blk = self._roll_bufs.get(key)
+                if out_blk is None:
+                    out_blk = self._roll_bufs[key] = torch.empty_like(b["x"])
+                rel, base = 0, self._frame_base
+                base.fill_(s)                                             # in stream order ahead of the launches that read it
             g = self._graphs.get(key)
             if g is not None:
                 g.replay()
             else:
-                self._run_block(b, out_blk, s, write, vis, scalars)      # first use: the real work, eagerly ...
+                self._run_block(b, out_blk, rel, write, vis, scalars, base)   # first use: the real work, eagerly ...
                 if self.use_graphs:                                       # ... then the same launches into the block's graph
                     torch.cuda.synchronize(dev)
                     g = torch.cuda.CUDAGraph()
                     self.graph_captures += 1
                     with torch.cuda.graph(g):
-                        self._run_block(b, out_blk, s, write, vis, scalars)
+                        self._run_block(b, out_blk, rel, write, vis, scalars, base)
                     self._graphs[key] = g
+            if rolled:
+                output[0, s:s + F].copy_(out_blk)                         # on the compute stream: complete before the yield's consumers
             self.generator.set_cache_ends(self.kv_cache1, s + F, le)
             current_start_frame += F
             yield s, F, output

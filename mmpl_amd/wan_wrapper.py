@@ -435,6 +435,35 @@ def causal_slots(start_frame: int, n_frames: int, n_slots: int, window_frames: i
     return list(range(ls, le)), list(range(max(0, le - window_frames), le)), le
 
 
+ROPE_POSITIONS = 1024     # temporal positions the engine's RoPE tables hold (QkNormArgs cos_tab / sin_tab)
+
+
+def rolling_slots(start_frame: int, n_frames: int, window_frames: int, sink_frames: int = 0):
+    """KV slots of a block under the rolling window: the cache has ``window_frames`` slots, its first ``sink_frames`` are never
+    overwritten once written, the rest is a ring.  Frame f < window lives in slot f (as ``causal_slots`` puts it); frame
+    f >= window in slot ``sink + (f - sink) % (window - sink)``, i.e. over the oldest frame that is not a sink frame.  The block
+    attends to slots ``0 .. min(end, window) - 1`` IN SLOT ORDER (contiguous pages for the attention launcher): the sink frames
+    plus the most recent ``window - sink`` frames, its own included.  Returns (write_slots, visible_slots); the write slots of a
+    block may wrap (window 8, sink 2: frames 6, 7, 8 -> slots 6, 7, 2).  RoPE stays on the absolute frame id, hence the table limit.
+
+    ValueError: a sink outside ``0 <= sink < window``, a block of more than ``window - sink`` frames (it would overwrite its own
+    frames), a block whose last frame id exceeds the RoPE tables' last position."""
+    W, s = int(window_frames), int(sink_frames)
+    if s < 0 or s >= W:
+        raise ValueError(f"rolling KV window: sink_size {s} must satisfy 0 <= sink_size < window ({W} frames)")
+    if n_frames < 1 or start_frame < 0:
+        raise ValueError(f"rolling KV window: bad block (start frame {start_frame}, {n_frames} frames)")
+    R = W - s
+    if n_frames > R:
+        raise ValueError(f"rolling KV window: a block of {n_frames} frames does not fit the {R} rolling slots "
+                         f"(window {W} - sink_size {s})")
+    end = start_frame + n_frames
+    if end - 1 > ROPE_POSITIONS - 1:
+        raise ValueError(f"rolling KV window: frame id {end - 1} is past the RoPE tables' last position ({ROPE_POSITIONS - 1})")
+    write = [f if f < W else s + (f - s) % R for f in range(start_frame, end)]
+    return write, list(range(min(end, W)))
+
+
 class _CausalModelHandle(_ModelHandle):
     """`generator.model` of the causal wrapper: the reference's CausalWanModel attributes the pipeline reads or sets."""
 
@@ -517,9 +546,16 @@ class WanDiffusionWrapper(torch.nn.Module):
         return float(s.sigmas[torch.argmin((s.timesteps.unsqueeze(0) - t.unsqueeze(1)).abs(), dim=1)].item())
 
     # -- device pieces (capturable) ------------------------------------------------------------------------------------------
-    def slots(self, kv_cache: KVCache, start_frame: int, n_frames: int):
-        """(write_slots, visible_slots, local_end) of a forward at `start_frame` against `kv_cache`'s current bookkeeping."""
+    def slots(self, kv_cache: KVCache, start_frame: int, n_frames: int, rolling: bool = False):
+        """(write_slots, visible_slots, local_end) of a forward at `start_frame` against `kv_cache`'s current bookkeeping.
+        ``rolling``: the rolling window with ``model.sink_size`` sink frames (``rolling_slots``) over a cache of exactly
+        ``window_frames`` slots; local_end is then ``min(start + n, window)``, what ``set_cache_ends`` records."""
         n_slots = kv_cache.k_all.shape[1] // self.engine.S
+        if rolling:
+            if n_slots != self.window_frames:
+                raise ValueError(f"rolling KV window: the cache holds {n_slots} frame slots, the window is {self.window_frames}")
+            write, vis = rolling_slots(start_frame, n_frames, self.window_frames, int(self.model.sink_size))
+            return write, vis, min(start_frame + n_frames, self.window_frames)
         return causal_slots(start_frame, n_frames, n_slots, self.window_frames, int(kv_cache[0]["local_end_index"][0]),
                             int(kv_cache[0]["global_end_index"][0]))
 
@@ -532,12 +568,14 @@ class WanDiffusionWrapper(torch.nn.Module):
             blk["local_end_index"].fill_(local_end_frame * S)
 
     def flow(self, x: torch.Tensor, t: torch.Tensor, start_frame: int, write_slots, visible_slots, kv_cache: KVCache,
-             crossattn_cache: CrossAttnCache, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+             crossattn_cache: CrossAttnCache, out: Optional[torch.Tensor] = None,
+             frame_base: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One CausalWanModel._forward_inference on explicit slots: x [F, 16, h, w] bf16, t [F] float32 on the device.  Stateless
-        attention; the text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch)."""
+        attention; the text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch).
+        ``frame_base`` (int32 device scalar): `start_frame` is then relative to its value at execution time (DitEngine.forward)."""
         frames = [start_frame + i for i in range(x.shape[0])]
         return self.engine.forward(x, t, frames, write_slots, visible_slots, kv_cache.k_all, kv_cache.v_all, crossattn_cache.k_all,
-                                   crossattn_cache.v_all, out=out)
+                                   crossattn_cache.v_all, out=out, frame_base=frame_base)
 
     @staticmethod
     def fewstep_update(flow: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], x0_out: torch.Tensor, sigma_t: float,
