@@ -13,6 +13,7 @@
 #include "../../include/mmpl_hip.h"
 #include "kernels.h"
 #include "mmpl_config.h"
+#include "mmpl_error.h"
 
 static thread_local std::string g_err;
 static int fail(const char* where, const char* what) {
@@ -102,7 +103,7 @@ struct MmplDit {
   float* cos_tab = nullptr;  // [1024][64]
   float* sin_tab = nullptr;
   std::vector<const bf16_t*> w;
-  unsigned long long* attn_stats = nullptr;    // mmpl_dit_set_attn_stats: 4 counters of the self-attention launches (header)
+  unsigned long long* attn_stats = nullptr;    // mmpl_dit_set_attn_stats: 5 counters of the self-attention launches (header)
   unsigned long long* share_chk = nullptr;     // MMPL_CHECK_SHARE=1: {producer fingerprint[2], consumer fingerprint[2], mismatches} (device)
   const bf16_t* G(int i) const { return w[i]; }
   const bf16_t* Lw(int l, int i) const { return w[NG + l * NL + i]; }
@@ -265,6 +266,25 @@ int gemm(const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias,
   return 0;
 }
 #define TRY(x) do { if ((x) != 0) return 1; } while (0)
+
+// Epilogue and operand validation of the mmpl_gemm* entries (all three report it as "mmpl_gemm").
+int gemm_check_epilogue(int epi, const void* res, const void* gate) {
+  if (epi < EPI_BIAS || epi > EPI_F32_SCALE) return fail("mmpl_gemm", "unknown epilogue");
+  if ((epi == EPI_GATE_RES && (!res || !gate)) || (epi == EPI_RES && !res)) return fail("mmpl_gemm", "missing epilogue operand");
+  return 0;
+}
+
+// The argument list mmpl_attn_fwd_variant and mmpl_attn_fwd_history share (n_pages already checked against MMPL_MAX_PAGES).
+AttnArgs attn_entry_args(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages, int ldk,
+                         int ldv, int n_pages, int page_rows, int Lq, int num_heads, float softmax_scale, void* workspace,
+                         size_t workspace_bytes) {
+  AttnArgs a = {};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv; a.n_pages = n_pages;
+  a.page_rows = page_rows; a.Lq = Lq; a.H = num_heads; a.scale = softmax_scale;
+  a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
+  for (int i = 0; i < n_pages; ++i) { a.k_pages[i] = (const bf16_t*)k_pages[i]; a.v_pages[i] = (const bf16_t*)v_pages[i]; }
+  return a;
+}
 }  // namespace
 
 extern "C" {
@@ -577,15 +597,12 @@ int mmpl_attn_fwd_history(const void* q, int ldq, void* o, int ldo, const void* 
                           void* workspace, size_t workspace_bytes, void* history, void* stats_dev, mmpl_stream_t stream) {
   if (n_pages < 1 || n_pages > MMPL_MAX_PAGES) return fail("mmpl_attn_fwd_history", "n_pages out of range");
   if (reinterpret_cast<uintptr_t>(stats_dev) % 8) return fail("mmpl_attn_fwd_history", "stats must be 8-byte aligned");
-  AttnArgs a = {};
+  AttnArgs a = attn_entry_args(q, ldq, o, ldo, k_pages, v_pages, ldk, ldv, n_pages, page_rows, Lq, num_heads, softmax_scale, workspace,
+                               workspace_bytes);
   a.variant = ATTN_W64;
   a.q_prescaled = 1;
-  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv; a.n_pages = n_pages;
-  a.page_rows = page_rows; a.Lq = Lq; a.H = num_heads; a.scale = softmax_scale;
-  a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
   a.history = (unsigned char*)history;
   a.redo_stats = (unsigned long long*)stats_dev;
-  for (int i = 0; i < n_pages; ++i) { a.k_pages[i] = (const bf16_t*)k_pages[i]; a.v_pages[i] = (const bf16_t*)v_pages[i]; }
   HIP_TRY(mmpl_launch_attention(a, (hipStream_t)stream), "mmpl_attn_fwd_history");
   return 0;
 }
@@ -599,14 +616,11 @@ int mmpl_attn_fwd_variant(const void* q, int ldq, void* o, int ldo, const void* 
   if (n_pages < 1 || n_pages > MMPL_MAX_PAGES) return fail("mmpl_attn_fwd", "n_pages out of range");
   if (variant != ATTN_AUTO && variant != ATTN_LOCKSTEP && variant != ATTN_W64 && variant != ATTN_W64 + 1)
     return fail("mmpl_attn_fwd", "unknown kernel variant");
-  AttnArgs a = {};
+  AttnArgs a = attn_entry_args(q, ldq, o, ldo, k_pages, v_pages, ldk, ldv, n_pages, page_rows, Lq, num_heads, softmax_scale, workspace,
+                               workspace_bytes);
   a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
   a.q_prescaled = variant == ATTN_W64 + 1;
   a.cross = cross != 0;
-  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv; a.n_pages = n_pages;
-  a.page_rows = page_rows; a.Lq = Lq; a.H = num_heads; a.scale = softmax_scale;
-  a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
-  for (int i = 0; i < n_pages; ++i) { a.k_pages[i] = (const bf16_t*)k_pages[i]; a.v_pages[i] = (const bf16_t*)v_pages[i]; }
   HIP_TRY(mmpl_launch_attention(a, (hipStream_t)stream), "mmpl_attn_fwd");
   return 0;
 }
@@ -628,17 +642,13 @@ int mmpl_attn_fwd(const void* q, int ldq, void* o, int ldo, const void* const* k
 int mmpl_gemm(const void* A, int lda, const void* W, int ldw, const void* bias, void* C, int ldc, int M, int N, int K,
               int epi, const void* res, int ldres, const void* gate, int gate_frame_stride, int rows_per_frame,
               mmpl_stream_t stream) {
-  if (epi < EPI_BIAS || epi > EPI_F32_SCALE) return fail("mmpl_gemm", "unknown epilogue");
-  if ((epi == EPI_GATE_RES && (!res || !gate)) || (epi == EPI_RES && !res)) return fail("mmpl_gemm", "missing epilogue operand");
-  return gemm((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (bf16_t*)C, ldc, M, N, K, epi,
-              (const bf16_t*)res, ldres, (const bf16_t*)gate, gate_frame_stride, rows_per_frame, (hipStream_t)stream);
+  return mmpl_gemm_tickets(A, lda, W, ldw, bias, C, ldc, M, N, K, epi, res, ldres, gate, gate_frame_stride, rows_per_frame, nullptr, stream);
 }
 
 int mmpl_gemm_tickets(const void* A, int lda, const void* W, int ldw, const void* bias, void* C, int ldc, int M, int N, int K,
                       int epi, const void* res, int ldres, const void* gate, int gate_frame_stride, int rows_per_frame,
                       void* tile_counter, mmpl_stream_t stream) {
-  if (epi < EPI_BIAS || epi > EPI_F32_SCALE) return fail("mmpl_gemm", "unknown epilogue");
-  if ((epi == EPI_GATE_RES && (!res || !gate)) || (epi == EPI_RES && !res)) return fail("mmpl_gemm", "missing epilogue operand");
+  TRY(gemm_check_epilogue(epi, res, gate));
   return gemm((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (bf16_t*)C, ldc, M, N, K, epi,
               (const bf16_t*)res, ldres, (const bf16_t*)gate, gate_frame_stride, rows_per_frame, (hipStream_t)stream, (int*)tile_counter);
 }
@@ -649,8 +659,7 @@ int mmpl_device_xcd_round_robin(void) { return mmpl_xcd_dispatch_ok(true) ? 1 : 
 int mmpl_gemm_scratch(const void* A, int lda, const void* W, int ldw, const void* bias, void* C, int ldc, int M, int N, int K,
                       int epi, const void* res, int ldres, const void* gate, int gate_frame_stride, int rows_per_frame,
                       void* scratch, size_t scratch_bytes, mmpl_stream_t stream) {
-  if (epi < EPI_BIAS || epi > EPI_F32_SCALE) return fail("mmpl_gemm", "unknown epilogue");
-  if ((epi == EPI_GATE_RES && (!res || !gate)) || (epi == EPI_RES && !res)) return fail("mmpl_gemm", "missing epilogue operand");
+  TRY(gemm_check_epilogue(epi, res, gate));
   if (!scratch || scratch_bytes < mmpl_gemm_scratch_bytes()) return fail("mmpl_gemm_scratch", "scratch missing or smaller than mmpl_gemm_scratch_bytes()");
   if (reinterpret_cast<uintptr_t>(scratch) % 256) return fail("mmpl_gemm_scratch", "scratch must be 256-byte aligned");
   return gemm((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (bf16_t*)C, ldc, M, N, K, epi,

@@ -13,7 +13,7 @@
 
 #pragma clang fp contract(off)
 
-extern int mmpl_set_error(const char* where, const char* what);  // api.hip
+#include "mmpl_error.h"
 
 namespace {
 

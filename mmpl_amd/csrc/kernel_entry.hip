@@ -9,7 +9,7 @@
 #include "taehv_kernels.h"
 #include "vae_kernels.h"
 
-extern int mmpl_set_error(const char* where, const char* what);  // api.hip
+#include "mmpl_error.h"
 
 namespace {
 inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }

@@ -11,7 +11,7 @@
 
 #include "../../include/mmpl_hip.h"
 
-extern int mmpl_set_error(const char* where, const char* what);  // api.hip
+#include "mmpl_error.h"
 
 namespace {
 typedef __attribute__((ext_vector_type(8))) short pbf16x8;

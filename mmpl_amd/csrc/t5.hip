@@ -10,7 +10,7 @@
 #include "../../include/mmpl_hip.h"
 #include "kernels.h"
 
-extern int mmpl_set_error(const char* where, const char* what);  // api.hip
+#include "mmpl_error.h"
 
 namespace {
 

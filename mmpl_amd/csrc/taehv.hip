@@ -19,7 +19,7 @@
 #include "kernels.h"
 #include "taehv_kernels.h"
 
-extern int mmpl_set_error(const char* where, const char* what);  // api.hip
+#include "mmpl_error.h"
 
 namespace {
 

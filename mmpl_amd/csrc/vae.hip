@@ -13,7 +13,7 @@
 #include "mmpl_config.h"
 #include "vae_kernels.h"
 
-extern int mmpl_set_error(const char* where, const char* what);  // api.hip
+#include "mmpl_error.h"
 
 namespace {
 

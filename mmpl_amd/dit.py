@@ -18,10 +18,40 @@ import torch
 
 from . import _lib
 
-_GLOBAL_KEYS = ["patch_embedding.weight", "patch_embedding.bias", "text_embedding.0.weight", "text_embedding.0.bias",
-                "text_embedding.2.weight", "text_embedding.2.bias", "time_embedding.0.weight", "time_embedding.0.bias",
-                "time_embedding.2.weight", "time_embedding.2.bias", "time_projection.1.weight", "time_projection.1.bias",
-                "head.modulation", "head.head.weight", "head.head.bias"]
+# The library's packed weight slots, under the names mmpl_dit_weight_name reports: (g, layer prefix, num_layers, dim) -> tensor
+_PACKERS = {
+    "pack:blocks.*.modulation[L,6,dim]": lambda g, p, L, dim: torch.stack([g(f"blocks.{i}.modulation").reshape(6, dim) for i in range(L)]),
+    "pack:self_attn.{q,k,v}.weight[3dim,dim]": lambda g, p, L, dim: torch.cat([g(p + f"self_attn.{x}.weight") for x in "qkv"]),
+    "pack:self_attn.{q,k,v}.bias[3dim]": lambda g, p, L, dim: torch.cat([g(p + f"self_attn.{x}.bias") for x in "qkv"]),
+}
+
+
+def weight_slot_names(lib, per_layer: int) -> List[str]:
+    """The library's global (per_layer 0) or per-layer (1) weight slots, in bind order."""
+    names: List[str] = []
+    while (n := lib.mmpl_dit_weight_name(len(names), per_layer)) is not None:
+        names.append(n.decode())
+    return names
+
+
+def slot_tensors(lib, g, num_layers: int, dim: int, in_dim: int) -> List[torch.Tensor]:
+    """What mmpl_dit_bind_weights takes, in the order the library reports its slots.  `g(key)` fetches one state-dict tensor; a plain
+    slot name is that key ("blocks.N." in front of a per-layer one), a "pack:" one is built by its packer."""
+    def slot(name: str, p: str = "") -> torch.Tensor:
+        if name.startswith("pack:"):
+            if name not in _PACKERS:
+                raise KeyError(f"mmpl_dit_weight_name reports the packed slot {name!r}, which DitEngine has no packer for")
+            return _PACKERS[name](g, p, num_layers, dim).contiguous()
+        t = g(p + name)
+        if name == "patch_embedding.weight":
+            t = t.reshape(t.shape[0], -1)
+            pe_k = (t.shape[1] + 63) // 64 * 64         # K of the patch GEMM: 4 * in_dim padded to a multiple of 64 (zeros)
+            assert t.shape[1] == 4 * in_dim, (tuple(t.shape), in_dim)
+            t = torch.nn.functional.pad(t, (0, pe_k - t.shape[1])).contiguous()
+        return t
+
+    per_layer = weight_slot_names(lib, 1)
+    return [slot(n) for n in weight_slot_names(lib, 0)] + [slot(n, f"blocks.{i}.") for i in range(num_layers) for n in per_layer]
 
 
 class CrossKV(tuple):
@@ -90,26 +120,7 @@ class DitEngine:
         def g(k):
             return sd[prefix + k].to(device=dev, dtype=bf).contiguous()
 
-        w: List[torch.Tensor] = []
-        for k in _GLOBAL_KEYS:
-            t = g(k)
-            if k == "patch_embedding.weight":
-                t = t.reshape(t.shape[0], -1)
-                pe_k = (t.shape[1] + 63) // 64 * 64         # K of the patch GEMM: 4 * in_dim padded to a multiple of 64 (zeros)
-                assert t.shape[1] == 4 * self.in_dim, (tuple(t.shape), self.in_dim)
-                t = torch.nn.functional.pad(t, (0, pe_k - t.shape[1])).contiguous()
-            w.append(t)
-        w.append(torch.stack([g(f"blocks.{i}.modulation").reshape(6, self.dim) for i in range(self.L)]).contiguous())
-        for i in range(self.L):
-            p = f"blocks.{i}."
-            w.append(torch.cat([g(p + "self_attn.q.weight"), g(p + "self_attn.k.weight"), g(p + "self_attn.v.weight")]).contiguous())
-            w.append(torch.cat([g(p + "self_attn.q.bias"), g(p + "self_attn.k.bias"), g(p + "self_attn.v.bias")]).contiguous())
-            for k in ("self_attn.norm_q.weight", "self_attn.norm_k.weight", "self_attn.o.weight", "self_attn.o.bias",
-                      "norm3.weight", "norm3.bias", "cross_attn.q.weight", "cross_attn.q.bias", "cross_attn.norm_q.weight",
-                      "cross_attn.k.weight", "cross_attn.k.bias", "cross_attn.norm_k.weight", "cross_attn.v.weight",
-                      "cross_attn.v.bias", "cross_attn.o.weight", "cross_attn.o.bias", "ffn.0.weight", "ffn.0.bias",
-                      "ffn.2.weight", "ffn.2.bias"):
-                w.append(g(p + k))
+        w = slot_tensors(self._lib, g, self.L, self.dim, self.in_dim)
         n = self._lib.mmpl_dit_num_weights(C.byref(self._c))
         assert len(w) == n, (len(w), n)
         arr = (C.c_void_p * n)(*[t.data_ptr() for t in w])
