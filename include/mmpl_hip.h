@@ -438,6 +438,41 @@ int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long
                     int Nsplit, int relu, const void* skip, long long fss, void* keep, mmpl_stream_t stream);
 /* taehv_prep_kernel: z [16, h, w] -> bf16(tanh(z / 3) * 3) -> channels [0, 16) of the interior of dst [h + 2, w + 2, 32] (16-byte aligned). */
 int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream);
+/* The GEMM (gemm.hip) in every form the DiT forward, T5, CLIP and the VAE launch it, for tests/test_gemm_forms_gpu.py: the arguments
+ * of mmpl_gemm_scratch plus what only the internal callers could set.  mmpl_gemm / _tickets / _scratch are unchanged.
+ *   epi     0-4 as mmpl_gemm; 5: C is dev float32 [M, ldc], C = float(alpha * acc), 16-byte aligned, bias must be NULL; 6: bias, and the columns
+ *           n >= v_col0 of row m go to v_dst[m / rows_per_frame] + (m % rows_per_frame) * v_ld + (n - v_col0) instead of C, whose
+ *           columns >= v_col0 are not written (the V third of the fused qkv projection into per-frame KV pages).
+ *   A       [M, lda], W [N, ldw]: lda, ldw % 8 == 0 and >= K, K % 64 == 0, 16-byte aligned.  bias NULL (= 0) or [N].  N % 4 == 0.
+ *   C       [M, ldc], ldc % 4 == 0, ldc >= N; rows m < M, columns n < N are written and nothing else.  8-byte aligned, as are res, gate,
+ *           bias and the pages; when any of them (or N, a stride, v_col0, v_ld) is not 8-element aligned the 256 x 256 kernels take
+ *           their direct 8-byte epilogue instead of the LDS-staged 16-byte one, as they do for epi 3 with rows_per_frame < 128.
+ *   res     epi 3 / 4: [M, ldres], ldres >= N, ldres % 4 == 0; may be C itself.  gate (epi 3): [ceil(M / rows_per_frame),
+ *           gate_frame_stride] with N valid columns, gate_frame_stride % 4 == 0; row m uses gate row m / rows_per_frame.  With more
+ *           than one frame (M > rows_per_frame) gate_frame_stride is >= N, or 0 for one gate row shared by every frame; gate holds
+ *           (frames - 1) * gate_frame_stride + N elements.
+ *   alpha   epi 5 only.
+ *   batch   >= 1.  batch > 1 (epi 0, 1, 2, 5; small-problem kernel only, which the launcher then always picks): problem b reads
+ *           A + b * sA, W + b * sW and writes C + b * sC (elements of C's type); sA, sW % 8 == 0, sC % 4 == 0.  A must hold
+ *           (batch - 1) * sA + (M - 1) * lda + K elements, W likewise, C (batch - 1) * sC + (M - 1) * ldc + N.
+ *   v_dst   epi 6: host array of 1 <= n_v_dst <= 8 device pages with n_v_dst * rows_per_frame >= M; page f holds
+ *           min(rows_per_frame, M - f * rows_per_frame) rows of v_ld >= N - v_col0 elements (v_ld, v_col0 % 4 == 0, 0 < v_col0 < N),
+ *           of which the first N - v_col0 are written.
+ *   scratch NULL, or mmpl_gemm_scratch_bytes() device bytes, 256-byte aligned, as for mmpl_gemm_scratch (first 2048 bytes zero before
+ *           and after every launch).  With scratch NULL: tile_counter NULL, or 8 device ints as for mmpl_gemm_tickets.
+ *   plan_out NULL or 6 host ints, filled from the launcher's own plan before the launch (all 0 when the call is rejected):
+ *           [0] kernel: 1 gemm_bf16_kernel (128 x 128, small problems and every batched one), 2 gemm_bf16_v2_kernel (256 x 128),
+ *               3 gemm_bf16_v6_kernel, 4 gemm_bf16_v8_kernel (256 x 256);
+ *           [1] tail launch for the partial last round of 256 x 256 tiles: 0 none, 1 split-K, 2 128 x 128 quadrants on the DMA-ring
+ *               body (8 tile buffers of LDS), 3 the same on the register-staged body (4 tile buffers);
+ *           [2] 1 = LDS-staged epilogue (main launch and split-K tail; the 128 x 128 quadrants of a tail always store directly);
+ *           [3] blocks of the main launch (0: skipped, every tile runs in the tail launch);
+ *           [4] blocks of the tail launch; [5] split-K parts per tail tile (1 = no split).
+ * Every check runs before the first HIP call and a rejected call launches nothing. */
+int mmpl_gemm_ex(const void* A, int lda, const void* W, int ldw, const void* bias, void* C, int ldc, int M, int N, int K, int epi,
+                 const void* res, int ldres, const void* gate, int gate_frame_stride, int rows_per_frame, float alpha, int batch,
+                 long long sA, long long sW, long long sC, void* const* v_dst, int n_v_dst, int v_col0, int v_ld, void* scratch,
+                 size_t scratch_bytes, void* tile_counter, int* plan_out, mmpl_stream_t stream);
 
 /* Optional per-kernel-class hipEvent timing (bench.py's live roofline numbers; off by default, not thread-safe).
  * kinds: 0 gemm, 1 self-attention, 2 cross-attention, 3 layernorm, 4 qk-norm/rope/kv-write, 5 elementwise, 6 cfg+unipc,

@@ -1209,21 +1209,68 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
+constexpr int GEMM_SYNC_SWEEPS = 1;   // GemmArgs.sync_sweeps of every v6 / v8 launch (the plan's tile lists assume it)
+
+// The launchers below decide nothing: which kernel, which tail, how many blocks, which epilogue form all come from the GemmPlan.
 template <int EPI>
-hipError_t launch_v6(const GemmArgs& g, hipStream_t s) {
+hipError_t launch_v6(const GemmArgs& g, const GemmPlan& p, hipStream_t s) {
   constexpr int smem = 2 * STAGE4 + 1024;        // ring + the L2 prefetch's dump area
   if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v6_kernel<EPI>), smem); e != hipSuccess) return e;
   if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v6_kernel<EPI, true>), smem); e != hipSuccess) return e;
   if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v8_kernel<EPI>), 2 * STAGE4 + 2048); e != hipSuccess) return e;
   if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_tail128_kernel<EPI, true>), 8 * TILE_BYTES); e != hipSuccess) return e;
   if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_tail128_kernel<EPI, false>), 4 * TILE_BYTES); e != hipSuccess) return e;
-  // main-launch kernel: v8 (one wave per SIMD, 128 x 128 per wave) or v6 (two, 128 x 64).  MMPL_GEMM_V8 = 1 / 0 forces it.
-  const int env_v8 = mmpl_config().gemm_v8;
-  const bool use_v8 = env_v8 >= 0 ? env_v8 != 0 : g.N >= 8192;       // the wide GEMMs (qkv, ffn0): profiles/r04c_gemm_v8_*.log
-  const int tiles = ((g.M + BM3 - 1) / BM3) * ((g.N + BN3 - 1) / BN3);
   GemmArgs g2 = g;
+  g2.group = p.group;
+  g2.staged_epilogue = p.staged_epilogue;
+  // L2 prefetch distance (k-tiles): 2 measured best on the 14B / 720p block shapes (+1 % qkv / o / ffn0, +6 % ffn2 whose A operand is
+  // 700 MB; 1 = no gain, 4 and more lose again); MMPL_GEMM_PF=0 switches it off
+  g2.pf_dist = mmpl_config().gemm_pf;
+  g2.sync_sweeps = GEMM_SYNC_SWEEPS;
+  // (the main kernel only looks at splitk_s > 1: stop at the full rounds; a 128 x 128 tail says 4)
+  g2.splitk_s = p.tail == GEMM_TAIL_NONE ? 1 : p.tail == GEMM_TAIL_SPLITK ? p.splitk_s : 4;
+  g2.splitk_tb = p.tail_tiles;
+  g2.splitk_per = p.cus_per_xcd;
+  if (!p.tickets) g2.tile_counter = nullptr;                  // one round or less: nothing to balance
+  if (p.main_blocks > 0) {
+    if (p.kernel == GEMM_KERNEL_V8) hipLaunchKernelGGL(gemm_bf16_v8_kernel<EPI>, dim3(p.main_blocks), dim3(256), 2 * STAGE4 + 2048, s, g2);
+    else hipLaunchKernelGGL(gemm_bf16_v6_kernel<EPI>, dim3(p.main_blocks), dim3(512), smem, s, g2);
+  }
+  if (p.tail == GEMM_TAIL_SPLITK) hipLaunchKernelGGL((gemm_bf16_v6_kernel<EPI, true>), dim3(p.tail_blocks), dim3(512), smem, s, g2);
+  else if (p.tail == GEMM_TAIL_128_8) hipLaunchKernelGGL((gemm_tail128_kernel<EPI, true>), dim3(p.tail_blocks), dim3(256), 8 * TILE_BYTES, s, g2);
+  else if (p.tail == GEMM_TAIL_128_4) hipLaunchKernelGGL((gemm_tail128_kernel<EPI, false>), dim3(p.tail_blocks), dim3(256), 4 * TILE_BYTES, s, g2);
+  return hipGetLastError();
+}
+
+template <int EPI>
+hipError_t launch_v2(const GemmArgs& g, const GemmPlan& p, hipStream_t s) {
+  constexpr int smem = NSTAGE2 * STAGE2;
+  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v2_kernel<EPI>), smem); e != hipSuccess) return e;
+  hipLaunchKernelGGL(gemm_bf16_v2_kernel<EPI>, dim3(p.main_blocks), dim3(512), smem, s, g);
+  return hipGetLastError();
+}
+
+template <int EPI>
+hipError_t launch(const GemmArgs& g, hipStream_t s) {
+  const GemmPlan p = mmpl_gemm_plan(g);
+  if (p.kernel == GEMM_KERNEL_V6 || p.kernel == GEMM_KERNEL_V8) return launch_v6<EPI>(g, p, s);
+  if (p.kernel == GEMM_KERNEL_V2) return launch_v2<EPI>(g, p, s);
+  constexpr int smem = 4 * TILE_BYTES;
+  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_kernel<EPI>), smem); e != hipSuccess) return e;
+  const int batch = g.batch > 1 ? g.batch : 1;
+  hipLaunchKernelGGL(gemm_bf16_kernel<EPI>, dim3(p.main_blocks / batch, batch), dim3(256), smem, s, g);
+  return hipGetLastError();
+}
+
+// The plan of the 256 x 256 kernels (v6 / v8): main-launch kernel, block order, epilogue form and the tail of the partial last round.
+GemmPlan plan_v6(const GemmArgs& g) {
+  GemmPlan p = {};
   const MmplRuntimeConfig& rc = mmpl_config();
-  const int env_group = rc.gemm_group;
+  // main-launch kernel: v8 (one wave per SIMD, 128 x 128 per wave) or v6 (two, 128 x 64).  MMPL_GEMM_V8 = 1 / 0 forces it.
+  const int env_v8 = rc.gemm_v8;
+  const bool use_v8 = env_v8 >= 0 ? env_v8 != 0 : g.N >= 8192;       // the wide GEMMs (qkv, ffn0): profiles/r04c_gemm_v8_*.log
+  p.kernel = use_v8 ? GEMM_KERNEL_V8 : GEMM_KERNEL_V6;
+  const int tiles_m = (g.M + BM3 - 1) / BM3, tiles_n = (g.N + BN3 - 1) / BN3, tiles = tiles_m * tiles_n;
   // M-tile group of the block order (how many row panels the tiles in flight on an XCD span).  Round 3 swept it on the kernels of the
   // time (profiles/r03d_*, r03C_*) and gave the narrow (N < 8192) GEMMs groups of 3 (2 for the long-K one) where the row panels divide
   // by 3; re-swept in round 6 on today's kernels (staged epilogue in phases, split-K tail; profiles/r06w_gemm_group_sweep_v6_shapes.log,
@@ -1232,113 +1279,88 @@ hipError_t launch_v6(const GemmArgs& g, hipStream_t s) {
   //   M = 21600 (85 row panels): o 1293 / 1307 / 1331 / 1310 / 1326, ffn2 1344 / 1345 / 1396 / 1350 / 1388
   // -> 4 (also what the wide GEMMs on v8 keep: profiles/r05g_gemm_group_sweep.log), except the narrow short-K GEMMs (o, cross-q,
   // cross-o) of the 7-frame stage (>= 96 row panels): 8.
-  const int tiles_m_ = (g.M + BM3 - 1) / BM3;
-  g2.group = env_group > 0 ? env_group : ((tiles_m_ >= 96 && g.N < 8192 && g.K < 8192) ? 8 : 4);
+  p.group = rc.gemm_group > 0 ? rc.gemm_group : ((tiles_m >= 96 && g.N < 8192 && g.K < 8192) ? 8 : 4);
   // the 16-byte epilogue needs 8-element alignment of everything it touches; otherwise the direct 8-byte one
   // (strides AND base pointers: mmpl_gemm is public ABI and callers hand in views such as a column-offset C)
-  auto al = [](const void* p, uintptr_t a) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % a == 0; };
+  auto al = [](const void* ptr, uintptr_t a) { return ptr == nullptr || reinterpret_cast<uintptr_t>(ptr) % a == 0; };
   bool ptrs_ok = al(g.C, 16) && al(g.bias, 8);
   if (g.epi == EPI_GATE_RES || g.epi == EPI_RES) ptrs_ok = ptrs_ok && al(g.res, 16);
   if (g.epi == EPI_GATE_RES) ptrs_ok = ptrs_ok && al(g.gate, 16);
   if (g.epi == EPI_BIAS_VPAGES)
     for (int i = 0; i < 8; ++i) ptrs_ok = ptrs_ok && al(g.v_dst[i], 16);
-  g2.staged_epilogue = ptrs_ok && g.N % 8 == 0 && g.ldc % 8 == 0 &&
-                       (g.epi != EPI_GATE_RES || (g.gate_frame_stride % 8 == 0 && g.rows_per_frame >= 128)) &&
-                       ((g.epi != EPI_GATE_RES && g.epi != EPI_RES) || g.ldres % 8 == 0) &&
-                       (g.epi != EPI_BIAS_VPAGES || (g.v_col0 % 8 == 0 && g.v_ld % 8 == 0));
-  // L2 prefetch distance (k-tiles): 2 measured best on the 14B / 720p block shapes (+1 % qkv / o / ffn0, +6 % ffn2 whose A operand is
-  // 700 MB; 1 = no gain, 4 and more lose again); MMPL_GEMM_PF=0 switches it off
-  g2.pf_dist = rc.gemm_pf;
-  g2.sync_sweeps = 1;
+  // (a gate frame shorter than the 128-row sub-tile would need more than the two candidate gate rows the staged epilogue holds)
+  // (EPI_F32_SCALE stores 16 bytes per lane as it is: the kernels have no staged form of it)
+  p.staged_epilogue = g.epi != EPI_F32_SCALE && ptrs_ok && g.N % 8 == 0 && g.ldc % 8 == 0 &&
+                      (g.epi != EPI_GATE_RES || (g.gate_frame_stride % 8 == 0 && g.rows_per_frame >= 128)) &&
+                      ((g.epi != EPI_GATE_RES && g.epi != EPI_RES) || g.ldres % 8 == 0) &&
+                      (g.epi != EPI_BIAS_VPAGES || (g.v_col0 % 8 == 0 && g.v_ld % 8 == 0));
   const int per = mmpl_cus_per_xcd(), n_cu = 8 * per;
-  // Split-K launch for the partial last round.  With one tile per CU a GEMM of R * 256 + t tiles takes R + 1 rounds however small t
-  // is (Wan 1.3B at 480p: 43 x 6 = 258 tiles for o / ffn2 at s1, 78 at s0; 14B / 720p s0: 580).  When every XCD's leftover (its
-  // list length mod 32, same arithmetic as the kernel) fits one round in s >= 2 parts, the main launch stops at the full rounds and
-  // the leftover tiles run as s blocks each over 1/s of K.  s <= 4: the last part to arrive reads all s partials (256 KiB each)
-  // alone.  Only for K >= 4096: the few blocks of the tail launch stream their operands alone (no neighbours sharing the L2 lines)
-  // at about half the usual rate and the partials' round trip is ~15 us, so short-K GEMMs lose (K = 1536: -9...-23 %; K = 5120:
-  // +1...+10 %; K = 8960 / 13824: +14...+58 %, profiles/r03S_gemm_splitk_micro.log).
-  g2.splitk_s = 1; g2.splitk_tb = 0; g2.splitk_per = per;
-  if (g2.tile_counter && g.splitk_ws && g.splitk_cnt && !rc.gemm_no_splitk && EPI != EPI_F32_SCALE && g.K / BK4 >= 64) {
-    const int tiles_n_ = (g.N + BN3 - 1) / BN3, per_group = g2.group * tiles_n_;
-    const int dealt = g2.sync_sweeps ? ((tiles_m_ / g2.group) >> 3) * per_group : 0, left = tiles - 8 * dealt;
+  p.cus_per_xcd = per;
+  p.splitk_s = 1;
+  if (g.tile_counter && !rc.gemm_no_splitk && g.epi != EPI_F32_SCALE) {
+    // every XCD's leftover = its list length mod the CUs of an XCD, same arithmetic as the kernels
+    const int per_group = p.group * tiles_n;
+    const int dealt = GEMM_SYNC_SWEEPS ? ((tiles_m / p.group) >> 3) * per_group : 0, left = tiles - 8 * dealt;
     int tb = 0, main_tiles = 0;
     for (int x = 0; x < 8; ++x) {
       const int chunk = dealt + (left >> 3) + (x < (left & 7) ? 1 : 0);
       tb = chunk % per > tb ? chunk % per : tb;
       main_tiles += chunk - chunk % per;
     }
-    int sp = tb > 0 ? per / tb : 1;
-    sp = sp > 4 ? 4 : sp;
-    if (sp >= 2 && (size_t)8 * tb * sp * (BM3 * BN3 * sizeof(float)) <= mmpl_gemm_splitk_ws_bytes()) {
-      g2.splitk_s = sp; g2.splitk_tb = tb;
-      if (main_tiles > 0) {
-        if (use_v8) hipLaunchKernelGGL(gemm_bf16_v8_kernel<EPI>, dim3(main_tiles < n_cu ? main_tiles : n_cu), dim3(256), 2 * STAGE4 + 2048, s, g2);
-        else hipLaunchKernelGGL(gemm_bf16_v6_kernel<EPI>, dim3(main_tiles < n_cu ? main_tiles : n_cu), dim3(512), smem, s, g2);
+    if (g.K / BK4 >= 64) {
+      // Split-K launch for the partial last round.  With one tile per CU a GEMM of R * 256 + t tiles takes R + 1 rounds however small t
+      // is (Wan 1.3B at 480p: 43 x 6 = 258 tiles for o / ffn2 at s1, 78 at s0; 14B / 720p s0: 580).  When every XCD's leftover fits one
+      // round in s >= 2 parts, the main launch stops at the full rounds and the leftover tiles run as s blocks each over 1/s of K.
+      // s <= 4: the last part to arrive reads all s partials (256 KiB each) alone.  Only for K >= 4096: the few blocks of the tail
+      // launch stream their operands alone (no neighbours sharing the L2 lines) at about half the usual rate and the partials' round
+      // trip is ~15 us, so short-K GEMMs lose (K = 1536: -9...-23 %; K = 5120: +1...+10 %; K = 8960 / 13824: +14...+58 %,
+      // profiles/r03S_gemm_splitk_micro.log).  Needs the tile tickets and the scratch.
+      int sp = tb > 0 ? per / tb : 1;
+      sp = sp > 4 ? 4 : sp;
+      if (g.splitk_ws && g.splitk_cnt && sp >= 2 && (size_t)8 * tb * sp * (BM3 * BN3 * sizeof(float)) <= mmpl_gemm_splitk_ws_bytes()) {
+        p.tail = GEMM_TAIL_SPLITK; p.splitk_s = sp; p.tail_blocks = 8 * tb * sp;
       }
-      hipLaunchKernelGGL((gemm_bf16_v6_kernel<EPI, true>), dim3(8 * tb * sp), dim3(512), smem, s, g2);
-      return hipGetLastError();
+    } else if (!rc.gemm_no_subtile && tb > 0 && 2 * tb <= per) {
+      // Sub-tile launch for the partial last round of short-K GEMMs (gemm_tail128_kernel): when every XCD's leftover is at most half a
+      // round of tiles, the main launch stops at the full rounds and the leftovers run as 128 x 128 quadrants (the DMA-ring body when
+      // they fit one round at one block per CU, else the register-staged body at two) instead of a whole round of one 256 x 256 tile
+      // per CU.  Needs the tile tickets (like the split-K launch), no scratch; MMPL_GEMM_NO_SUBTILE (or MMPL_GEMM_NO_SPLITK) switches
+      // it off.
+      p.tail = 4 * tb <= per ? GEMM_TAIL_128_8 : GEMM_TAIL_128_4; p.tail_blocks = 8 * tb * 4;
+    }
+    if (p.tail != GEMM_TAIL_NONE) {
+      // (tickets: the XCDs' full-round counts can differ by a whole round, which only the ticket loop absorbs)
+      p.tail_tiles = tb; p.tickets = 1;
+      p.main_blocks = main_tiles < n_cu ? main_tiles : n_cu;
+      return p;
     }
   }
-  // Sub-tile launch for the partial last round of short-K GEMMs (gemm_tail128_kernel): when every XCD's leftover is at most half a
-  // round of tiles, the main launch stops at the full rounds and the leftovers run as 128 x 128 quadrants (a 4-stage DMA-ring body, one
-  // short round) instead of a whole round of one 256 x 256 tile per CU.  Needs the tile tickets (like the split-K launch), no scratch;
-  // MMPL_GEMM_NO_SUBTILE (or MMPL_GEMM_NO_SPLITK) switches it off.
-  if (g2.tile_counter && !rc.gemm_no_splitk && !rc.gemm_no_subtile && EPI != EPI_F32_SCALE && g.K / BK4 < 64) {
-    const int tiles_n_ = (g.N + BN3 - 1) / BN3, per_group = g2.group * tiles_n_;
-    const int dealt = g2.sync_sweeps ? ((tiles_m_ / g2.group) >> 3) * per_group : 0, left = tiles - 8 * dealt;
-    int tb = 0, main_tiles = 0;
-    for (int x = 0; x < 8; ++x) {
-      const int chunk = dealt + (left >> 3) + (x < (left & 7) ? 1 : 0);
-      tb = chunk % per > tb ? chunk % per : tb;
-      main_tiles += chunk - chunk % per;
-    }
-    if (tb > 0 && 2 * tb <= per) {
-      g2.splitk_s = 4; g2.splitk_tb = tb;                       // (the main kernel only looks at splitk_s > 1: stop at the full rounds)
-      // (tickets, like the split-K launch: the XCDs' full-round counts can differ by a whole round, which only the ticket loop absorbs)
-      if (main_tiles > 0) {
-        if (use_v8) hipLaunchKernelGGL(gemm_bf16_v8_kernel<EPI>, dim3(main_tiles < n_cu ? main_tiles : n_cu), dim3(256), 2 * STAGE4 + 2048, s, g2);
-        else hipLaunchKernelGGL(gemm_bf16_v6_kernel<EPI>, dim3(main_tiles < n_cu ? main_tiles : n_cu), dim3(512), smem, s, g2);
-      }
-      if (4 * tb <= per) hipLaunchKernelGGL((gemm_tail128_kernel<EPI, true>), dim3(8 * tb * 4), dim3(256), 8 * TILE_BYTES, s, g2);
-      else hipLaunchKernelGGL((gemm_tail128_kernel<EPI, false>), dim3(8 * tb * 4), dim3(256), 4 * TILE_BYTES, s, g2);
-      return hipGetLastError();
-    }
-  }
-  const int blocks = g2.tile_counter && tiles > n_cu ? n_cu : tiles;
-  if (blocks == tiles) g2.tile_counter = nullptr;             // one round or less: nothing to balance
-  if (use_v8) hipLaunchKernelGGL(gemm_bf16_v8_kernel<EPI>, dim3(blocks), dim3(256), 2 * STAGE4 + 2048, s, g2);
-  else hipLaunchKernelGGL(gemm_bf16_v6_kernel<EPI>, dim3(blocks), dim3(512), smem, s, g2);
-  return hipGetLastError();
+  p.main_blocks = g.tile_counter && tiles > n_cu ? n_cu : tiles;
+  p.tickets = p.main_blocks != tiles;
+  return p;
 }
 
-template <int EPI>
-hipError_t launch_v2(const GemmArgs& g, hipStream_t s) {
-  constexpr int smem = NSTAGE2 * STAGE2;
-  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v2_kernel<EPI>), smem); e != hipSuccess) return e;
-  const int tiles = ((g.M + BM2 - 1) / BM2) * ((g.N + BN2 - 1) / BN2);
-  hipLaunchKernelGGL(gemm_bf16_v2_kernel<EPI>, dim3(tiles), dim3(512), smem, s, g);
-  return hipGetLastError();
-}
+}  // namespace
 
-template <int EPI>
-hipError_t launch(const GemmArgs& g, hipStream_t s) {
+GemmPlan mmpl_gemm_plan(const GemmArgs& g) {
   // kernel-selection overrides for A/B runs (mmpl_config.h).  (gemm_w64.hip -- one wave per SIMD, 32x32x16 MFMAs, 85 % matrix-pipe
   // issue rate inside its k loop yet 3-6 % slower end to end than v6 on this power-limited chip -- was removed in round 3;
   // DESIGN.md section 3.2 keeps what it taught.)
   const bool env_v1 = mmpl_config().gemm_v1, env_v2 = mmpl_config().gemm_v2;
   const bool big = g.batch <= 1 && g.M >= 1024 && g.N >= 256 && g.K >= 128 && !env_v1 && !env_v2;
   // v6 addresses its operands with 32-bit byte offsets from the base pointers; anything larger goes to v2 (64-bit pointers)
-  if (big && (long long)g.M * g.lda < (1ll << 31) && (long long)g.N * g.ldw < (1ll << 31)) return launch_v6<EPI>(g, s);
-  if (g.batch <= 1 && g.M >= 1024 && g.N >= 128 && g.K >= 128 && !env_v1) return launch_v2<EPI>(g, s);
-  constexpr int smem = 4 * TILE_BYTES;
-  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_kernel<EPI>), smem); e != hipSuccess) return e;
-  const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-  hipLaunchKernelGGL(gemm_bf16_kernel<EPI>, dim3(tiles, g.batch > 1 ? g.batch : 1), dim3(256), smem, s, g);
-  return hipGetLastError();
+  if (big && (long long)g.M * g.lda < (1ll << 31) && (long long)g.N * g.ldw < (1ll << 31)) return plan_v6(g);
+  GemmPlan p = {};
+  p.splitk_s = 1;
+  if (g.batch <= 1 && g.M >= 1024 && g.N >= 128 && g.K >= 128 && !env_v1) {
+    p.kernel = GEMM_KERNEL_V2;
+    p.main_blocks = ((g.M + BM2 - 1) / BM2) * ((g.N + BN2 - 1) / BN2);
+    return p;
+  }
+  p.kernel = GEMM_KERNEL_SMALL;
+  p.main_blocks = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) * (g.batch > 1 ? g.batch : 1);
+  return p;
 }
-
-}  // namespace
 
 size_t mmpl_gemm_splitk_ws_bytes() { return (size_t)256 * BM3 * BN3 * sizeof(float); }   // <= one part per CU
 

@@ -1,11 +1,13 @@
-// Kernel-level entry points of the VAE / TAEHV launchers (include/mmpl_hip.h, "kernel-level entry points for tests and tools"):
-// one launch of vae_kernels.hip / taehv_kernels.hip on plain arguments, the way mmpl_gemm / mmpl_layernorm expose the DiT kernels.
+// Kernel-level entry points of the VAE / TAEHV launchers and of the GEMM in all its forms (include/mmpl_hip.h, "kernel-level entry
+// points for tests and tools"): one launch of vae_kernels.hip / taehv_kernels.hip / gemm.hip on plain arguments, the way mmpl_gemm /
+// mmpl_layernorm expose the DiT kernels.
 // They fill the launchers' argument structs and do no arithmetic of their own.  Every check below runs before the first HIP call:
 // a rejected call launches nothing.  The checks bound what a kernel can reach by the sizes the caller states (the header says,
 // per entry, how large each buffer must be for them); alignment is checked because the kernels move 8 or 16 bytes per access.
 #include <stdint.h>
 
 #include "../../include/mmpl_hip.h"
+#include "kernels.h"
 #include "taehv_kernels.h"
 #include "vae_kernels.h"
 
@@ -155,6 +157,94 @@ int mmpl_vae_mu_out(const void* enc, const void* w1, const void* b1, const float
   for (int i = 0; i < 16; ++i) { a.mean[i] = mean[i]; a.inv_std[i] = inv_std[i]; }
   a.F = F; a.f_out = f_out; a.h = h; a.w = w;
   LAUNCH(vae_launch_mu_out(a, (hipStream_t)stream), me);
+}
+
+// One launch of mmpl_launch_gemm in any of the forms the forwards use (include/mmpl_hip.h).  The plan is the launcher's own
+// (mmpl_gemm_plan, which mmpl_launch_gemm consults for every choice); it is computed after the checks, because the 256 x 256
+// kernels' plan asks the device for its CU count.
+int mmpl_gemm_ex(const void* A, int lda, const void* W, int ldw, const void* bias, void* C, int ldc, int M, int N, int K, int epi,
+                 const void* res, int ldres, const void* gate, int gate_frame_stride, int rows_per_frame, float alpha, int batch,
+                 long long sA, long long sW, long long sC, void* const* v_dst, int n_v_dst, int v_col0, int v_ld, void* scratch,
+                 size_t scratch_bytes, void* tile_counter, int* plan_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_gemm_ex";
+  if (plan_out)
+    for (int i = 0; i < 6; ++i) plan_out[i] = 0;
+  REJECT(epi < EPI_BIAS || epi > EPI_BIAS_VPAGES, me, "unknown epilogue");
+  REJECT(!A || !W || !C, me, "null argument");
+  REJECT((epi == EPI_GATE_RES && (!res || !gate)) || (epi == EPI_RES && !res) || (epi == EPI_BIAS_VPAGES && !v_dst), me, "missing epilogue operand");
+  REJECT(M < 1 || N < 1 || K < 1, me, "non-positive size");
+  REJECT(K % 64, me, "K % 64");
+  REJECT(N % 4, me, "N % 4");
+  REJECT(lda % 8, me, "lda % 8");
+  REJECT(lda < K, me, "lda < K");
+  REJECT(ldw % 8, me, "ldw % 8");
+  REJECT(ldw < K, me, "ldw < K");
+  REJECT(batch < 1, me, "batch < 1");
+  REJECT(batch > 65535, me, "batch > 65535");
+  REJECT(ldc % 4, me, "ldc % 4");
+  REJECT(batch == 1 && ldc < N, me, "ldc < N");
+  REJECT(epi == EPI_F32_SCALE && bias, me, "the fp32 epilogue takes no bias");
+  const bool has_res = epi == EPI_GATE_RES || epi == EPI_RES;
+  REJECT(has_res && ldres < N, me, "ldres < N");
+  REJECT(has_res && ldres % 4, me, "ldres % 4");
+  REJECT((epi == EPI_GATE_RES || epi == EPI_BIAS_VPAGES) && rows_per_frame < 1, me, "rows_per_frame < 1");
+  if (epi == EPI_GATE_RES) {
+    REJECT(gate_frame_stride < 0, me, "gate_frame_stride < 0");
+    REJECT(gate_frame_stride % 4, me, "gate_frame_stride % 4");
+    // (0: one gate row for every frame; otherwise the frames' rows must not overlap)
+    REJECT(M > rows_per_frame && gate_frame_stride != 0 && gate_frame_stride < N, me, "gate_frame_stride < N with more than one frame");
+  }
+  REJECT(misaligned(A, 16), me, "A not 16-byte aligned");
+  REJECT(misaligned(W, 16), me, "W not 16-byte aligned");
+  REJECT(misaligned(C, epi == EPI_F32_SCALE ? 16 : 8), me, epi == EPI_F32_SCALE ? "fp32 C not 16-byte aligned" : "C not 8-byte aligned");
+  REJECT(misaligned(bias, 8), me, "bias not 8-byte aligned");
+  REJECT(has_res && misaligned(res, 8), me, "res not 8-byte aligned");
+  REJECT(epi == EPI_GATE_RES && misaligned(gate, 8), me, "gate not 8-byte aligned");
+  GemmArgs g = {};
+  g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.bias = (const bf16_t*)bias; g.C = (bf16_t*)C; g.ldc = ldc;
+  g.M = M; g.N = N; g.K = K; g.epi = epi; g.res = (const bf16_t*)res; g.ldres = ldres; g.gate = (const bf16_t*)gate;
+  g.gate_frame_stride = gate_frame_stride; g.rows_per_frame = rows_per_frame > 0 ? rows_per_frame : 1; g.alpha = alpha;
+  g.batch = batch; g.sA = (long)sA; g.sW = (long)sW; g.sC = (long)sC;
+  if (batch > 1) {
+    REJECT(has_res || epi == EPI_BIAS_VPAGES, me, "the batched form has no residual and no pages");
+    REJECT(sA < 0 || sW < 0 || sC < 0, me, "negative batch stride");
+    REJECT(sA % 8, me, "sA % 8");
+    REJECT(sW % 8, me, "sW % 8");
+    REJECT(sC % 4, me, "sC % 4");
+  }
+  if (epi == EPI_BIAS_VPAGES) {
+    REJECT(n_v_dst < 1, me, "n_v_dst < 1");
+    REJECT(n_v_dst > 8, me, "more than 8 pages");
+    REJECT((long)n_v_dst * rows_per_frame < M, me, "the pages hold fewer than M rows");
+    REJECT(v_col0 % 4, me, "v_col0 % 4");
+    REJECT(v_col0 <= 0 || v_col0 >= N, me, "v_col0 outside (0, N)");
+    REJECT(v_ld < N - v_col0, me, "v_ld < N - v_col0");
+    REJECT(v_ld % 4, me, "v_ld % 4");
+    for (int i = 0; i < n_v_dst; ++i) {
+      REJECT(!v_dst[i], me, "null page");
+      REJECT(misaligned(v_dst[i], 8), me, "page not 8-byte aligned");
+      g.v_dst[i] = (bf16_t*)v_dst[i];
+    }
+    g.v_col0 = v_col0; g.v_ld = v_ld;
+  }
+  if (scratch) {
+    REJECT(scratch_bytes < mmpl_gemm_scratch_bytes(), me, "scratch smaller than mmpl_gemm_scratch_bytes()");
+    REJECT(misaligned(scratch, 256), me, "scratch must be 256-byte aligned");
+    g.tile_counter = (int*)scratch;                        // the layout mmpl_gemm_scratch documents
+    g.splitk_cnt = g.tile_counter + 64;
+    g.splitk_ws = (float*)((char*)scratch + 2048);
+  } else {
+    REJECT(misaligned(tile_counter, 4), me, "tile_counter not 4-byte aligned");
+    g.tile_counter = (int*)tile_counter;
+  }
+  // (today the launcher sends every batched GEMM to the small kernel, the only one that reads the batch strides: this guards that)
+  const GemmPlan p = mmpl_gemm_plan(g);
+  REJECT(batch > 1 && p.kernel != GEMM_KERNEL_SMALL, me, "batched GEMMs run on the small kernel only");
+  if (plan_out) {
+    plan_out[0] = p.kernel; plan_out[1] = p.tail; plan_out[2] = p.staged_epilogue; plan_out[3] = p.main_blocks;
+    plan_out[4] = p.tail_blocks; plan_out[5] = p.splitk_s;
+  }
+  LAUNCH(mmpl_launch_gemm(g, (hipStream_t)stream), me);
 }
 
 int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long fs1, int C0, int C1, int up, int ntaps,

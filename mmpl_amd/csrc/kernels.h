@@ -41,6 +41,27 @@ struct GemmArgs {
   int splitk_s, splitk_tb, splitk_per;   // set by the launcher: parts per tile (1 = no split), tail tiles per XCD (max), CUs per XCD
 };
 size_t mmpl_gemm_splitk_ws_bytes();
+// What mmpl_launch_gemm does with a GemmArgs: every choice of the launchers is made by mmpl_gemm_plan and nowhere else (the launchers
+// read it from the plan; mmpl_gemm_ex reports it to the tests).  Pure host arithmetic except for the CU count of the current device,
+// which is looked up only when the 256 x 256 kernels are chosen.
+enum GemmKernel { GEMM_KERNEL_SMALL = 1, GEMM_KERNEL_V2 = 2, GEMM_KERNEL_V6 = 3, GEMM_KERNEL_V8 = 4 };
+enum GemmTail { GEMM_TAIL_NONE = 0, GEMM_TAIL_SPLITK = 1,
+                GEMM_TAIL_128_8 = 2,    // gemm_tail128_kernel<EPI, true>: the DMA-ring body, 8 tile buffers of LDS, one block per CU
+                GEMM_TAIL_128_4 = 3 };  // gemm_tail128_kernel<EPI, false>: the register-staged body, 4 tile buffers, two blocks per CU
+struct GemmPlan {
+  int kernel;             // GemmKernel of the main launch (also when the main launch is skipped: the kernel whose tile order the tail follows)
+  int tail;               // GemmTail: the second launch for the partial last round of tiles
+  int staged_epilogue;    // v6 / v8 (and the split-K tail): LDS-staged 16-byte epilogue; 0 = the direct 8-byte one
+  int main_blocks;        // blocks of the main launch (small kernel: tiles x batch); 0 = the main launch is skipped
+  int tail_blocks;        // blocks of the tail launch (0 without a tail)
+  int splitk_s;           // parts per tail tile of the split-K launch (1 = no split; GemmArgs.splitk_s is 4 for a 128 x 128 tail as well)
+  // the rest is what the launchers need beside the above
+  int tickets;            // the main launch draws its tiles from GemmArgs.tile_counter (persistent blocks)
+  int group;              // GemmArgs.group
+  int tail_tiles;         // GemmArgs.splitk_tb: tail tiles per XCD (max)
+  int cus_per_xcd;        // GemmArgs.splitk_per
+};
+GemmPlan mmpl_gemm_plan(const GemmArgs& g);
 bool mmpl_xcd_dispatch_ok(bool may_probe);   // device_state.hip: workgroup b runs on XCD b & 7 (probed once per device, never inside a capture)
 hipError_t mmpl_launch_gemm(const GemmArgs& g, hipStream_t s);
 

@@ -1,4 +1,4 @@
-"""Argument checks of the kernel-level VAE / TAEHV entry points (include/mmpl_hip.h): every rejection happens before the first HIP
+"""Argument checks of the kernel-level VAE / TAEHV / GEMM entry points (include/mmpl_hip.h): every rejection happens before the first HIP
 call, so this file needs no GPU and no real buffer -- the pointers below are made-up, aligned addresses that nothing dereferences.
 Each call is wrong in exactly one way and is matched against the message of the check that must catch it."""
 import ctypes as C
@@ -124,3 +124,69 @@ TAEHV_REJECTS = [
 def test_taehv_conv_rejects(kw, msg):
     text = _taehv(**kw)
     assert text.startswith("mmpl_taehv_conv:") and msg in text, text
+
+
+def _gemm(**kw):
+    """mmpl_gemm_ex on a valid 1100 x 520 x 192 call (epi 0, no scratch), with overrides; epi 3 / 4 / 6 get their operands unless overridden."""
+    a = dict(A=P, lda=192, W=P, ldw=192, bias=P, C=P, ldc=520, M=1100, N=520, K=192, epi=0, res=None, ldres=0, gate=None,
+             gate_frame_stride=0, rows_per_frame=0, alpha=1.0, batch=1, sA=0, sW=0, sC=0, v_dst=None, n_v_dst=0, v_col0=0, v_ld=0,
+             scratch=None, scratch_bytes=0, tile_counter=None)
+    epi = kw.get("epi", 0)
+    if epi in (3, 4):
+        a.update(res=P, ldres=520)
+    if epi == 3:
+        a.update(gate=P, gate_frame_stride=520, rows_per_frame=200)
+    if epi == 6:
+        a.update(v_dst=_frames(6), n_v_dst=6, v_col0=256, v_ld=264, rows_per_frame=200)
+    a.update(kw)
+    plan = (C.c_int * 6)(*([-1] * 6))
+    rc = _lib.load().mmpl_gemm_ex(*a.values(), plan, None)
+    return _err(rc), list(plan)
+
+
+BIG = 1 << 40
+GEMM_REJECTS = [
+    (dict(epi=7), "unknown epilogue"), (dict(epi=-1), "unknown epilogue"),
+    (dict(A=None), "null argument"), (dict(W=None), "null argument"), (dict(C=None), "null argument"),
+    (dict(epi=3, res=None), "missing epilogue operand"), (dict(epi=3, gate=None), "missing epilogue operand"),
+    (dict(epi=4, res=None), "missing epilogue operand"), (dict(epi=6, v_dst=None), "missing epilogue operand"),
+    (dict(M=0), "non-positive size"), (dict(N=0), "non-positive size"), (dict(K=0), "non-positive size"),
+    (dict(K=96), "K % 64"), (dict(N=518), "N % 4"),
+    (dict(lda=196), "lda % 8"), (dict(lda=184), "lda < K"), (dict(ldw=196), "ldw % 8"), (dict(ldw=128), "ldw < K"),
+    (dict(batch=0), "batch < 1"), (dict(batch=65536), "batch > 65535"),
+    (dict(ldc=522), "ldc % 4"), (dict(ldc=516), "ldc < N"),
+    (dict(epi=5), "takes no bias"),
+    (dict(epi=4, ldres=516), "ldres < N"), (dict(epi=4, ldres=522), "ldres % 4"),
+    (dict(epi=3, rows_per_frame=0), "rows_per_frame < 1"), (dict(epi=6, rows_per_frame=0), "rows_per_frame < 1"),
+    (dict(epi=3, gate_frame_stride=-520), "gate_frame_stride < 0"), (dict(epi=3, gate_frame_stride=522), "gate_frame_stride % 4"),
+    (dict(epi=3, gate_frame_stride=516), "gate_frame_stride < N with more than one frame"),
+    (dict(A=P + 8), "A not 16-byte"), (dict(W=P + 8), "W not 16-byte"), (dict(C=P + 4), "C not 8-byte"),
+    (dict(epi=5, bias=None, C=P + 8), "fp32 C not 16-byte"),
+    (dict(bias=P + 4), "bias not 8-byte"), (dict(epi=4, res=P + 4), "res not 8-byte"), (dict(epi=3, gate=P + 4), "gate not 8-byte"),
+    (dict(epi=4, batch=2), "no residual and no pages"), (dict(epi=6, batch=2), "no residual and no pages"),
+    (dict(batch=2, sA=-8), "negative batch stride"), (dict(batch=2, sW=-8), "negative batch stride"), (dict(batch=2, sC=-4), "negative batch stride"),
+    (dict(batch=2, sA=4), "sA % 8"), (dict(batch=2, sW=4), "sW % 8"), (dict(batch=2, sC=6), "sC % 4"),
+    (dict(epi=6, n_v_dst=0), "n_v_dst < 1"), (dict(epi=6, v_dst=_frames(9), n_v_dst=9), "more than 8 pages"),
+    (dict(epi=6, v_dst=_frames(5), n_v_dst=5), "fewer than M rows"),
+    (dict(epi=6, v_col0=258), "v_col0 % 4"), (dict(epi=6, v_col0=0), "v_col0 outside"), (dict(epi=6, v_col0=520), "v_col0 outside"),
+    (dict(epi=6, v_ld=260), "v_ld < N - v_col0"), (dict(epi=6, v_ld=266), "v_ld % 4"),
+    (dict(epi=6, v_dst=_frames(6, bad=3)), "null page"),
+    (dict(epi=6, v_dst=(VP * 6)(*[P + 0x10000 * i + (4 if i == 2 else 0) for i in range(6)])), "page not 8-byte"),
+    (dict(scratch=P, scratch_bytes=4096), "scratch smaller"), (dict(scratch=P + 128, scratch_bytes=BIG), "256-byte aligned"),
+    (dict(tile_counter=P + 2), "tile_counter not 4-byte"),
+]
+
+
+@pytest.mark.parametrize("kw,msg", GEMM_REJECTS, ids=[f"{i}-{m[:18]}" for i, (_, m) in enumerate(GEMM_REJECTS)])
+def test_gemm_ex_rejects(kw, msg):
+    text, plan = _gemm(**kw)
+    assert text.startswith("mmpl_gemm_ex:") and msg in text, text
+    assert plan == [0] * 6                                         # no plan was made, nothing was launched
+
+
+def test_gemm_entries_keep_their_checks():
+    """mmpl_gemm / _tickets / _scratch still reject the page epilogue (6) and report as before."""
+    lib = _lib.load()
+    assert "mmpl_gemm: unknown epilogue" in _err(lib.mmpl_gemm(P, 192, P, 192, P, P, 520, 1100, 520, 192, 6, None, 0, None, 0, 0, None))
+    assert "mmpl_gemm: missing epilogue operand" in _err(lib.mmpl_gemm_tickets(P, 192, P, 192, P, P, 520, 1100, 520, 192, 4, None, 0, None, 0, 0, None, None))
+    assert "mmpl_gemm_scratch: scratch missing" in _err(lib.mmpl_gemm_scratch(P, 192, P, 192, P, P, 520, 1100, 520, 192, 0, None, 0, None, 0, 0, None, 0, None))
