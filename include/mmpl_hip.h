@@ -474,6 +474,31 @@ int mmpl_gemm_ex(const void* A, int lda, const void* W, int ldw, const void* bia
                  long long sA, long long sW, long long sC, void* const* v_dst, int n_v_dst, int v_col0, int v_ld, void* scratch,
                  size_t scratch_bytes, void* tile_counter, int* plan_out, mmpl_stream_t stream);
 
+/* The attention kernels (attention.hip, attn_w64.hip) on every path mmpl_dit_forward can take through them, for
+ * tests/test_attn_exact_gpu.py: the arguments of mmpl_attn_fwd_variant plus what only the internal callers could set.
+ * mmpl_attn_fwd / _ws / _variant / _history are unchanged.
+ *   q, o, pages  as mmpl_attn_fwd; additionally every ld >= 128 * num_heads, so the stated sizes bound what a launch reaches:
+ *           q [Lq, ldq], o [Lq, ldo] (rows < Lq, columns < 128 * num_heads are written and nothing else), page p [page_rows, ldk / ldv].
+ *   page_group   NULL (one group) or a host array of n_pages bytes: the allocation page p lies in.  The 64-rows-per-wave kernel
+ *           orders the pages by (group, address) and merges back-to-back pages of one group into one longer page.
+ *   variant 0 / 1 / 3 / 4 as mmpl_attn_fwd_variant; q_prescaled != 0 with variant 0 or 3 = the caller multiplied q by
+ *           softmax_scale * log2(e) before rounding it (variant 4 is variant 3 with q_prescaled; variant 0 with q_prescaled is what
+ *           mmpl_dit_forward's self-attention passes).  A prescaled q that resolves to the lock-step kernel is an error.
+ *   cross   != 0: a text cross-attention launch.  With the lock-step kernel, ONE page and page_rows <= 128 this is attn_cross_kernel.
+ *   last_row_copies  0 / 1: plain.  > 1 (lock-step kernels, one page): the page's last row stands for that many identical keys.
+ *   workspace    NULL or scratch for the split-KV tail round (mmpl_attn_workspace_bytes() is always enough), 16-byte aligned.
+ *   history, stats_dev  as mmpl_attn_fwd_history (64-rows-per-wave kernel; ignored by the others).
+ *   plan_out NULL or 8 host ints, filled from the launcher's own plan before the launch (all 0 when the call is rejected):
+ *           [0] kernel: 1 attn_fwd_kernel, 2 attn_cross_kernel<1>, 3 attn_cross_kernel<2>, 4 attn_w64_kernel;
+ *           [1] pages the kernel walks (4: after the merge); [2] 64-row KV tiles per query block; [3] blocks of the main launch;
+ *           [4] kernel 4: query blocks per XCD that run split over the KV tiles in the tail round (0 = none); [5] their parts (1 = none);
+ *           [6] kernels 2, 3: 256-row query blocks per block; [7] blocks per head.
+ * Every check runs before the first HIP call and a rejected call launches nothing. */
+int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
+                     const unsigned char* page_group, int ldk, int ldv, int n_pages, int page_rows, int Lq, int num_heads,
+                     float softmax_scale, void* workspace, size_t workspace_bytes, int variant, int q_prescaled, int cross,
+                     int last_row_copies, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream);
+
 /* Optional per-kernel-class hipEvent timing (bench.py's live roofline numbers; off by default, not thread-safe).
  * kinds: 0 gemm, 1 self-attention, 2 cross-attention, 3 layernorm, 4 qk-norm/rope/kv-write, 5 elementwise, 6 cfg+unipc,
  * 7 vae.  on = 0 off, 1 every kind, > 1: only the kinds in the bit mask (on >> 1) (e.g. 2 << 1 | ... ; bench.py times the

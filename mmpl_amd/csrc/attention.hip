@@ -471,78 +471,112 @@ AttnArgs merge_contiguous_pages(const AttnArgs& a) {
 }
 }  // namespace
 
-hipError_t mmpl_launch_attention(const AttnArgs& a_in, hipStream_t s) {
-  if (a_in.Lq <= 0) return hipSuccess;
-  if (a_in.n_pages <= 0 || a_in.n_pages > MMPL_MAX_PAGES) return hipErrorInvalidValue;
-  const bool no_merge = mmpl_config().attn_no_merge;
-  const bool w64_bound = a_in.variant == ATTN_W64 || (a_in.variant == ATTN_AUTO && !a_in.cross && a_in.q_prescaled && mmpl_attention_self_variant() == ATTN_W64);
-  AttnArgs a = a_in;
-  for (int p = 0; p < a.n_pages; ++p) a.page_rows_each[p] = a.page_rows;
-  if (!no_merge && w64_bound && a.n_pages > 1) a = merge_contiguous_pages(a);
-  if (a.n_pages <= 0 || a.n_pages > MMPL_MAX_PAGES || a.page_rows <= 0 || (a.ldq % 8) || (a.ldk % 8) || (a.ldv % 8) ||
-      (a.ldo % 8) || ((uintptr_t)a.o & 15) || (a.variant != ATTN_AUTO && a.variant != ATTN_LOCKSTEP && a.variant != ATTN_W64))
-    return hipErrorInvalidValue;
+int mmpl_attn_resolve_variant(const AttnArgs& a) {
   // Kernel choice.  The DiT forward's self-attention (q prescaled by its producer) -> the 64-rows-per-wave kernel
   // (attn_w64.hip); the 8-tile text cross-attention -> the lock-step kernel (its prologue is the shortest); a raw-q launch
   // (the attention() seam) -> the lock-step kernel too (exact online softmax on the caller's q; attn_w64 would round q a second
   // time, kernels.h).  AttnArgs.variant (C ABI: mmpl_attn_fwd_variant) selects one explicitly.
-  const bool no_split = mmpl_config().attn_nosplit;
-  int variant = a.variant;
-  if (variant == ATTN_AUTO) {
-    variant = a.cross ? ATTN_LOCKSTEP : mmpl_attention_self_variant();
-    if (variant == ATTN_W64 && !a.q_prescaled) variant = ATTN_LOCKSTEP;
-  }
-  if (a.q_prescaled && variant != ATTN_W64) return hipErrorInvalidValue;
-  if (a.last_row_copies > 1 && (variant != ATTN_LOCKSTEP || a.n_pages != 1)) return hipErrorInvalidValue;
+  if (a.variant != ATTN_AUTO) return a.variant;
+  int variant = a.cross ? ATTN_LOCKSTEP : mmpl_attention_self_variant();
+  if (variant == ATTN_W64 && !a.q_prescaled) variant = ATTN_LOCKSTEP;
+  return variant;
+}
+
+AttnPlan mmpl_attn_plan(const AttnArgs& a_in) {
+  AttnPlan p = {};
+  if (a_in.Lq <= 0) return p;
+  const AttnPlan invalid = {1};
+  if (a_in.n_pages <= 0 || a_in.n_pages > MMPL_MAX_PAGES) return invalid;
+  const int variant = mmpl_attn_resolve_variant(a_in);
+  p.args = a_in;
+  AttnArgs& a = p.args;
+  for (int i = 0; i < a.n_pages; ++i) a.page_rows_each[i] = a.page_rows;
+  if (!mmpl_config().attn_no_merge && variant == ATTN_W64 && a.n_pages > 1) a = merge_contiguous_pages(a);
+  if (a.n_pages <= 0 || a.n_pages > MMPL_MAX_PAGES || a.page_rows <= 0 || (a.ldq % 8) || (a.ldk % 8) || (a.ldv % 8) ||
+      (a.ldo % 8) || ((uintptr_t)a.o & 15) || (variant != ATTN_LOCKSTEP && variant != ATTN_W64))
+    return invalid;
+  if (a.q_prescaled && variant != ATTN_W64) return invalid;
+  if (a.last_row_copies > 1 && (variant != ATTN_LOCKSTEP || a.n_pages != 1)) return invalid;
   const int n_qb = (a.Lq + QB - 1) / QB;
+  p.n_pages = a.n_pages;
+  p.sp = 1;
   if (variant == ATTN_LOCKSTEP && a.cross && a.n_pages == 1 && a.page_rows <= 2 * KVB) {
     // <= 2 KV tiles: the head's K / V stay in LDS over a run of query blocks; every CU gets one block (the registers allow no more),
     // the blocks of a head share its query blocks evenly
-    const int nt = (a.page_rows + KVB - 1) / KVB;
-    const void* f = nt == 1 ? reinterpret_cast<const void*>(attn_cross_kernel<1>) : reinterpret_cast<const void*>(attn_cross_kernel<2>);
-    if (hipError_t e = mmpl_dyn_smem_once(f, SMEM_X); e != hipSuccess) return e;
+    p.kv_tiles = (a.page_rows + KVB - 1) / KVB;
+    p.kernel = p.kv_tiles == 1 ? ATTN_KERNEL_CROSS1 : ATTN_KERNEL_CROSS2;
     const int cus = 8 * mmpl_cus_per_xcd();
     int bph = cus / a.H < 1 ? 1 : cus / a.H;                    // blocks per head (40 heads, 256 CUs: 6)
     if (bph > n_qb) bph = n_qb;
-    const int qpb = (n_qb + bph - 1) / bph;
-    bph = (n_qb + qpb - 1) / qpb;
-    if (nt == 1) hipLaunchKernelGGL(attn_cross_kernel<1>, dim3(bph * a.H), dim3(512), SMEM_X, s, a, qpb, bph);
-    else hipLaunchKernelGGL(attn_cross_kernel<2>, dim3(bph * a.H), dim3(512), SMEM_X, s, a, qpb, bph);
-    return hipGetLastError();
+    p.qb_per_block = (n_qb + bph - 1) / bph;
+    p.blocks_per_head = (n_qb + p.qb_per_block - 1) / p.qb_per_block;
+    p.main_blocks = p.blocks_per_head * a.H;
+    return p;
   }
   if (variant == ATTN_LOCKSTEP) {
-    const void* f = a.cross ? reinterpret_cast<const void*>(attn_fwd_kernel<1>) : reinterpret_cast<const void*>(attn_fwd_kernel<0>);
-    if (hipError_t e = mmpl_dyn_smem_once(f, SMEM); e != hipSuccess) return e;
-    if (a.cross) hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3(n_qb * a.H), dim3(512), SMEM, s, a);
-    else hipLaunchKernelGGL(attn_fwd_kernel<0>, dim3(n_qb * a.H), dim3(512), SMEM, s, a);
-    return hipGetLastError();
+    p.kernel = ATTN_KERNEL_LOCKSTEP;
+    p.kv_tiles = a.n_pages * ((a.page_rows + KVB - 1) / KVB);
+    p.main_blocks = n_qb * a.H;
+    return p;
   }
+  p.kernel = ATTN_KERNEL_W64;
   if (a.history) a.history_mem = reinterpret_cast<short*>(a.history + mmpl_attention_history_state_bytes(a.Lq, a.H));
-  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_symbol(0), mmpl_attention_w64_smem()); e != hipSuccess) return e;
-  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_symbol(1), mmpl_attention_w64_smem()); e != hipSuccess) return e;
-  auto run = [&](int blocks, int local_base, int sp, bool split) { mmpl_launch_attention_w64(a, blocks, local_base, sp, split, s); };
   // Tail round: with one block per CU and b = n_qb*H/8 query blocks per XCD (32 CUs), the last b mod 32 blocks of every
   // XCD would run alone for a whole block time.  They are launched instead as `sp` blocks each over 1/sp of the KV tiles
   // (fp32 partials in split_ws) followed by a small merge kernel, so the tail round lasts ~1/sp block times.
   const int per_xcd = mmpl_cus_per_xcd();
   int tiles = 0;
-  for (int p = 0; p < a.n_pages; ++p) tiles += (a.page_rows_each[p] + KVB - 1) / KVB;
+  for (int i = 0; i < a.n_pages; ++i) tiles += (a.page_rows_each[i] + KVB - 1) / KVB;
+  p.kv_tiles = tiles;
   // b = work items per XCD (kernels.h: mmpl_attn_item), tb = those of the partial last round.  Only a tail that fits ONE round of
   // parts is split (tb * sp <= CUs per XCD): tails of 3 shorter rounds (tb = 17 -> 3 parts, 23-24 -> 4) and launches with fewer
   // items than CUs measured 0.6-8 % SLOWER than leaving them alone (profiles/r03Q_*).
   const int total = n_qb * a.H;
   const int b = (a.H & 7) == 0 ? total / 8 : (total + 7) / 8, tb = b % per_xcd;
   int sp = 1;
-  if (!no_split && a.split_ws && b > per_xcd && tb > 0 && per_xcd / tb >= 2) {
+  if (!mmpl_config().attn_nosplit && a.split_ws && b > per_xcd && tb > 0 && per_xcd / tb >= 2) {
     sp = per_xcd / tb > 4 ? 4 : per_xcd / tb;
     if (tiles / sp < 8 || (size_t)8 * tb * sp * QB * 130 * sizeof(float) > a.split_ws_bytes) sp = 1;
   }
-  if (sp == 1) {
-    run(8 * b, 0, 1, false);
-  } else {
-    run(8 * (b - tb), 0, 1, false);
-    run(8 * tb * sp, b - tb, sp, true);
-    hipLaunchKernelGGL(attn_merge_kernel, dim3(8 * tb), dim3(256), 0, s, a, b - tb, sp, tb);
+  p.sp = sp;
+  p.tail_items = sp == 1 ? 0 : tb;
+  p.main_blocks = 8 * (b - p.tail_items);
+  return p;
+}
+
+hipError_t mmpl_launch_attention(const AttnArgs& a_in, hipStream_t s) {
+  const AttnPlan p = mmpl_attn_plan(a_in);
+  if (p.invalid) return hipErrorInvalidValue;
+  const AttnArgs& a = p.args;
+  switch (p.kernel) {
+    case ATTN_KERNEL_NONE:
+      return hipSuccess;
+    case ATTN_KERNEL_CROSS1:
+    case ATTN_KERNEL_CROSS2: {
+      const bool one = p.kernel == ATTN_KERNEL_CROSS1;
+      const void* f = one ? reinterpret_cast<const void*>(attn_cross_kernel<1>) : reinterpret_cast<const void*>(attn_cross_kernel<2>);
+      if (hipError_t e = mmpl_dyn_smem_once(f, SMEM_X); e != hipSuccess) return e;
+      if (one) hipLaunchKernelGGL(attn_cross_kernel<1>, dim3(p.main_blocks), dim3(512), SMEM_X, s, a, p.qb_per_block, p.blocks_per_head);
+      else hipLaunchKernelGGL(attn_cross_kernel<2>, dim3(p.main_blocks), dim3(512), SMEM_X, s, a, p.qb_per_block, p.blocks_per_head);
+      return hipGetLastError();
+    }
+    case ATTN_KERNEL_LOCKSTEP: {
+      const void* f = a.cross ? reinterpret_cast<const void*>(attn_fwd_kernel<1>) : reinterpret_cast<const void*>(attn_fwd_kernel<0>);
+      if (hipError_t e = mmpl_dyn_smem_once(f, SMEM); e != hipSuccess) return e;
+      if (a.cross) hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3(p.main_blocks), dim3(512), SMEM, s, a);
+      else hipLaunchKernelGGL(attn_fwd_kernel<0>, dim3(p.main_blocks), dim3(512), SMEM, s, a);
+      return hipGetLastError();
+    }
+    default:
+      break;
+  }
+  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_symbol(0), mmpl_attention_w64_smem()); e != hipSuccess) return e;
+  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_symbol(1), mmpl_attention_w64_smem()); e != hipSuccess) return e;
+  // main launch: the full rounds, one block per work item; then the tail round's items as sp parts each, and their merge
+  mmpl_launch_attention_w64(a, p.main_blocks, 0, 1, false, s);
+  if (p.sp > 1) {
+    mmpl_launch_attention_w64(a, 8 * p.tail_items * p.sp, p.main_blocks / 8, p.sp, true, s);
+    hipLaunchKernelGGL(attn_merge_kernel, dim3(8 * p.tail_items), dim3(256), 0, s, a, p.main_blocks / 8, p.sp, p.tail_items);
   }
   return hipGetLastError();
 }

@@ -401,7 +401,9 @@ template <int MODE> MMPL_DEV void w64_pass(Ctx& k) {
     float mx = k.score_max();
     if (T > FAST_REF_TILES) {
       // ... and of KV tiles 1 .. 3, which the prologue above already sent on their way into ring slots 1 .. 3: four times the
-      // sample for ~0.2 % more MFMAs per block (all full tiles strictly before the block's last one; T is block-uniform)
+      // sample for ~0.2 % more MFMAs per block (all strictly before the block's last tile; T is block-uniform).  They are scored under tile
+      // 0's mask: a page shorter than 4 tiles puts a ragged tile here, whose zero-filled rows add a score of 0 to the sample -- any
+      // reference inside the window gives the exact softmax, so this only moves WHICH blocks go to the GENERAL pass
       sfor<FAST_REF_TILES - 1>([&k, &mx](auto ei) {
         constexpr int e = decltype(ei)::value + 1;
         // in flight, oldest first: K0 | K1 V0 | K2 V1 | K3 V2 (4 pieces each): K(e) has landed when at most 24 - 8 e are outstanding

@@ -1,6 +1,6 @@
-// Kernel-level entry points of the VAE / TAEHV launchers and of the GEMM in all its forms (include/mmpl_hip.h, "kernel-level entry
-// points for tests and tools"): one launch of vae_kernels.hip / taehv_kernels.hip / gemm.hip on plain arguments, the way mmpl_gemm /
-// mmpl_layernorm expose the DiT kernels.
+// Kernel-level entry points of the VAE / TAEHV launchers, of the GEMM in all its forms and of the attention kernels in all their
+// paths (include/mmpl_hip.h, "kernel-level entry points for tests and tools"): one launch of vae_kernels.hip / taehv_kernels.hip /
+// gemm.hip / attention.hip + attn_w64.hip on plain arguments, the way mmpl_gemm / mmpl_layernorm expose the DiT kernels.
 // They fill the launchers' argument structs and do no arithmetic of their own.  Every check below runs before the first HIP call:
 // a rejected call launches nothing.  The checks bound what a kernel can reach by the sizes the caller states (the header says,
 // per entry, how large each buffer must be for them); alignment is checked because the kernels move 8 or 16 bytes per access.
@@ -245,6 +245,65 @@ int mmpl_gemm_ex(const void* A, int lda, const void* W, int ldw, const void* bia
     plan_out[4] = p.tail_blocks; plan_out[5] = p.splitk_s;
   }
   LAUNCH(mmpl_launch_gemm(g, (hipStream_t)stream), me);
+}
+
+// One launch of mmpl_launch_attention with everything AttnArgs carries (include/mmpl_hip.h).  The plan is the launcher's own
+// (mmpl_attn_plan, which mmpl_launch_attention consults for every choice); it is computed after the checks, because the plan of
+// the cross and the w64 kernel asks the device for its CU count.
+int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
+                     const unsigned char* page_group, int ldk, int ldv, int n_pages, int page_rows, int Lq, int num_heads,
+                     float softmax_scale, void* workspace, size_t workspace_bytes, int variant, int q_prescaled, int cross,
+                     int last_row_copies, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_attn_fwd_ex";
+  if (plan_out)
+    for (int i = 0; i < 8; ++i) plan_out[i] = 0;
+  REJECT(!q || !o || !k_pages || !v_pages, me, "null argument");
+  REJECT(n_pages < 1, me, "n_pages < 1");
+  REJECT(n_pages > MMPL_MAX_PAGES, me, "more than 24 pages");
+  REJECT(page_rows < 1 || Lq < 1 || num_heads < 1, me, "non-positive size");
+  REJECT(!(softmax_scale > 0.f) || softmax_scale > 3.0e38f, me, "softmax_scale must be positive and finite");
+  REJECT(variant != ATTN_AUTO && variant != ATTN_LOCKSTEP && variant != ATTN_W64 && variant != ATTN_W64 + 1, me, "unknown kernel variant");
+  REJECT(ldq % 8, me, "ldq % 8");
+  REJECT(ldo % 8, me, "ldo % 8");
+  REJECT(ldk % 8, me, "ldk % 8");
+  REJECT(ldv % 8, me, "ldv % 8");
+  REJECT(ldq < 128 * num_heads, me, "ldq < 128 * num_heads");
+  REJECT(ldo < 128 * num_heads, me, "ldo < 128 * num_heads");
+  REJECT(ldk < 128 * num_heads, me, "ldk < 128 * num_heads");
+  REJECT(ldv < 128 * num_heads, me, "ldv < 128 * num_heads");
+  REJECT(misaligned(q, 16), me, "q not 16-byte aligned");
+  REJECT(misaligned(o, 16), me, "o not 16-byte aligned");
+  REJECT(last_row_copies < 0, me, "last_row_copies < 0");
+  REJECT(misaligned(workspace, 16), me, "workspace not 16-byte aligned");
+  REJECT(misaligned(history, 2), me, "history not 2-byte aligned");
+  REJECT(misaligned(stats_dev, 8), me, "stats not 8-byte aligned");
+  AttnArgs a = {};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv; a.n_pages = n_pages;
+  a.page_rows = page_rows; a.Lq = Lq; a.H = num_heads; a.scale = softmax_scale;
+  a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
+  for (int i = 0; i < n_pages; ++i) {
+    REJECT(!k_pages[i] || !v_pages[i], me, "null page");
+    REJECT(misaligned(k_pages[i], 16) || misaligned(v_pages[i], 16), me, "page not 16-byte aligned");
+    a.k_pages[i] = (const bf16_t*)k_pages[i]; a.v_pages[i] = (const bf16_t*)v_pages[i];
+    a.page_group[i] = page_group ? page_group[i] : 0;
+  }
+  a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
+  a.q_prescaled = variant == ATTN_W64 + 1 || q_prescaled != 0;
+  a.cross = cross != 0;
+  a.last_row_copies = last_row_copies;
+  a.history = (unsigned char*)history;
+  a.redo_stats = (unsigned long long*)stats_dev;
+  const int resolved = mmpl_attn_resolve_variant(a);          // (no HIP call: the arguments and the run-time switches)
+  REJECT(a.q_prescaled && resolved != ATTN_W64, me, "a prescaled q runs on the 64-rows-per-wave kernel only");
+  REJECT(last_row_copies > 1 && resolved != ATTN_LOCKSTEP, me, "last_row_copies > 1 runs on the lock-step kernel only");
+  REJECT(last_row_copies > 1 && n_pages != 1, me, "last_row_copies > 1 with more than one page");
+  const AttnPlan p = mmpl_attn_plan(a);
+  REJECT(p.invalid, me, "invalid argument");                  // the launcher's own rejections, all stated above: a guard
+  if (plan_out) {
+    plan_out[0] = p.kernel; plan_out[1] = p.n_pages; plan_out[2] = p.kv_tiles; plan_out[3] = p.main_blocks;
+    plan_out[4] = p.tail_items; plan_out[5] = p.sp; plan_out[6] = p.qb_per_block; plan_out[7] = p.blocks_per_head;
+  }
+  LAUNCH(mmpl_launch_attention(a, (hipStream_t)stream), me);
 }
 
 int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long fs1, int C0, int C1, int up, int ntaps,

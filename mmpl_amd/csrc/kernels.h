@@ -126,6 +126,28 @@ int mmpl_attention_w64_smem();
 const void* mmpl_attention_w64_symbol(int split);
 void mmpl_launch_attention_w64(const AttnArgs& a, int blocks, int local_base, int sp, bool split, hipStream_t s);
 size_t mmpl_attention_split_ws_bytes();     // upper bound of what a launch can use
+// What mmpl_launch_attention does with an AttnArgs: every choice of the launcher is made by mmpl_attn_plan and nowhere else (the
+// launcher reads it from the plan; mmpl_attn_fwd_ex reports it to the tests).  Host arithmetic on the arguments and the run-time
+// switches (mmpl_config.h); the CU count of the current device is looked up only for a valid launch of the cross or the w64 kernel.
+enum AttnKernel { ATTN_KERNEL_NONE = 0,      // Lq <= 0: nothing is launched
+                  ATTN_KERNEL_LOCKSTEP = 1,  // attn_fwd_kernel<cross>
+                  ATTN_KERNEL_CROSS1 = 2, ATTN_KERNEL_CROSS2 = 3,   // attn_cross_kernel<1 | 2>
+                  ATTN_KERNEL_W64 = 4 };     // attn_w64_kernel (+ the split launch and attn_merge_kernel when sp > 1)
+struct AttnPlan {
+  int invalid;            // the launcher answers hipErrorInvalidValue and launches nothing (the fields below are then 0)
+  int kernel;             // AttnKernel
+  int n_pages;            // pages the kernel walks (w64: after merge_contiguous_pages)
+  int kv_tiles;           // 64-row KV tiles per query block
+  int main_blocks;        // blocks of the main launch (w64: grid padding included)
+  int tail_items;         // w64: query blocks per XCD that run split in the tail round (0 = no split)
+  int sp;                 // w64: KV parts per tail query block (1 = no split)
+  int qb_per_block;       // cross kernel: 256-row query blocks per block
+  int blocks_per_head;    // cross kernel
+  AttnArgs args;          // what the kernels receive: pages merged and ordered, page_rows_each and history_mem filled
+};
+// The ATTN_* kernel an AttnArgs resolves to (ATTN_AUTO: the text cross-attention and every raw q -> ATTN_LOCKSTEP).
+int mmpl_attn_resolve_variant(const AttnArgs& a);
+AttnPlan mmpl_attn_plan(const AttnArgs& a);
 inline size_t mmpl_attention_history_state_bytes(int Lq, int H) { return ((size_t)H * ((Lq + 255) / 256) * 4 + 255) & ~(size_t)255; }
 inline size_t mmpl_attention_history_bytes(int Lq, int H) { return mmpl_attention_history_state_bytes(Lq, H) + (size_t)H * ((Lq + 255) / 256) * 4 * 128 * sizeof(short); }
 hipError_t mmpl_launch_attention(const AttnArgs& a, hipStream_t s);

@@ -1,4 +1,4 @@
-"""Argument checks of the kernel-level VAE / TAEHV / GEMM entry points (include/mmpl_hip.h): every rejection happens before the first HIP
+"""Argument checks of the kernel-level VAE / TAEHV / GEMM / attention entry points (include/mmpl_hip.h): every rejection happens before the first HIP
 call, so this file needs no GPU and no real buffer -- the pointers below are made-up, aligned addresses that nothing dereferences.
 Each call is wrong in exactly one way and is matched against the message of the check that must catch it."""
 import ctypes as C
@@ -182,6 +182,58 @@ def test_gemm_ex_rejects(kw, msg):
     text, plan = _gemm(**kw)
     assert text.startswith("mmpl_gemm_ex:") and msg in text, text
     assert plan == [0] * 6                                         # no plan was made, nothing was launched
+
+
+def _pages(n, bad=None, off=0):
+    return (VP * max(n, 1))(*[0 if i == bad else P + 0x10000 * i + (off if i == 1 else 0) for i in range(max(n, 1))])
+
+
+def _attn(**kw):
+    """mmpl_attn_fwd_ex on a valid 2-head, 3-page w64 call (variant 3, no workspace), with overrides."""
+    a = dict(q=P, ldq=256, o=P, ldo=256, k_pages=_pages(3), v_pages=_pages(3), page_group=None, ldk=256, ldv=256, n_pages=3, page_rows=72,
+             Lq=300, num_heads=2, softmax_scale=0.6931472, workspace=None, workspace_bytes=0, variant=3, q_prescaled=0, cross=0,
+             last_row_copies=0, history=None, stats_dev=None)
+    a.update(kw)
+    plan = (C.c_int * 8)(*([-1] * 8))
+    rc = _lib.load().mmpl_attn_fwd_ex(*a.values(), plan, None)
+    return _err(rc), list(plan)
+
+
+ATTN_REJECTS = [
+    (dict(q=None), "null argument"), (dict(o=None), "null argument"), (dict(k_pages=None), "null argument"), (dict(v_pages=None), "null argument"),
+    (dict(n_pages=0), "n_pages < 1"), (dict(n_pages=25, k_pages=_pages(25), v_pages=_pages(25)), "more than 24 pages"),
+    (dict(page_rows=0), "non-positive size"), (dict(Lq=0), "non-positive size"), (dict(num_heads=0), "non-positive size"),
+    (dict(softmax_scale=0.0), "softmax_scale"), (dict(softmax_scale=float("nan")), "softmax_scale"), (dict(softmax_scale=float("inf")), "softmax_scale"),
+    (dict(variant=2), "unknown kernel variant"), (dict(variant=5), "unknown kernel variant"), (dict(variant=-1), "unknown kernel variant"),
+    (dict(ldq=260), "ldq % 8"), (dict(ldo=260), "ldo % 8"), (dict(ldk=260), "ldk % 8"), (dict(ldv=260), "ldv % 8"),
+    (dict(ldq=128), "ldq < 128 * num_heads"), (dict(ldo=128), "ldo < 128 * num_heads"), (dict(ldk=128), "ldk < 128 * num_heads"),
+    (dict(ldv=128), "ldv < 128 * num_heads"),
+    (dict(q=P + 8), "q not 16-byte"), (dict(o=P + 8), "o not 16-byte"),
+    (dict(last_row_copies=-1), "last_row_copies < 0"),
+    (dict(workspace=P + 8, workspace_bytes=BIG), "workspace not 16-byte"), (dict(history=P + 1), "history not 2-byte"),
+    (dict(stats_dev=P + 4), "stats not 8-byte"),
+    (dict(k_pages=_pages(3, bad=1)), "null page"), (dict(v_pages=_pages(3, bad=2)), "null page"),
+    (dict(k_pages=_pages(3, off=8)), "page not 16-byte"), (dict(v_pages=_pages(3, off=8)), "page not 16-byte"),
+    (dict(variant=1, q_prescaled=1), "prescaled q"), (dict(variant=0, q_prescaled=1, cross=1), "prescaled q"),
+    (dict(variant=3, last_row_copies=2, n_pages=1), "lock-step kernel only"), (dict(variant=4, last_row_copies=448, n_pages=1), "lock-step kernel only"),
+    (dict(variant=1, last_row_copies=2), "more than one page"),
+]
+
+
+@pytest.mark.parametrize("kw,msg", ATTN_REJECTS, ids=[f"{i}-{m[:18]}" for i, (_, m) in enumerate(ATTN_REJECTS)])
+def test_attn_fwd_ex_rejects(kw, msg):
+    text, plan = _attn(**kw)
+    assert text.startswith("mmpl_attn_fwd_ex:") and msg in text, text
+    assert plan == [0] * 8                                         # no plan was made, nothing was launched
+
+
+def test_attn_entries_keep_their_checks():
+    """mmpl_attn_fwd_variant / _history reject as before."""
+    lib = _lib.load()
+    pg = _pages(3)
+    assert "mmpl_attn_fwd: n_pages out of range" in _err(lib.mmpl_attn_fwd_variant(P, 256, P, 256, pg, pg, 256, 256, 0, 72, 300, 2, 0.5, None, 0, 0, 0, None))
+    assert "mmpl_attn_fwd: unknown kernel variant" in _err(lib.mmpl_attn_fwd_variant(P, 256, P, 256, pg, pg, 256, 256, 3, 72, 300, 2, 0.5, None, 0, 2, 0, None))
+    assert "mmpl_attn_fwd_history: stats must be 8-byte aligned" in _err(lib.mmpl_attn_fwd_history(P, 256, P, 256, pg, pg, 256, 256, 3, 72, 300, 2, 0.5, None, 0, None, P + 4, None))
 
 
 def test_gemm_entries_keep_their_checks():
