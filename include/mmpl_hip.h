@@ -499,6 +499,62 @@ int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const
                      float softmax_scale, void* workspace, size_t workspace_bytes, int variant, int q_prescaled, int cross,
                      int last_row_copies, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream);
 
+/* The norm / RoPE / elementwise kernels (elementwise.hip) one launch at a time, for tests/test_rowpass_exact_gpu.py.  mmpl_layernorm,
+ * mmpl_qknorm_rope and mmpl_qknorm_rope_at are unchanged.  Every check runs before the first HIP call, with one message per check; a
+ * rejected call launches nothing and leaves plan_out all 0.  Rows are moved 16 bytes per lane: x, y, q, k, v, the column vectors,
+ * the gains and the pages are 16-byte aligned and every ld a multiple of 8 elements.
+ *
+ * mmpl_layernorm_ex: the arguments of mmpl_layernorm plus two host-side overrides and the plan.
+ *   x [rows, ldx], y [rows, ldy]: ldx, ldy >= d; d % 8 == 0, d <= 5120; columns < d of rows < rows are read / written, nothing else.
+ *   modulation form (w NULL): row r takes frame r / rows_per_frame; scale and shift each hold
+ *           (ceil(rows / rows_per_frame) - 1) * mod_frame_stride + d elements; mod_frame_stride >= 0 and % 8 == 0, rows_per_frame >= 1.
+ *   affine form: w and b [d].
+ *   pipeline  -1: the launcher's choice (layernorm_pipelined_kernel where NIT = ceil(d / 512) >= 6 and rows >= MMPL_LN_PIPELINE_MIN_ROWS),
+ *           0: never, 1: always -- still only where NIT >= 6, otherwise rejected.
+ *   groups_per_block  0: the launcher's choice (one round of resident blocks); > 0: that many 4-row groups per block, with the
+ *           pipelined kernel only (otherwise rejected).
+ *   plan_out NULL or 7 host ints, filled from the launcher's own plan before the launch:
+ *           [0] kernel: 1 layernorm_kernel, 2 layernorm_pipelined_kernel, 3 qknorm_kernel; [1] NIT as instantiated (1, 2, 3, 4, 6, 8, 10);
+ *           [2] FULL (kernels 2, 3); [3] kernels 2, 3: the blocks counted resident at once; [4] 4-row groups per block;
+ *           [5] grid x; [6] grid y.
+ *
+ * mmpl_qknorm_ex: all of the QK-norm launch as mmpl_dit_forward makes it.  q [rows, ldq] in place; k NULL or [rows, ldk], normed
+ * (and rotated) into the pages; v NULL or [rows, ldv], copied into the pages (needs k); each ld >= d, d % 128 == 0, d <= 5120.
+ *   wq, wk  gains [d] (wk with k).  q_scale: q is multiplied by it before its one rounding; 0 = 1.
+ *   rope != 0: cos_tab / sin_tab are dev float32 [1024][64], 4-byte aligned: row = position, column = rotary pair of the 128-wide head;
+ *           pairs 0-21 take the frame's position frame_ids[f] + *frame_base_dev clamped to 0 .. 1023 (frame_ids: host, n_frames ints;
+ *           frame_base_dev: dev int or NULL = 0), pairs 22-42 the token's grid row, 43-63 its grid column, token t of a frame at
+ *           (t / grid_w, t % grid_w).  Required: rows == n_frames * rows_per_frame, 1 <= grid_w <= 1024 and
+ *           (rows_per_frame - 1) / grid_w <= 1023 (only the frame position is clamped).  Row r belongs to frame r / rows_per_frame
+ *           and goes to row r % rows_per_frame of k_dst / v_dst[frame] (host arrays of n_frames dev pages of rows_per_frame rows of d).
+ *   rope == 0: no rotation; every row r goes to row r of k_dst[0] / v_dst[0] ([rows, d]); rows_per_frame and grid_w are ignored.
+ *           With k NULL this is the plain in-place RMSNorm of T5, CLIP / i2v, the context K and the cross-attention q.
+ *   n_frames  1 .. 8 in either case.  groups_per_block, plan_out: as above (grid y = 1 + k + v).
+ *
+ * mmpl_modulation: emod[l][f][k][:] = bf16(mod[l * mod_layer_stride + k * d + :] + e[f * e_frame_stride + (bcast ? : : k * d + :)]),
+ *   k < nmod.  mod holds (n_layers - 1) * mod_layer_stride + nmod * d elements, e (n_frames - 1) * e_frame_stride + (bcast ? d : nmod * d),
+ *   emod n_layers * n_frames * nmod * d.
+ * mmpl_patchify: x [F, C, h, w] -> a [F * h/2 * w/2, lda], column c * 4 + ph * 2 + pw; columns >= 4 C are zeroed.  h, w even, lda >= 4 C.
+ * mmpl_unpatchify: y [F * h/2 * w/2, ldy], column (ph * 2 + pw) * C + c -> out [F, C, h, w].  h, w even, ldy >= 4 C.
+ * mmpl_sinusoid: t dev float32 [F] -> out [F, freq_dim] = [cos | sin] of t * 10000^(-k / (freq_dim / 2)) in double.  freq_dim even.
+ * mmpl_silu: y[i] = bf16(x[i] / (1 + exp(-x[i]))), n elements.
+ * mmpl_rows_equal_last: flags_dev[r] (dev int32 [rows]) = row r of x [rows, ld] equals row rows - 1 in its first d columns, bit for
+ *   bit.  rows >= 1, d % 8 == 0, ld % 8 == 0, ld >= d, x 16-byte aligned. */
+int mmpl_layernorm_ex(const void* x, int ldx, void* y, int ldy, int rows, int d, float eps, const void* scale, const void* shift,
+                      int mod_frame_stride, int rows_per_frame, const void* w, const void* b, int pipeline, int groups_per_block,
+                      int* plan_out, mmpl_stream_t stream);
+int mmpl_qknorm_ex(void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* wq, const void* wk, int rows, int d,
+                   float eps, float q_scale, int rope, const float* cos_tab, const float* sin_tab, int n_frames, const int* frame_ids,
+                   const int* frame_base_dev, void* const* k_dst, void* const* v_dst, int rows_per_frame, int grid_w,
+                   int groups_per_block, int* plan_out, mmpl_stream_t stream);
+int mmpl_modulation(const void* mod, long long mod_layer_stride, const void* e, int e_frame_stride, int bcast, void* emod, int n_layers,
+                    int n_frames, int nmod, int d, mmpl_stream_t stream);
+int mmpl_patchify(const void* x, void* a, int lda, int F, int C, int h, int w, mmpl_stream_t stream);
+int mmpl_unpatchify(const void* y, int ldy, void* out, int F, int C, int h, int w, mmpl_stream_t stream);
+int mmpl_sinusoid(const float* t, void* out, int F, int freq_dim, mmpl_stream_t stream);
+int mmpl_silu(const void* x, void* y, size_t n, mmpl_stream_t stream);
+int mmpl_rows_equal_last(const void* x, int ld, int rows, int d, int* flags_dev, mmpl_stream_t stream);
+
 /* Optional per-kernel-class hipEvent timing (bench.py's live roofline numbers; off by default, not thread-safe).
  * kinds: 0 gemm, 1 self-attention, 2 cross-attention, 3 layernorm, 4 qk-norm/rope/kv-write, 5 elementwise, 6 cfg+unipc,
  * 7 vae.  on = 0 off, 1 every kind, > 1: only the kinds in the bit mask (on >> 1) (e.g. 2 << 1 | ... ; bench.py times the

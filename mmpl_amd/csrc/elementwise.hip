@@ -424,17 +424,32 @@ inline int grid_for(size_t n, int block = 256) {
 
 }  // namespace
 
-#define DISPATCH_NIT(NITV, KERNEL, ARGS, ROWS, STREAM)                                                     \
-  switch (NITV) {                                                                                          \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(((ROWS) + 3) / 4), dim3(256), 0, STREAM, ARGS); break;      \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(((ROWS) + 3) / 4), dim3(256), 0, STREAM, ARGS); break;      \
-    case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(((ROWS) + 3) / 4), dim3(256), 0, STREAM, ARGS); break;      \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(((ROWS) + 3) / 4), dim3(256), 0, STREAM, ARGS); break;      \
-    case 5: case 6: hipLaunchKernelGGL(KERNEL<6>, dim3(((ROWS) + 3) / 4), dim3(256), 0, STREAM, ARGS); break; \
-    case 7: case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(((ROWS) + 3) / 4), dim3(256), 0, STREAM, ARGS); break; \
-    case 9: case 10: hipLaunchKernelGGL(KERNEL<10>, dim3(((ROWS) + 3) / 4), dim3(256), 0, STREAM, ARGS); break; \
-    default: return hipErrorInvalidValue;                                                                  \
+// ---------------------------------------------------------------- launch plans of the two row passes (kernels.h)
+// The instantiations, in one place: NIT 1-4 as they are, 5 -> 6, 7 -> 8, 9 -> 10 (a whole dead iteration per lane).
+typedef void (*LnKernel)(LnArgs);
+typedef void (*LnPipelinedKernel)(LnArgs, int);
+typedef void (*QkNormKernel)(QkNormArgs, int);
+static int nit_instantiated(int nit) { return nit <= 4 ? nit : (nit + 1) & ~1; }
+static int nit_slot(int n) { return n <= 4 ? n - 1 : n / 2 + 1; }   // 1 2 3 4 6 8 10 -> 0 .. 6
+#define NIT_SWITCH(NV, KERNEL_T, KERNEL_F)                                                                 \
+  switch (NV) {                                                                                            \
+    case 1: return full ? KERNEL_T(1) : KERNEL_F(1);                                                       \
+    case 2: return full ? KERNEL_T(2) : KERNEL_F(2);                                                       \
+    case 3: return full ? KERNEL_T(3) : KERNEL_F(3);                                                       \
+    case 4: return full ? KERNEL_T(4) : KERNEL_F(4);                                                       \
+    case 6: return full ? KERNEL_T(6) : KERNEL_F(6);                                                       \
+    case 8: return full ? KERNEL_T(8) : KERNEL_F(8);                                                       \
+    case 10: return full ? KERNEL_T(10) : KERNEL_F(10);                                                    \
+    default: return nullptr;                                                                               \
   }
+#define LNP_T(N) layernorm_pipelined_kernel<N, true>
+#define LNP_F(N) layernorm_pipelined_kernel<N, false>
+#define LN_ANY(N) layernorm_kernel<N>
+#define QK_T(N) qknorm_kernel<N, true>
+#define QK_F(N) qknorm_kernel<N, false>
+static LnPipelinedKernel ln_pipelined_kernel_of(int n, bool full) { NIT_SWITCH(n, LNP_T, LNP_F) }
+static LnKernel ln_kernel_of(int n) { const bool full = false; NIT_SWITCH(n, LN_ANY, LN_ANY) }
+static QkNormKernel qknorm_kernel_of(int n, bool full) { NIT_SWITCH(n, QK_T, QK_F) }
 // pipelined kernels: all blocks resident at once (blocks per CU from the occupancy query, cached per instantiation), each with
 // a contiguous range of 4-row groups
 template <typename K>
@@ -446,51 +461,86 @@ static int resident_blocks(K kernel, int* cache) {
   }
   return *cache;
 }
-template <typename A>
-static void launch_pipelined(void (*kernel)(A, int), int* cache, const A& a, int rows, int ny, hipStream_t s) {
-  const int ngroups = (rows + 3) / 4, resident = resident_blocks(kernel, cache);
-  int gpb = (ngroups + resident - 1) / resident;
-  hipLaunchKernelGGL(kernel, dim3((ngroups + gpb - 1) / gpb, ny), dim3(256), 0, s, a, gpb);
+// groups per block and grid of a pipelined launch (groups_per_block > 0: the caller's, a test's; 0: one round of resident blocks)
+static void plan_pipelined(RowPassPlan& p, int rows, int groups_per_block) {
+  const int ngroups = (rows + 3) / 4;
+  p.groups_per_block = groups_per_block > 0 ? groups_per_block : (ngroups + p.resident - 1) / p.resident;
+  p.grid_x = (ngroups + p.groups_per_block - 1) / p.groups_per_block;
 }
-#define PIPELINED_CASE(N, KERNEL, ARGS, ROWS, NY, STREAM, FULLV)                                           \
-  { static int c0 = 0, c1 = 0;                                                                             \
-    if (FULLV) launch_pipelined(KERNEL<N, true>, &c1, ARGS, ROWS, NY, STREAM);                             \
-    else launch_pipelined(KERNEL<N, false>, &c0, ARGS, ROWS, NY, STREAM); }
-#define DISPATCH_PIPELINED(NITV, KERNEL, ARGS, ROWS, NY, STREAM, FULLV)                                    \
-  switch (NITV) {                                                                                          \
-    case 1: PIPELINED_CASE(1, KERNEL, ARGS, ROWS, NY, STREAM, FULLV) break;                                \
-    case 2: PIPELINED_CASE(2, KERNEL, ARGS, ROWS, NY, STREAM, FULLV) break;                                \
-    case 3: PIPELINED_CASE(3, KERNEL, ARGS, ROWS, NY, STREAM, FULLV) break;                                \
-    case 4: PIPELINED_CASE(4, KERNEL, ARGS, ROWS, NY, STREAM, FULLV) break;                                \
-    case 5: case 6: PIPELINED_CASE(6, KERNEL, ARGS, ROWS, NY, STREAM, (FULLV) && (NITV) == 6) break;       \
-    case 7: case 8: PIPELINED_CASE(8, KERNEL, ARGS, ROWS, NY, STREAM, (FULLV) && (NITV) == 8) break;       \
-    case 9: case 10: PIPELINED_CASE(10, KERNEL, ARGS, ROWS, NY, STREAM, (FULLV) && (NITV) == 10) break;    \
-    default: return hipErrorInvalidValue;                                                                  \
-  }
 
-hipError_t mmpl_launch_layernorm(const LnArgs& a, hipStream_t s) {
-  if (a.rows <= 0) return hipSuccess;
-  if (a.d % 8 || a.d > 5120 || a.ldx % 8 || a.ldy % 8) return hipErrorInvalidValue;
+// which kernel: host arithmetic on the arguments and the run-time switch only (no HIP call)
+bool mmpl_ln_pipelined(const LnArgs& a, int pipeline) {
   const int nit = (a.d / 8 + 63) / 64;
   // measured (profiles/r05q_*, r05r_*, r05x_*): the pipeline pays from ~6 row groups per block on rows of >= 6 KB (25 200 x 5120: 131 -> 110 us,
   // 21 600: 110 -> 98); below that its prologue / tail cost more than the overlap returns (10 920 x 5120: 44 vs 46 us, 9360: 40 vs 45,
   // 7200: 33 vs 35; 1536-wide rows: 16 vs 18).  MMPL_LN_PIPELINE_MIN_ROWS moves the threshold (mmpl_config.h).
-  if (nit >= 6 && a.rows >= mmpl_config().ln_pipeline_min_rows) {
-    const bool full = a.d == 512 * nit && a.rows % 4 == 0 && (a.w || a.rows_per_frame % 4 == 0);
-    DISPATCH_PIPELINED(nit, layernorm_pipelined_kernel, a, a.rows, 1, s, full);
+  return nit >= 6 && (pipeline < 0 ? a.rows >= mmpl_config().ln_pipeline_min_rows : pipeline == 1);
+}
+
+RowPassPlan mmpl_ln_plan(const LnArgs& a, int pipeline, int groups_per_block) {
+  RowPassPlan p = {};
+  if (a.rows <= 0) return p;                                       // ROWPASS_KERNEL_NONE: nothing is launched
+  p.invalid = 1;
+  if (a.d % 8 || a.d > 5120 || a.ldx % 8 || a.ldy % 8) return p;
+  const int nit = (a.d / 8 + 63) / 64;
+  if (nit < 1 || pipeline < -1 || pipeline > 1 || groups_per_block < 0) return p;
+  if (nit < 6 && pipeline == 1) return p;                          // the pipelined kernel is dispatched from NIT 6 only
+  const bool pipelined = mmpl_ln_pipelined(a, pipeline);
+  if (!pipelined && groups_per_block) return p;                    // the one-row-per-wave kernel has no block ranges
+  p.invalid = 0;
+  p.nit = nit_instantiated(nit);
+  p.grid_y = 1;
+  if (pipelined) {
+    static int cache[7][2];
+    p.kernel = ROWPASS_KERNEL_LN_PIPELINED;
+    // FULL has no per-chunk predicate: only where the row fills every iteration of the INSTANTIATED NIT (d = 2560, 3584, 4608 run
+    // NIT 6, 8, 10 with a dead iteration and are never FULL)
+    p.full = a.d == 512 * p.nit && a.rows % 4 == 0 && (a.w || a.rows_per_frame % 4 == 0);
+    p.resident = resident_blocks(ln_pipelined_kernel_of(p.nit, p.full), &cache[nit_slot(p.nit)][p.full]);
+    plan_pipelined(p, a.rows, groups_per_block);
   } else {
-    DISPATCH_NIT(nit, layernorm_kernel, a, a.rows, s);
+    p.kernel = ROWPASS_KERNEL_LN;
+    p.groups_per_block = 1;
+    p.grid_x = (a.rows + 3) / 4;
   }
+  return p;
+}
+
+hipError_t mmpl_launch_layernorm(const LnArgs& a, hipStream_t s, int pipeline, int groups_per_block) {
+  const RowPassPlan p = mmpl_ln_plan(a, pipeline, groups_per_block);
+  if (p.invalid) return hipErrorInvalidValue;
+  if (p.kernel == ROWPASS_KERNEL_NONE) return hipSuccess;
+  if (p.kernel == ROWPASS_KERNEL_LN_PIPELINED)
+    hipLaunchKernelGGL(ln_pipelined_kernel_of(p.nit, p.full), dim3(p.grid_x, p.grid_y), dim3(256), 0, s, a, p.groups_per_block);
+  else
+    hipLaunchKernelGGL(ln_kernel_of(p.nit), dim3(p.grid_x), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
-hipError_t mmpl_launch_qknorm(const QkNormArgs& a, hipStream_t s) {
-  if (a.rows <= 0) return hipSuccess;
-  if (a.d % 128 || a.d > 5120 || a.ldq % 8 || a.ldk % 8 || a.ldv % 8) return hipErrorInvalidValue;
-  if (a.v && !a.k) return hipErrorInvalidValue;
+RowPassPlan mmpl_qknorm_plan(const QkNormArgs& a, int groups_per_block) {
+  RowPassPlan p = {};
+  if (a.rows <= 0) return p;                                       // ROWPASS_KERNEL_NONE: nothing is launched
+  p.invalid = 1;
+  if (a.d % 128 || a.d > 5120 || a.ldq % 8 || a.ldk % 8 || a.ldv % 8) return p;
+  if (a.v && !a.k) return p;
   const int nit = (a.d / 8 + 63) / 64;
-  const bool full = a.d == 512 * nit && a.rows % 4 == 0;
-  DISPATCH_PIPELINED(nit, qknorm_kernel, a, a.rows, 1 + (a.k ? 1 : 0) + (a.v ? 1 : 0), s, full);
+  if (nit < 1 || groups_per_block < 0) return p;
+  static int cache[7][2];
+  p.invalid = 0;
+  p.kernel = ROWPASS_KERNEL_QKNORM;
+  p.nit = nit_instantiated(nit);
+  p.full = a.d == 512 * p.nit && a.rows % 4 == 0;              // (the instantiated NIT, as in mmpl_ln_plan)
+  p.grid_y = 1 + (a.k ? 1 : 0) + (a.v ? 1 : 0);                    // q | k | v rows go to different blocks
+  p.resident = resident_blocks(qknorm_kernel_of(p.nit, p.full), &cache[nit_slot(p.nit)][p.full]);
+  plan_pipelined(p, a.rows, groups_per_block);
+  return p;
+}
+
+hipError_t mmpl_launch_qknorm(const QkNormArgs& a, hipStream_t s, int groups_per_block) {
+  const RowPassPlan p = mmpl_qknorm_plan(a, groups_per_block);
+  if (p.invalid) return hipErrorInvalidValue;
+  if (p.kernel == ROWPASS_KERNEL_NONE) return hipSuccess;
+  hipLaunchKernelGGL(qknorm_kernel_of(p.nit, p.full), dim3(p.grid_x, p.grid_y), dim3(256), 0, s, a, p.groups_per_block);
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
-// Kernel-level entry points of the VAE / TAEHV launchers, of the GEMM in all its forms and of the attention kernels in all their
-// paths (include/mmpl_hip.h, "kernel-level entry points for tests and tools"): one launch of vae_kernels.hip / taehv_kernels.hip /
-// gemm.hip / attention.hip + attn_w64.hip on plain arguments, the way mmpl_gemm / mmpl_layernorm expose the DiT kernels.
+// Kernel-level entry points of the VAE / TAEHV launchers, of the GEMM in all its forms, of the attention kernels in all their
+// paths and of the norm / RoPE / elementwise kernels (include/mmpl_hip.h, "kernel-level entry points for tests and tools"): one
+// launch of vae_kernels.hip / taehv_kernels.hip / gemm.hip / attention.hip + attn_w64.hip / elementwise.hip on plain arguments,
+// the way mmpl_gemm / mmpl_layernorm expose the DiT kernels.
 // They fill the launchers' argument structs and do no arithmetic of their own.  Every check below runs before the first HIP call:
 // a rejected call launches nothing.  The checks bound what a kernel can reach by the sizes the caller states (the header says,
 // per entry, how large each buffer must be for them); alignment is checked because the kernels move 8 or 16 bytes per access.
@@ -337,6 +338,174 @@ int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream
   REJECT(h < 1 || w < 1 || (long)h * w > 0x7fffffffL / 64, me, "non-positive size");
   REJECT(misaligned(z, 2) || misaligned(dst, 16), me, "misaligned pointer");
   LAUNCH(taehv_launch_prep((const bf16_t*)z, (bf16_t*)dst, h, w, (hipStream_t)stream), me);
+}
+
+// One launch of mmpl_launch_layernorm (include/mmpl_hip.h).  The plan is the launcher's own (mmpl_ln_plan, which mmpl_launch_layernorm
+// consults for every choice); it is computed after the checks, because a pipelined kernel's plan asks the device for its occupancy.
+int mmpl_layernorm_ex(const void* x, int ldx, void* y, int ldy, int rows, int d, float eps, const void* scale, const void* shift,
+                      int mod_frame_stride, int rows_per_frame, const void* w, const void* b, int pipeline, int groups_per_block,
+                      int* plan_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_layernorm_ex";
+  if (plan_out)
+    for (int i = 0; i < 7; ++i) plan_out[i] = 0;
+  REJECT(!x || !y, me, "null argument");
+  REJECT(!w && (!scale || !shift), me, "need (scale, shift) or (w, b)");
+  REJECT(w && !b, me, "w without b");
+  REJECT(rows < 1 || d < 1, me, "non-positive size");
+  REJECT(d % 8, me, "d % 8");
+  REJECT(d > 5120, me, "d > 5120");
+  REJECT(ldx % 8, me, "ldx % 8");
+  REJECT(ldx < d, me, "ldx < d");
+  REJECT(ldy % 8, me, "ldy % 8");
+  REJECT(ldy < d, me, "ldy < d");
+  if (!w) {
+    REJECT(rows_per_frame < 1, me, "rows_per_frame < 1");
+    REJECT(mod_frame_stride < 0, me, "mod_frame_stride < 0");
+    REJECT(mod_frame_stride % 8, me, "mod_frame_stride % 8");
+  }
+  REJECT(misaligned(x, 16), me, "x not 16-byte aligned");
+  REJECT(misaligned(y, 16), me, "y not 16-byte aligned");
+  REJECT(w ? misaligned(w, 16) || misaligned(b, 16) : misaligned(scale, 16) || misaligned(shift, 16), me, "column vector not 16-byte aligned");
+  REJECT(pipeline < -1 || pipeline > 1, me, "pipeline outside -1 .. 1");
+  REJECT(pipeline == 1 && (d / 8 + 63) / 64 < 6, me, "the pipelined kernel exists from NIT 6 (d > 2560) only");
+  REJECT(groups_per_block < 0, me, "groups_per_block < 0");
+  LnArgs a{(const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, d, eps, (const bf16_t*)scale, (const bf16_t*)shift, mod_frame_stride,
+           rows_per_frame > 0 ? rows_per_frame : 1, (const bf16_t*)w, (const bf16_t*)b};
+  // (which kernel runs is the plan's decision, made on the host alone: the last check still precedes the first HIP call)
+  REJECT(groups_per_block && !mmpl_ln_pipelined(a, pipeline), me, "groups_per_block with the one-row-per-wave kernel");
+  const RowPassPlan p = mmpl_ln_plan(a, pipeline, groups_per_block);
+  REJECT(p.invalid, me, "invalid argument");                  // the launcher's own rejections, all stated above: a guard
+  if (plan_out) {
+    plan_out[0] = p.kernel; plan_out[1] = p.nit; plan_out[2] = p.full; plan_out[3] = p.resident; plan_out[4] = p.groups_per_block;
+    plan_out[5] = p.grid_x; plan_out[6] = p.grid_y;
+  }
+  LAUNCH(mmpl_launch_layernorm(a, (hipStream_t)stream, pipeline, groups_per_block), me);
+}
+
+// One launch of mmpl_launch_qknorm with everything QkNormArgs carries (include/mmpl_hip.h); with rope == 0 and k == NULL the
+// arguments are exactly those mmpl_launch_rmsnorm builds.
+int mmpl_qknorm_ex(void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* wq, const void* wk, int rows, int d,
+                   float eps, float q_scale, int rope, const float* cos_tab, const float* sin_tab, int n_frames, const int* frame_ids,
+                   const int* frame_base_dev, void* const* k_dst, void* const* v_dst, int rows_per_frame, int grid_w,
+                   int groups_per_block, int* plan_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_qknorm_ex";
+  if (plan_out)
+    for (int i = 0; i < 7; ++i) plan_out[i] = 0;
+  REJECT(!q || !wq, me, "null argument");
+  REJECT(v && !k, me, "v without k");
+  REJECT(k && (!wk || !k_dst), me, "k without wk or k_dst");
+  REJECT(v && !v_dst, me, "v without v_dst");
+  REJECT(rows < 1 || d < 1, me, "non-positive size");
+  REJECT(d % 128, me, "d % 128");
+  REJECT(d > 5120, me, "d > 5120");
+  REJECT(ldq % 8, me, "ldq % 8");
+  REJECT(ldq < d, me, "ldq < d");
+  REJECT(k && ldk % 8, me, "ldk % 8");
+  REJECT(k && ldk < d, me, "ldk < d");
+  REJECT(v && ldv % 8, me, "ldv % 8");
+  REJECT(v && ldv < d, me, "ldv < d");
+  REJECT(misaligned(q, 16), me, "q not 16-byte aligned");
+  REJECT(misaligned(k, 16), me, "k not 16-byte aligned");
+  REJECT(misaligned(v, 16), me, "v not 16-byte aligned");
+  REJECT(misaligned(wq, 16) || misaligned(wk, 16), me, "gain not 16-byte aligned");
+  REJECT(n_frames < 1 || n_frames > 8, me, "n_frames outside 1 .. 8");
+  if (rope) {
+    REJECT(!cos_tab || !sin_tab || !frame_ids, me, "rope without tables or frame ids");
+    REJECT(misaligned(cos_tab, 4) || misaligned(sin_tab, 4) || misaligned(frame_base_dev, 4), me, "table or frame base not 4-byte aligned");
+    REJECT(rows_per_frame < 1, me, "rows_per_frame < 1");
+    REJECT((long)n_frames * rows_per_frame != rows, me, "rows != n_frames * rows_per_frame");
+    REJECT(grid_w < 1, me, "grid_w < 1");
+    REJECT(grid_w > 1024, me, "grid_w > 1024");
+    REJECT((rows_per_frame - 1) / grid_w > 1023, me, "more than 1024 grid rows");
+  }
+  REJECT(groups_per_block < 0, me, "groups_per_block < 0");
+  QkNormArgs a = {};
+  a.q = (bf16_t*)q; a.ldq = ldq; a.k = (const bf16_t*)k; a.ldk = k ? ldk : 0; a.v = (const bf16_t*)v; a.ldv = v ? ldv : 0;
+  a.wq = (const bf16_t*)wq; a.wk = (const bf16_t*)wk; a.rows = rows; a.d = d; a.eps = eps; a.q_scale = q_scale; a.rope = rope ? 1 : 0;
+  // without rope every row belongs to local frame 0: the one geometry mmpl_launch_rmsnorm states
+  a.rows_per_frame = rope ? rows_per_frame : rows; a.grid_w = rope ? grid_w : 1;
+  if (rope) {
+    a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.frame_base = frame_base_dev;
+    for (int i = 0; i < n_frames; ++i) a.frame_ids[i] = frame_ids[i];
+  }
+  for (int i = 0; k && i < (rope ? n_frames : 1); ++i) {
+    REJECT(!k_dst[i] || (v && !v_dst[i]), me, "null page");
+    REJECT(misaligned(k_dst[i], 16) || (v && misaligned(v_dst[i], 16)), me, "page not 16-byte aligned");
+    a.k_dst[i] = (bf16_t*)k_dst[i];
+    if (v) a.v_dst[i] = (bf16_t*)v_dst[i];
+  }
+  const RowPassPlan p = mmpl_qknorm_plan(a, groups_per_block);
+  REJECT(p.invalid, me, "invalid argument");                  // the launcher's own rejections, all stated above: a guard
+  if (plan_out) {
+    plan_out[0] = p.kernel; plan_out[1] = p.nit; plan_out[2] = p.full; plan_out[3] = p.resident; plan_out[4] = p.groups_per_block;
+    plan_out[5] = p.grid_x; plan_out[6] = p.grid_y;
+  }
+  LAUNCH(mmpl_launch_qknorm(a, (hipStream_t)stream, groups_per_block), me);
+}
+
+// The small kernels of elementwise.hip, one launch each on plain arguments.
+int mmpl_modulation(const void* mod, long long mod_layer_stride, const void* e, int e_frame_stride, int bcast, void* emod, int n_layers,
+                    int n_frames, int nmod, int d, mmpl_stream_t stream) {
+  const char* me = "mmpl_modulation";
+  REJECT(!mod || !e || !emod, me, "null argument");
+  REJECT(n_layers < 1 || n_frames < 1 || nmod < 1 || d < 1, me, "non-positive size");
+  REJECT(mod_layer_stride < 0 || e_frame_stride < 0, me, "negative stride");
+  REJECT(too_many(n_layers, n_frames, (long)nmod * d) || (long)nmod * d > 0x7fffffffL, me, "too many elements");
+  REJECT(misaligned(mod, 2) || misaligned(e, 2) || misaligned(emod, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_modulation((const bf16_t*)mod, (size_t)mod_layer_stride, (const bf16_t*)e, e_frame_stride, bcast ? 1 : 0, (bf16_t*)emod,
+                                n_layers, n_frames, nmod, d, (hipStream_t)stream), me);
+}
+
+int mmpl_patchify(const void* x, void* a, int lda, int F, int C, int h, int w, mmpl_stream_t stream) {
+  const char* me = "mmpl_patchify";
+  REJECT(!x || !a, me, "null argument");
+  REJECT(F < 1 || C < 1 || h < 1 || w < 1, me, "non-positive size");
+  REJECT((h | w) & 1, me, "odd h or w");
+  REJECT(C > 0x1fffffff || lda < 4 * C, me, "lda < 4 C");
+  REJECT(too_many(F, h, w), me, "too many pixels");
+  REJECT(misaligned(x, 2) || misaligned(a, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_patchify((const bf16_t*)x, (bf16_t*)a, lda, F, C, h, w, (hipStream_t)stream), me);
+}
+
+int mmpl_unpatchify(const void* y, int ldy, void* out, int F, int C, int h, int w, mmpl_stream_t stream) {
+  const char* me = "mmpl_unpatchify";
+  REJECT(!y || !out, me, "null argument");
+  REJECT(F < 1 || C < 1 || h < 1 || w < 1, me, "non-positive size");
+  REJECT((h | w) & 1, me, "odd h or w");
+  REJECT(C > 0x1fffffff || ldy < 4 * C, me, "ldy < 4 C");
+  REJECT(too_many(F, h, w), me, "too many pixels");
+  REJECT(misaligned(y, 2) || misaligned(out, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_unpatchify((const bf16_t*)y, ldy, (bf16_t*)out, F, C, h, w, (hipStream_t)stream), me);
+}
+
+int mmpl_sinusoid(const float* t, void* out, int F, int freq_dim, mmpl_stream_t stream) {
+  const char* me = "mmpl_sinusoid";
+  REJECT(!t || !out, me, "null argument");
+  REJECT(F < 1 || freq_dim < 2, me, "non-positive size");
+  REJECT(freq_dim & 1, me, "odd freq_dim");
+  REJECT((long)F * (freq_dim / 2) > 0x7fffffffL - 256, me, "too many elements");
+  REJECT(misaligned(t, 4) || misaligned(out, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_sinusoid(t, (bf16_t*)out, F, freq_dim, (hipStream_t)stream), me);
+}
+
+int mmpl_silu(const void* x, void* y, size_t n, mmpl_stream_t stream) {
+  const char* me = "mmpl_silu";
+  REJECT(!x || !y, me, "null argument");
+  REJECT(n < 1, me, "non-positive size");
+  REJECT(misaligned(x, 2) || misaligned(y, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_silu((const bf16_t*)x, (bf16_t*)y, n, (hipStream_t)stream), me);
+}
+
+int mmpl_rows_equal_last(const void* x, int ld, int rows, int d, int* flags_dev, mmpl_stream_t stream) {
+  const char* me = "mmpl_rows_equal_last";
+  REJECT(!x || !flags_dev, me, "null argument");
+  REJECT(rows < 1, me, "rows < 1");
+  REJECT(d < 1, me, "non-positive size");
+  REJECT(d % 8, me, "d % 8");
+  REJECT(ld % 8, me, "ld % 8");
+  REJECT(ld < d, me, "ld < d");
+  REJECT(misaligned(x, 16) || misaligned(flags_dev, 4), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_rows_equal_last((const bf16_t*)x, ld, rows, d, flags_dev, (hipStream_t)stream), me);
 }
 
 }  // extern "C"

@@ -163,7 +163,30 @@ struct LnArgs {
   const bf16_t* scale; const bf16_t* shift; int mod_frame_stride; int rows_per_frame;  // modulation form
   const bf16_t* w; const bf16_t* b;                                                    // affine form (if w != null)
 };
-hipError_t mmpl_launch_layernorm(const LnArgs& a, hipStream_t s);
+// What mmpl_launch_layernorm / mmpl_launch_qknorm do with their arguments: every choice of the two launchers is made by mmpl_ln_plan /
+// mmpl_qknorm_plan and nowhere else (the launchers read it from the plan; mmpl_layernorm_ex / mmpl_qknorm_ex report it to the tests).
+// Host arithmetic on the arguments and the run-time switches (mmpl_config.h); a pipelined kernel's resident blocks come from the
+// occupancy query and the CU count of the current device, once per instantiation.
+enum RowPassKernel { ROWPASS_KERNEL_NONE = 0,          // rows <= 0: nothing is launched
+                     ROWPASS_KERNEL_LN = 1,            // layernorm_kernel<NIT>: one row per wave
+                     ROWPASS_KERNEL_LN_PIPELINED = 2,  // layernorm_pipelined_kernel<NIT, FULL>
+                     ROWPASS_KERNEL_QKNORM = 3 };      // qknorm_kernel<NIT, FULL>
+struct RowPassPlan {
+  int invalid;            // the launcher answers hipErrorInvalidValue and launches nothing (the fields below are then 0)
+  int kernel;             // RowPassKernel
+  int nit;                // NIT as instantiated: 1, 2, 3, 4, 6, 8 or 10
+  int full;               // FULL (pipelined kernels): d == 512 NIT, rows % 4 == 0 (LayerNorm's modulation form: rows_per_frame % 4 == 0 too)
+  int resident;           // pipelined kernels: the blocks counted resident at once (blocks per CU x CUs)
+  int groups_per_block;   // 4-row groups per block (layernorm_kernel: 1)
+  int grid_x, grid_y;
+};
+// Two host-side overrides travel beside the argument structs (those are kernel arguments), for the kernel-level tests; the product
+// passes the defaults everywhere.  pipeline: -1 = the launcher's choice (NIT >= 6 and rows >= MMPL_LN_PIPELINE_MIN_ROWS), 0 = never,
+// 1 = always -- still only where NIT >= 6, else invalid.  groups_per_block: 0 = the launcher's choice (one round of resident blocks);
+// > 0 with a pipelined kernel only.
+bool mmpl_ln_pipelined(const LnArgs& a, int pipeline = -1);   // the plan's kernel choice by itself: no HIP call
+RowPassPlan mmpl_ln_plan(const LnArgs& a, int pipeline = -1, int groups_per_block = 0);
+hipError_t mmpl_launch_layernorm(const LnArgs& a, hipStream_t s, int pipeline = -1, int groups_per_block = 0);
 
 // Full-dim RMSNorm (+ optional 3-axis RoPE, + optional K/V page write) on the fused qkv projection.
 struct QkNormArgs {
@@ -182,7 +205,8 @@ struct QkNormArgs {
   bf16_t* k_dst[8]; bf16_t* v_dst[8]; // per local frame destination page base (row stride = d); k_out for no-page mode
   int rows_per_frame, grid_w;
 };
-hipError_t mmpl_launch_qknorm(const QkNormArgs& a, hipStream_t s);
+RowPassPlan mmpl_qknorm_plan(const QkNormArgs& a, int groups_per_block = 0);
+hipError_t mmpl_launch_qknorm(const QkNormArgs& a, hipStream_t s, int groups_per_block = 0);
 
 // rmsnorm of a plain [rows, d] matrix in place (context K)
 // out_scale != 0: the normalised row is multiplied by it before its (single) rounding (a q that feeds ATTN_W64: scale * log2 e)

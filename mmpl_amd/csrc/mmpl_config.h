@@ -1,6 +1,7 @@
 // Run-time switches of libmmpl_hip.so: ONE struct, filled ONCE from the environment on first use (device_state.hip), read by
-// every launcher.  They exist for A/B measurements and for the parity tests of the non-default paths (each is exercised by a
-// child-process test in tests/test_kernels_gpu.py); production runs set none of them.  Switches whose A/B is settled are removed
+// every launcher.  They exist for A/B measurements and for the parity tests of the non-default paths (the kernel switches are exercised by
+// child-process tests in tests/test_kernels_gpu.py; what MMPL_LN_PIPELINE_MIN_ROWS chooses between is launched directly, with mmpl_layernorm_ex's
+// `pipeline`, by tests/test_rowpass_exact_gpu.py); production runs set none of them.  Switches whose A/B is settled are removed
 // with their logs as the record (round 5: MMPL_GEMM_DIRECT_EPILOGUE / _STATIC_TILES / _NO_SYNC_SWEEPS, MMPL_VAE_NO_HALO --
 // profiles/r03d_*, r03C_*, r03_vae_decode_ladder.md; MMPL_CROSS_NO_COLLAPSE: the collapse is now the caller's explicit `cross_rows`).
 //

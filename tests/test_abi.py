@@ -78,6 +78,11 @@ def test_signatures_follow_header():
         "mmpl_dit_forward": (ci, fwd + [vp]),
         "mmpl_dit_forward_at": (ci, fwd + [vp, vp]),
         "mmpl_attn_fwd": (ci, [vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]),
+        "mmpl_layernorm_ex": (ci, [vp, ci, vp, ci, ci, ci, cf, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp]),
+        "mmpl_qknorm_ex": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, cf, cf, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp]),
+        "mmpl_modulation": (ci, [vp, ll, vp, ci, ci, vp, ci, ci, ci, ci, vp]),
+        "mmpl_silu": (ci, [vp, vp, sz, vp]),
+        "mmpl_rows_equal_last": (ci, [vp, ci, ci, ci, vp, vp]),
     }
     assert len(table["mmpl_dit_forward_at"][1]) == 22
     for name, (restype, argtypes) in table.items():

@@ -1,4 +1,4 @@
-"""Argument checks of the kernel-level VAE / TAEHV / GEMM / attention entry points (include/mmpl_hip.h): every rejection happens before the first HIP
+"""Argument checks of the kernel-level VAE / TAEHV / GEMM / attention / norm / RoPE / elementwise entry points (include/mmpl_hip.h): every rejection happens before the first HIP
 call, so this file needs no GPU and no real buffer -- the pointers below are made-up, aligned addresses that nothing dereferences.
 Each call is wrong in exactly one way and is matched against the message of the check that must catch it."""
 import ctypes as C
@@ -242,3 +242,132 @@ def test_gemm_entries_keep_their_checks():
     assert "mmpl_gemm: unknown epilogue" in _err(lib.mmpl_gemm(P, 192, P, 192, P, P, 520, 1100, 520, 192, 6, None, 0, None, 0, 0, None))
     assert "mmpl_gemm: missing epilogue operand" in _err(lib.mmpl_gemm_tickets(P, 192, P, 192, P, P, 520, 1100, 520, 192, 4, None, 0, None, 0, 0, None, None))
     assert "mmpl_gemm_scratch: scratch missing" in _err(lib.mmpl_gemm_scratch(P, 192, P, 192, P, P, 520, 1100, 520, 192, 0, None, 0, None, 0, 0, None, 0, None))
+
+
+def _ln(**kw):
+    """mmpl_layernorm_ex on a valid 50 x 3072 modulation call (2 frames of 25 rows, the forward's 6 d layout), with overrides."""
+    a = dict(x=P, ldx=3072, y=P, ldy=3072, rows=50, d=3072, eps=1e-6, scale=P + 2 * 3072, shift=P, mod_frame_stride=6 * 3072,
+             rows_per_frame=25, w=None, b=None, pipeline=-1, groups_per_block=0)
+    a.update(kw)
+    plan = (C.c_int * 7)(*([-1] * 7))
+    rc = _lib.load().mmpl_layernorm_ex(*a.values(), plan, None)
+    return _err(rc), list(plan)
+
+
+LN_REJECTS = [
+    (dict(x=None), "null argument"), (dict(y=None), "null argument"),
+    (dict(scale=None), "need (scale, shift) or (w, b)"), (dict(shift=None), "need (scale, shift) or (w, b)"), (dict(w=P), "w without b"),
+    (dict(rows=0), "non-positive size"), (dict(rows=-4), "non-positive size"), (dict(d=0), "non-positive size"),
+    (dict(d=3076, ldx=3080, ldy=3080), "d % 8"), (dict(d=5128, ldx=5128, ldy=5128), "d > 5120"),
+    (dict(ldx=3076), "ldx % 8"), (dict(ldx=3064), "ldx < d"), (dict(ldy=3076), "ldy % 8"), (dict(ldy=3064), "ldy < d"),
+    (dict(rows_per_frame=0), "rows_per_frame < 1"), (dict(mod_frame_stride=-8), "mod_frame_stride < 0"),
+    (dict(mod_frame_stride=3076), "mod_frame_stride % 8"),
+    (dict(x=P + 8), "x not 16-byte"), (dict(y=P + 8), "y not 16-byte"), (dict(scale=P + 8), "column vector not 16-byte"),
+    (dict(shift=P + 4), "column vector not 16-byte"), (dict(w=P, b=P + 8), "column vector not 16-byte"),
+    (dict(w=P + 2, b=P), "column vector not 16-byte"),
+    (dict(pipeline=2), "pipeline outside"), (dict(pipeline=-2), "pipeline outside"),
+    (dict(pipeline=1, d=2560, ldx=2560, ldy=2560), "from NIT 6"), (dict(pipeline=1, d=8, ldx=8, ldy=8), "from NIT 6"),
+    (dict(groups_per_block=-1), "groups_per_block < 0"),
+    (dict(groups_per_block=3), "one-row-per-wave kernel"), (dict(pipeline=0, groups_per_block=3), "one-row-per-wave kernel"),
+]
+
+
+@pytest.mark.parametrize("kw,msg", LN_REJECTS, ids=[f"{i}-{m[:18]}" for i, (_, m) in enumerate(LN_REJECTS)])
+def test_layernorm_ex_rejects(kw, msg):
+    text, plan = _ln(**kw)
+    assert text.startswith("mmpl_layernorm_ex:") and msg in text, text
+    assert plan == [0] * 7                                         # no plan was reported, nothing was launched
+
+
+def _qk(**kw):
+    """mmpl_qknorm_ex on a valid forward-form call (q, k in a [30, 3 d] matrix, 2 frames of a 3 x 5 grid, d = 1536), with overrides."""
+    d = 1536
+    a = dict(q=P, ldq=3 * d, k=P + 2 * d, ldk=3 * d, v=None, ldv=0, wq=P, wk=P, rows=30, d=d, eps=1e-6, q_scale=0.125, rope=1, cos_tab=P,
+             sin_tab=P, n_frames=2, frame_ids=(C.c_int * 8)(), frame_base_dev=None, k_dst=_frames(2), v_dst=None, rows_per_frame=15,
+             grid_w=5, groups_per_block=0)
+    a.update(kw)
+    plan = (C.c_int * 7)(*([-1] * 7))
+    rc = _lib.load().mmpl_qknorm_ex(*a.values(), plan, None)
+    return _err(rc), list(plan)
+
+
+_V = dict(v=P + 4 * 1536, ldv=3 * 1536, v_dst=_frames(2))
+QK_REJECTS = [
+    (dict(q=None), "null argument"), (dict(wq=None), "null argument"),
+    (dict(_V, k=None), "v without k"), (dict(wk=None), "k without wk or k_dst"), (dict(k_dst=None), "k without wk or k_dst"),
+    (dict(_V, v_dst=None), "v without v_dst"),
+    (dict(rows=0, n_frames=1, rows_per_frame=0), "non-positive size"), (dict(d=0), "non-positive size"),
+    (dict(d=1544), "d % 128"), (dict(d=5248, ldq=3 * 5248, ldk=3 * 5248), "d > 5120"),
+    (dict(ldq=4612), "ldq % 8"), (dict(ldq=1528), "ldq < d"), (dict(ldk=4612), "ldk % 8"), (dict(ldk=1528), "ldk < d"),
+    (dict(_V, ldv=4612), "ldv % 8"), (dict(_V, ldv=1528), "ldv < d"),
+    (dict(q=P + 8), "q not 16-byte"), (dict(k=P + 8), "k not 16-byte"), (dict(_V, v=P + 8), "v not 16-byte"),
+    (dict(wq=P + 8), "gain not 16-byte"), (dict(wk=P + 4), "gain not 16-byte"),
+    (dict(n_frames=0), "n_frames outside"), (dict(n_frames=9, rows=135), "n_frames outside"),
+    (dict(cos_tab=None), "rope without tables"), (dict(sin_tab=None), "rope without tables"), (dict(frame_ids=None), "rope without tables"),
+    (dict(cos_tab=P + 2), "not 4-byte aligned"), (dict(frame_base_dev=P + 2), "not 4-byte aligned"),
+    (dict(rows_per_frame=0), "rows_per_frame < 1"),
+    (dict(rows=31), "rows != n_frames * rows_per_frame"), (dict(rows_per_frame=16), "rows != n_frames * rows_per_frame"),
+    (dict(grid_w=0), "grid_w < 1"), (dict(grid_w=1025), "grid_w > 1024"),
+    (dict(rows=2050, rows_per_frame=1025, grid_w=1), "more than 1024 grid rows"),
+    (dict(groups_per_block=-1), "groups_per_block < 0"),
+    (dict(k_dst=_frames(2, bad=1)), "null page"), (dict(_V, v_dst=_frames(2, bad=0)), "null page"),
+    (dict(k_dst=(VP * 2)(P, P + 0x1008)), "page not 16-byte"), (dict(_V, v_dst=(VP * 2)(P + 8, P + 0x1000)), "page not 16-byte"),
+    (dict(rope=0, k_dst=_frames(1, bad=0)), "null page"),
+]
+
+
+@pytest.mark.parametrize("kw,msg", QK_REJECTS, ids=[f"{i}-{m[:18]}" for i, (_, m) in enumerate(QK_REJECTS)])
+def test_qknorm_ex_rejects(kw, msg):
+    text, plan = _qk(**kw)
+    assert text.startswith("mmpl_qknorm_ex:") and msg in text, text
+    assert plan == [0] * 7                                         # no plan was reported, nothing was launched
+
+
+def test_small_elementwise_entry_points_reject():
+    lib = _lib.load()
+    e = lambda rc: _err(rc)
+    d = 256
+    assert "mmpl_modulation: null argument" in e(lib.mmpl_modulation(None, 6 * d, P, 6 * d, 0, P, 2, 3, 6, d, None))
+    assert "null argument" in e(lib.mmpl_modulation(P, 6 * d, None, 6 * d, 0, P, 2, 3, 6, d, None))
+    assert "null argument" in e(lib.mmpl_modulation(P, 6 * d, P, 6 * d, 0, None, 2, 3, 6, d, None))
+    assert "non-positive" in e(lib.mmpl_modulation(P, 6 * d, P, 6 * d, 0, P, 0, 3, 6, d, None))
+    assert "non-positive" in e(lib.mmpl_modulation(P, 6 * d, P, 6 * d, 0, P, 2, 3, 6, 0, None))
+    assert "negative stride" in e(lib.mmpl_modulation(P, -6 * d, P, 6 * d, 0, P, 2, 3, 6, d, None))
+    assert "negative stride" in e(lib.mmpl_modulation(P, 6 * d, P, -d, 0, P, 2, 3, 6, d, None))
+    assert "too many elements" in e(lib.mmpl_modulation(P, 6 * d, P, 6 * d, 0, P, 1 << 12, 1 << 12, 1 << 8, d, None))
+    assert "misaligned" in e(lib.mmpl_modulation(P + 1, 6 * d, P, 6 * d, 0, P, 2, 3, 6, d, None))
+    assert "mmpl_patchify: null argument" in e(lib.mmpl_patchify(None, P, 64, 3, 16, 6, 10, None))
+    assert "non-positive" in e(lib.mmpl_patchify(P, P, 64, 0, 16, 6, 10, None))
+    assert "odd h or w" in e(lib.mmpl_patchify(P, P, 64, 3, 16, 7, 10, None))
+    assert "odd h or w" in e(lib.mmpl_patchify(P, P, 64, 3, 16, 6, 9, None))
+    assert "lda < 4 C" in e(lib.mmpl_patchify(P, P, 63, 3, 16, 6, 10, None))
+    assert "too many pixels" in e(lib.mmpl_patchify(P, P, 64, 2, 16, 1 << 16, 1 << 14, None))
+    assert "misaligned" in e(lib.mmpl_patchify(P, P + 1, 64, 3, 16, 6, 10, None))
+    assert "mmpl_unpatchify: null argument" in e(lib.mmpl_unpatchify(P, 64, None, 3, 16, 6, 10, None))
+    assert "non-positive" in e(lib.mmpl_unpatchify(P, 64, P, 3, 0, 6, 10, None))
+    assert "odd h or w" in e(lib.mmpl_unpatchify(P, 64, P, 3, 16, 6, 11, None))
+    assert "ldy < 4 C" in e(lib.mmpl_unpatchify(P, 60, P, 3, 16, 6, 10, None))
+    assert "too many pixels" in e(lib.mmpl_unpatchify(P, 64, P, 2, 16, 1 << 16, 1 << 14, None))
+    assert "misaligned" in e(lib.mmpl_unpatchify(P + 1, 64, P, 3, 16, 6, 10, None))
+    assert "mmpl_sinusoid: null argument" in e(lib.mmpl_sinusoid(None, P, 4, 256, None))
+    assert "non-positive" in e(lib.mmpl_sinusoid(P, P, 0, 256, None))
+    assert "non-positive" in e(lib.mmpl_sinusoid(P, P, 4, 0, None))
+    assert "odd freq_dim" in e(lib.mmpl_sinusoid(P, P, 4, 255, None))
+    assert "too many elements" in e(lib.mmpl_sinusoid(P, P, 1 << 24, 256, None))
+    assert "misaligned" in e(lib.mmpl_sinusoid(P + 2, P, 4, 256, None))
+    assert "mmpl_silu: null argument" in e(lib.mmpl_silu(P, None, 16, None))
+    assert "non-positive" in e(lib.mmpl_silu(P, P, 0, None))
+    assert "misaligned" in e(lib.mmpl_silu(P + 1, P, 16, None))
+    assert "mmpl_rows_equal_last: null argument" in e(lib.mmpl_rows_equal_last(P, 4104, 5, 4096, None, None))
+    assert "rows < 1" in e(lib.mmpl_rows_equal_last(P, 4104, 0, 4096, P, None))
+    assert "non-positive" in e(lib.mmpl_rows_equal_last(P, 4104, 5, 0, P, None))
+    assert "d % 8" in e(lib.mmpl_rows_equal_last(P, 4104, 5, 4092, P, None))
+    assert "ld % 8" in e(lib.mmpl_rows_equal_last(P, 4100, 5, 4096, P, None))
+    assert "ld < d" in e(lib.mmpl_rows_equal_last(P, 4088, 5, 4096, P, None))
+    assert "misaligned" in e(lib.mmpl_rows_equal_last(P + 8, 4104, 5, 4096, P, None))
+    assert "misaligned" in e(lib.mmpl_rows_equal_last(P, 4104, 5, 4096, P + 2, None))
+
+
+def test_norm_entries_keep_their_checks():
+    """mmpl_layernorm rejects as before."""
+    assert "mmpl_layernorm: need (scale, shift) or (w, b)" in _err(_lib.load().mmpl_layernorm(P, 256, P, 256, 4, 256, 1e-6, None, None, 0, 1, None, None, None))

@@ -336,7 +336,8 @@ def test_attention_spiked_scores(lib, variant, spike):
 
 
 @pytest.mark.parametrize("d,rows,S", [(256, 200, 50), (1536, 97, 97), (5120, 130, 65), (512, 8, 4),
-                                      # several row groups per block (the pipelined loop), a frame change inside a block's range:
+                                      # many rows, several frames (all below MMPL_LN_PIPELINE_MIN_ROWS or NIT 6: layernorm_kernel; the pipelined
+                                      # kernel is run one launch at a time by tests/test_rowpass_exact_gpu.py):
                                       (5120, 7224, 1204), (1536, 9 * 1204, 1204), (5120, 7 * 1001, 1001), (1024, 20000, 20000)])
 def test_layernorm_modulate_and_affine(lib, d, rows, S):
     from mmpl_amd import _lib
@@ -363,7 +364,7 @@ def test_layernorm_modulate_and_affine(lib, d, rows, S):
 
 
 @pytest.mark.parametrize("H,lat,frames", [(2, (8, 12), [3, 10]), (12, (6, 10), [0, 19, 20]), (40, (4, 8), [5]),
-                                          # several row groups per block (the pipelined loop): 7224 rows of 5120 / 1536, and an odd row count
+                                          # several row groups per block (qknorm_kernel's prefetch loop): 7224 rows of 5120 / 1536, and an odd row count
                                           (40, (56, 86), [0, 1, 2, 7, 19, 20]), (12, (56, 86), [3, 4, 5, 6, 7, 8, 9]), (4, (70, 86), [2, 3, 4, 5, 6])])
 def test_qknorm_rope_kvwrite(lib, H, lat, frames):
     from mmpl_amd import _lib
