@@ -226,6 +226,8 @@ typedef struct MmplUniPCStep {
   int pred_order;
   float p_c1, p_c2, p_c3, p_inv_rk;
 } MmplUniPCStep;
+/* flow_cond, x, m0, m1, last_sample: dev bf16 [n], none of them NULL (rejected before the launch); flow_uncond NULL = flow_cond is
+ * already the combined flow. */
 int mmpl_cfg_unipc_step(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
                         size_t n, const MmplUniPCStep* s, mmpl_stream_t stream);
 /* Device-resident form, for ONE hipGraph per denoise step (2 DiT forwards + this) replayed sampling_steps times with no
@@ -554,6 +556,33 @@ int mmpl_unpatchify(const void* y, int ldy, void* out, int F, int C, int h, int 
 int mmpl_sinusoid(const float* t, void* out, int F, int freq_dim, mmpl_stream_t stream);
 int mmpl_silu(const void* x, void* y, size_t n, mmpl_stream_t stream);
 int mmpl_rows_equal_last(const void* x, int ld, int rows, int d, int* flags_dev, mmpl_stream_t stream);
+
+/* The glue kernels of the umT5 encoder (t5.hip) and of the CLIP / i2v path (i2v.hip) one launch at a time, for
+ * tests/test_glue_exact_gpu.py: the launches mmpl_t5_encode, mmpl_i2v_img_proj, mmpl_i2v_cross_attn and mmpl_clip_visual make, with
+ * their grid geometry.  Every check runs before the first HIP call, with one message per check; a rejected call launches nothing.
+ * Tensors are dev bf16 unless stated; ids, bucket and mask are dev int32.
+ *
+ * mmpl_t5_gather: out[l][:] = emb[ids[l]][:], 16 bytes per access.  ids [L]; emb [vocab, dim]; out [L, dim]; dim % 8 == 0; emb and
+ *   out 16-byte aligned.  PRECONDITION: every ids[l] lies in [0, vocab) -- the ids are device memory, which the entry cannot read,
+ *   and an id outside the table makes the kernel read outside emb (T5Engine.encode checks the ids on the host).
+ * mmpl_t5_softmax: scores dev float32 [H][L][L] -> p [H][L][L]; row (h, i), key j: bf16(bf16(scores) + bias), bias =
+ *   pos_emb[bucket[j - i + L - 1] * H + h], or finfo(bfloat16).min where mask[j] == 0; softmax over j in fp32, rounded once.
+ *   pos_emb [num_buckets, H]; bucket [2 L - 1] with every value in [0, num_buckets) (a PRECONDITION, like the ids); mask [L].
+ *   L % 64 == 0 (the rule of mmpl_t5_create); H * L blocks must fit the grid.
+ * mmpl_t5_transpose: v [L, ld], head h at column h * c -> vt [H][c][L].  ld >= H * c; v holds (L - 1) * ld + H * c elements, vt
+ *   H * c * L.  (mmpl_t5_encode passes the V third of the fused qkv: v = qkv + 2 H c, ld = 3 H c.)
+ * mmpl_t5_gated: f[i] = bf16(f[i] * gelu_tanh(g[i])), every tensor op of the reference's GELU rounded to bf16; f, g [n], f in place.
+ * mmpl_t5_zero_pad: out [L, dim] in place: rows l with mask[l] == 0 become +0; mask [L].
+ * mmpl_gelu_erf: x[i] = bf16(0.5 x[i] (1 + erf(x[i] / sqrt 2))) in fp32, in place; x [n].
+ * mmpl_add: a[i] = bf16(a[i] + b[i]), one fp32 add; a, b [n], a in place. */
+int mmpl_t5_gather(const int* ids, const void* emb, void* out, int L, int dim, mmpl_stream_t stream);
+int mmpl_t5_softmax(const float* scores, const void* pos_emb, const int* bucket, const int* mask, void* p, int H, int L,
+                    mmpl_stream_t stream);
+int mmpl_t5_transpose(const void* v, int ld, void* vt, int L, int c, int H, mmpl_stream_t stream);
+int mmpl_t5_gated(void* f, const void* g, size_t n, mmpl_stream_t stream);
+int mmpl_t5_zero_pad(void* out, const int* mask, int L, int dim, mmpl_stream_t stream);
+int mmpl_gelu_erf(void* x, size_t n, mmpl_stream_t stream);
+int mmpl_add(void* a, const void* b, size_t n, mmpl_stream_t stream);
 
 /* Optional per-kernel-class hipEvent timing (bench.py's live roofline numbers; off by default, not thread-safe).
  * kinds: 0 gemm, 1 self-attention, 2 cross-attention, 3 layernorm, 4 qk-norm/rope/kv-write, 5 elementwise, 6 cfg+unipc,

@@ -701,6 +701,7 @@ int mmpl_qknorm_rope_at(MmplDit* h, void* q, int ldq, const void* k, int ldk, co
 int mmpl_cfg_unipc_step(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
                         size_t n, const MmplUniPCStep* st, mmpl_stream_t stream) {
   if (!st) return fail("mmpl_cfg_unipc_step", "null step");
+  if (!flow_cond || !x || !m0 || !m1 || !last_sample) return fail("mmpl_cfg_unipc_step", "null argument");
   UniPCArgs a = {};
   a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.guidance = st->guidance; a.x = (bf16_t*)x;
   a.m0 = (bf16_t*)m0; a.m1 = (bf16_t*)m1; a.last_sample = (bf16_t*)last_sample; a.n = n; a.sigma_cur = st->sigma_cur;
@@ -717,6 +718,7 @@ int mmpl_cfg_unipc_step_table(const void* flow_cond, const void* flow_uncond, vo
                               const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream) {
   if (!table_dev || !step_dev || !timestep_dev || !timestep_table_dev || n_steps < 1 || n_timestep < 1)
     return fail("mmpl_cfg_unipc_step_table", "bad arguments");
+  if (!flow_cond || !x || !m0 || !m1 || !last_sample) return fail("mmpl_cfg_unipc_step_table", "null argument");
   static_assert(sizeof(MmplUniPCStep) == sizeof(UniPCStepDev), "table layout");
   UniPCArgs a = {};
   a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.x = (bf16_t*)x;

@@ -52,6 +52,12 @@ hipError_t mmpl_launch_add(bf16_t* a, const bf16_t* b, size_t n, hipStream_t s) 
   return hipGetLastError();
 }
 
+// x = bf16(gelu_erf(x)) in place, n elements
+hipError_t mmpl_launch_gelu_erf(bf16_t* x, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(gelu_erf_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, n);
+  return hipGetLastError();
+}
+
 extern "C" {
 
 size_t mmpl_i2v_img_proj_workspace_bytes(int n_tok, int clip_dim, int dim) {
@@ -73,7 +79,7 @@ int mmpl_i2v_img_proj(const void* clip_fea, int n_tok, int clip_dim, int dim, co
   LnArgs l0 = {(const bf16_t*)clip_fea, clip_dim, t0, clip_dim, n_tok, clip_dim, 1e-5f, nullptr, nullptr, 0, 1, W[0], W[1]};
   I2V_TRY(mmpl_launch_layernorm(l0, s), "mmpl_i2v_img_proj: layernorm 0");
   I2V_TRY(linear(t0, clip_dim, W[2], W[3], t1, n_tok, clip_dim, s), "mmpl_i2v_img_proj: fc1");
-  gelu_erf_kernel<<<blocks_for((size_t)n_tok * clip_dim), 256, 0, s>>>(t1, (size_t)n_tok * clip_dim);
+  I2V_TRY(mmpl_launch_gelu_erf(t1, (size_t)n_tok * clip_dim, s), "mmpl_i2v_img_proj: gelu");
   I2V_TRY(linear(t1, clip_dim, W[4], W[5], t2, n_tok, dim, s), "mmpl_i2v_img_proj: fc2");
   LnArgs l1 = {t2, dim, (bf16_t*)out, dim, n_tok, dim, 1e-5f, nullptr, nullptr, 0, 1, W[6], W[7]};
   I2V_TRY(mmpl_launch_layernorm(l1, s), "mmpl_i2v_img_proj: layernorm 1");
@@ -109,8 +115,7 @@ int mmpl_i2v_cross_attn(const void* x, int Lq, int dim, const void* wq, const vo
   I2V_TRY(mmpl_launch_rmsnorm(q, dim, (const bf16_t*)norm_q_w, Lq, dim, eps, s), "mmpl_i2v_cross_attn: norm_q");
   I2V_TRY(attend(q, ai, (const bf16_t*)k_img, (const bf16_t*)v_img, n_img, Lq, dim, s), "mmpl_i2v_cross_attn: image attention");
   I2V_TRY(attend(q, at, (const bf16_t*)k_txt, (const bf16_t*)v_txt, n_txt, Lq, dim, s), "mmpl_i2v_cross_attn: text attention");
-  add_kernel<<<blocks_for((size_t)Lq * dim), 256, 0, s>>>(at, ai, (size_t)Lq * dim);
-  I2V_TRY(hipGetLastError(), "mmpl_i2v_cross_attn: x + img_x");
+  I2V_TRY(mmpl_launch_add(at, ai, (size_t)Lq * dim, s), "mmpl_i2v_cross_attn: x + img_x");
   I2V_TRY(linear(at, dim, (const bf16_t*)wo, (const bf16_t*)bo, (bf16_t*)out, Lq, dim, s), "mmpl_i2v_cross_attn: o");
   I2V_TRY(hipGetLastError(), "mmpl_i2v_cross_attn");
   return 0;
@@ -158,8 +163,7 @@ int mmpl_clip_visual(const void* patches, int n_patch, int pk, int dim, int mlp_
     GemmArgs g = {(const bf16_t*)patches, pk, G[0], pk, nullptr, x + dim, dim, n_patch, dim, pk, EPI_BIAS, nullptr, 0, nullptr, 0, 1, 1.0f, 0, 0, 0, 0, 0};
     I2V_TRY(mmpl_launch_gemm(g, s), "mmpl_clip_visual: patch embedding");
   }
-  add_kernel<<<blocks_for((size_t)n * dim), 256, 0, s>>>(x, G[2], (size_t)n * dim);
-  I2V_TRY(hipGetLastError(), "mmpl_clip_visual: + pos_embedding");
+  I2V_TRY(mmpl_launch_add(x, G[2], (size_t)n * dim, s), "mmpl_clip_visual: + pos_embedding");
   {
     LnArgs l = {x, dim, hbuf, dim, n, dim, eps, nullptr, nullptr, 0, 1, G[3], G[4]};
     I2V_TRY(mmpl_launch_layernorm(l, s), "mmpl_clip_visual: pre_norm");
@@ -184,8 +188,7 @@ int mmpl_clip_visual(const void* patches, int n_patch, int pk, int dim, int mlp_
     LnArgs l2 = {x, dim, hbuf, dim, n, dim, eps, nullptr, nullptr, 0, 1, W[6], W[7]};
     I2V_TRY(mmpl_launch_layernorm(l2, s), "mmpl_clip_visual: norm2");
     I2V_TRY(linear(hbuf, dim, W[8], W[9], big, n, mlp_dim, s), "mmpl_clip_visual: mlp.0");
-    gelu_erf_kernel<<<blocks_for((size_t)n * mlp_dim), 256, 0, s>>>(big, (size_t)n * mlp_dim);
-    I2V_TRY(hipGetLastError(), "mmpl_clip_visual: gelu");
+    I2V_TRY(mmpl_launch_gelu_erf(big, (size_t)n * mlp_dim, s), "mmpl_clip_visual: gelu");
     {
       GemmArgs g = {big, mlp_dim, W[10], mlp_dim, W[11], x, dim, n, dim, mlp_dim, EPI_RES, x, dim, nullptr, 0, 1, 1.0f, 0, 0, 0, 0, 0};
       I2V_TRY(mmpl_launch_gemm(g, s), "mmpl_clip_visual: mlp.2 + residual");

@@ -1,7 +1,7 @@
 // Kernel-level entry points of the VAE / TAEHV launchers, of the GEMM in all its forms, of the attention kernels in all their
-// paths and of the norm / RoPE / elementwise kernels (include/mmpl_hip.h, "kernel-level entry points for tests and tools"): one
-// launch of vae_kernels.hip / taehv_kernels.hip / gemm.hip / attention.hip + attn_w64.hip / elementwise.hip on plain arguments,
-// the way mmpl_gemm / mmpl_layernorm expose the DiT kernels.
+// paths, of the norm / RoPE / elementwise kernels and of the umT5 / CLIP glue kernels (include/mmpl_hip.h, "kernel-level entry points
+// for tests and tools"): one launch of vae_kernels.hip / taehv_kernels.hip / gemm.hip / attention.hip + attn_w64.hip /
+// elementwise.hip / t5.hip / i2v.hip on plain arguments, the way mmpl_gemm / mmpl_layernorm expose the DiT kernels.
 // They fill the launchers' argument structs and do no arithmetic of their own.  Every check below runs before the first HIP call:
 // a rejected call launches nothing.  The checks bound what a kernel can reach by the sizes the caller states (the header says,
 // per entry, how large each buffer must be for them); alignment is checked because the kernels move 8 or 16 bytes per access.
@@ -506,6 +506,74 @@ int mmpl_rows_equal_last(const void* x, int ld, int rows, int d, int* flags_dev,
   REJECT(ld < d, me, "ld < d");
   REJECT(misaligned(x, 16) || misaligned(flags_dev, 4), me, "misaligned pointer");
   LAUNCH(mmpl_launch_rows_equal_last((const bf16_t*)x, ld, rows, d, flags_dev, (hipStream_t)stream), me);
+}
+
+// The glue kernels of t5.hip and i2v.hip, one launch each on plain arguments: the launchers mmpl_t5_encode, mmpl_i2v_* and
+// mmpl_clip_visual call.
+int mmpl_t5_gather(const int* ids, const void* emb, void* out, int L, int dim, mmpl_stream_t stream) {
+  const char* me = "mmpl_t5_gather";
+  REJECT(!ids || !emb || !out, me, "null argument");
+  REJECT(L < 1 || dim < 1, me, "non-positive size");
+  REJECT(dim % 8, me, "dim % 8");
+  REJECT(misaligned(emb, 16), me, "emb not 16-byte aligned");
+  REJECT(misaligned(out, 16), me, "out not 16-byte aligned");
+  REJECT(misaligned(ids, 4), me, "ids not 4-byte aligned");
+  LAUNCH(mmpl_launch_t5_gather(ids, (const bf16_t*)emb, (bf16_t*)out, L, dim, (hipStream_t)stream), me);
+}
+
+int mmpl_t5_softmax(const float* scores, const void* pos_emb, const int* bucket, const int* mask, void* p, int H, int L,
+                    mmpl_stream_t stream) {
+  const char* me = "mmpl_t5_softmax";
+  REJECT(!scores || !pos_emb || !bucket || !mask || !p, me, "null argument");
+  REJECT(H < 1 || L < 1, me, "non-positive size");
+  REJECT(L % 64, me, "L % 64");
+  REJECT((long)H * L > 0x7fffffffL, me, "H * L exceeds the grid");
+  REJECT(misaligned(scores, 4) || misaligned(bucket, 4) || misaligned(mask, 4), me, "scores, bucket or mask not 4-byte aligned");
+  REJECT(misaligned(pos_emb, 2) || misaligned(p, 2), me, "pos_emb or p not 2-byte aligned");
+  LAUNCH(mmpl_launch_t5_softmax(scores, (const bf16_t*)pos_emb, bucket, mask, (bf16_t*)p, H, L, (hipStream_t)stream), me);
+}
+
+int mmpl_t5_transpose(const void* v, int ld, void* vt, int L, int c, int H, mmpl_stream_t stream) {
+  const char* me = "mmpl_t5_transpose";
+  REJECT(!v || !vt, me, "null argument");
+  REJECT(L < 1 || c < 1 || H < 1, me, "non-positive size");
+  REJECT((long)ld < (long)H * c, me, "ld < H * c");
+  REJECT(H > 65535 || (c + 31) / 32 > 65535, me, "H or c / 32 exceeds the grid");
+  REJECT(misaligned(v, 2) || misaligned(vt, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_t5_transpose((const bf16_t*)v, ld, (bf16_t*)vt, L, c, H, (hipStream_t)stream), me);
+}
+
+int mmpl_t5_gated(void* f, const void* g, size_t n, mmpl_stream_t stream) {
+  const char* me = "mmpl_t5_gated";
+  REJECT(!f || !g, me, "null argument");
+  REJECT(n < 1, me, "non-positive size");
+  REJECT(misaligned(f, 2) || misaligned(g, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_t5_gated((bf16_t*)f, (const bf16_t*)g, n, (hipStream_t)stream), me);
+}
+
+int mmpl_t5_zero_pad(void* out, const int* mask, int L, int dim, mmpl_stream_t stream) {
+  const char* me = "mmpl_t5_zero_pad";
+  REJECT(!out || !mask, me, "null argument");
+  REJECT(L < 1 || dim < 1, me, "non-positive size");
+  REJECT(misaligned(out, 2), me, "out not 2-byte aligned");
+  REJECT(misaligned(mask, 4), me, "mask not 4-byte aligned");
+  LAUNCH(mmpl_launch_t5_zero_pad((bf16_t*)out, mask, L, dim, (hipStream_t)stream), me);
+}
+
+int mmpl_gelu_erf(void* x, size_t n, mmpl_stream_t stream) {
+  const char* me = "mmpl_gelu_erf";
+  REJECT(!x, me, "null argument");
+  REJECT(n < 1, me, "non-positive size");
+  REJECT(misaligned(x, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_gelu_erf((bf16_t*)x, n, (hipStream_t)stream), me);
+}
+
+int mmpl_add(void* a, const void* b, size_t n, mmpl_stream_t stream) {
+  const char* me = "mmpl_add";
+  REJECT(!a || !b, me, "null argument");
+  REJECT(n < 1, me, "non-positive size");
+  REJECT(misaligned(a, 2) || misaligned(b, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_add((bf16_t*)a, (const bf16_t*)b, n, (hipStream_t)stream), me);
 }
 
 }  // extern "C"

@@ -220,6 +220,8 @@ hipError_t mmpl_launch_patchify(const bf16_t* x, bf16_t* a, int lda, int F, int 
 // unpatchify: y[F*gh*gw, 4*C] (col = (ph*2+pw)*C + c) -> out[F, C, h, w]
 // a = bf16(a + b), n elements (i2v.hip)
 hipError_t mmpl_launch_add(bf16_t* a, const bf16_t* b, size_t n, hipStream_t s);
+// x = bf16(0.5 x (1 + erf(x / sqrt 2))) in place, n elements (i2v.hip: torch.nn.GELU())
+hipError_t mmpl_launch_gelu_erf(bf16_t* x, size_t n, hipStream_t s);
 hipError_t mmpl_launch_unpatchify(const bf16_t* y, int ldy, bf16_t* out, int F, int C, int h, int w, hipStream_t s);
 // sinusoidal timestep embedding (fp64 math): t[F] fp32 -> out[F, freq_dim] bf16 ([cos | sin])
 hipError_t mmpl_launch_zero_ints(int* p, int n, hipStream_t s);
@@ -255,3 +257,17 @@ struct UniPCStepDev {
 };
 hipError_t mmpl_launch_unipc_table(const UniPCArgs& a, const UniPCStepDev* table, int* step, float* t_out, const float* t_tab,
                                    int n_t, int n_steps, hipStream_t s);
+
+// ---------------------------------------------------------------- umT5 glue (t5.hip): the launches of mmpl_t5_encode, one each
+// out[l][:] = emb[ids[l]][:]   (dim % 8 == 0, 16 bytes per access; ids in [0, vocab))
+hipError_t mmpl_launch_t5_gather(const int* ids, const bf16_t* emb, bf16_t* out, int L, int dim, hipStream_t s);
+// sc fp32 [H][L][L] -> p bf16 [H][L][L]: softmax over j of bf16(bf16(sc) + bias), bias = pos_emb[bucket[j - i + L - 1] * H + h] or
+// finfo(bf16).min where mask[j] == 0; one block per (h, i)
+hipError_t mmpl_launch_t5_softmax(const float* sc, const bf16_t* pos_emb, const int* bucket, const int* mask, bf16_t* p, int H, int L,
+                                  hipStream_t s);
+// v [L][ld] (head h at column h * c) -> vt [H][c][L]
+hipError_t mmpl_launch_t5_transpose(const bf16_t* v, int ld, bf16_t* vt, int L, int c, int H, hipStream_t s);
+// f = bf16(f * GELU_tanh(g)) with every tensor op of the reference rounded to bf16, n elements
+hipError_t mmpl_launch_t5_gated(bf16_t* f, const bf16_t* g, size_t n, hipStream_t s);
+// out [L][dim]: rows l with mask[l] == 0 are zeroed
+hipError_t mmpl_launch_t5_zero_pad(bf16_t* out, const int* mask, int L, int dim, hipStream_t s);

@@ -90,6 +90,33 @@ inline int grid_for(size_t n) {
   return (int)(g > 8192 ? 8192 : (g == 0 ? 1 : g));
 }
 
+}  // namespace
+
+// The five launches, each with its grid geometry stated once: mmpl_t5_encode below and the kernel-level entries (kernel_entry.hip)
+hipError_t mmpl_launch_t5_gather(const int* ids, const bf16_t* emb, bf16_t* out, int L, int dim, hipStream_t s) {
+  hipLaunchKernelGGL(t5_gather_kernel, dim3(grid_for((size_t)L * dim / 8)), dim3(256), 0, s, ids, emb, out, L, dim);
+  return hipGetLastError();
+}
+hipError_t mmpl_launch_t5_softmax(const float* sc, const bf16_t* pos_emb, const int* bucket, const int* mask, bf16_t* p, int H, int L,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(t5_softmax_kernel, dim3(H * L), dim3(256), 0, s, sc, pos_emb, bucket, mask, p, H, L);
+  return hipGetLastError();
+}
+hipError_t mmpl_launch_t5_transpose(const bf16_t* v, int ld, bf16_t* vt, int L, int c, int H, hipStream_t s) {
+  hipLaunchKernelGGL(t5_transpose_kernel, dim3((L + 31) / 32, (c + 31) / 32, H), dim3(256), 0, s, v, ld, vt, L, c);
+  return hipGetLastError();
+}
+hipError_t mmpl_launch_t5_gated(bf16_t* f, const bf16_t* g, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(t5_gated_kernel, dim3(grid_for(n)), dim3(256), 0, s, f, g, n);
+  return hipGetLastError();
+}
+hipError_t mmpl_launch_t5_zero_pad(bf16_t* out, const int* mask, int L, int dim, hipStream_t s) {
+  hipLaunchKernelGGL(t5_zero_pad_kernel, dim3(grid_for((size_t)L * dim)), dim3(256), 0, s, out, mask, L, dim);
+  return hipGetLastError();
+}
+
+namespace {
+
 struct Carve {
   char* base;
   size_t off = 0;
@@ -177,25 +204,25 @@ int mmpl_t5_encode(MmplT5* h, const int* ids, const int* mask, const int* bucket
     chk(hipMemcpyAsync(y, x, (size_t)L * d * 2, hipMemcpyDeviceToDevice, s));
     chk(mmpl_launch_rmsnorm(y, d, wt, L, d, c.eps, s));
   };
-  hipLaunchKernelGGL(t5_gather_kernel, dim3(grid_for((size_t)L * d / 8)), dim3(256), 0, s, ids, h->w[T_EMB], w.x, L, d);
+  chk(mmpl_launch_t5_gather(ids, h->w[T_EMB], w.x, L, d, s));
   for (int l = 0; l < c.num_layers; ++l) {
     const bf16_t* const* lw = &h->w[TG + l * TLN];
     norm(w.x, lw[TL_N1], w.xn);
     gemm(w.xn, d, lw[TL_QKV], d, w.qkv, 3 * da, L, 3 * da, d, EPI_BIAS, nullptr, 0);
     // scores[h] = q_h . k_h^T (fp32), one batched launch over the heads
     gemm(w.qkv, 3 * da, w.qkv + da, 3 * da, w.sc, L, L, L, hc, EPI_F32_SCALE, nullptr, 0, H, hc, hc, (long)L * L);
-    hipLaunchKernelGGL(t5_softmax_kernel, dim3(H * L), dim3(256), 0, s, w.sc, lw[TL_POS], bucket, mask, w.p, H, L);
-    hipLaunchKernelGGL(t5_transpose_kernel, dim3((L + 31) / 32, (hc + 31) / 32, H), dim3(256), 0, s, w.qkv + 2 * da, 3 * da, w.vt, L, hc);
+    chk(mmpl_launch_t5_softmax(w.sc, lw[TL_POS], bucket, mask, w.p, H, L, s));
+    chk(mmpl_launch_t5_transpose(w.qkv + 2 * da, 3 * da, w.vt, L, hc, H, s));
     gemm(w.p, L, w.vt, L, w.attn, da, L, hc, L, EPI_BIAS, nullptr, 0, H, (long)L * L, (long)hc * L, hc);
     gemm(w.attn, da, lw[TL_O], da, w.x, d, L, d, da, EPI_RES, w.x, d);
     norm(w.x, lw[TL_N2], w.xn);
     gemm(w.xn, d, lw[TL_GATE], d, w.g, df, L, df, d, EPI_BIAS, nullptr, 0);
     gemm(w.xn, d, lw[TL_FC1], d, w.f, df, L, df, d, EPI_BIAS, nullptr, 0);
-    hipLaunchKernelGGL(t5_gated_kernel, dim3(grid_for((size_t)L * df)), dim3(256), 0, s, w.f, w.g, (size_t)L * df);
+    chk(mmpl_launch_t5_gated(w.f, w.g, (size_t)L * df, s));
     gemm(w.f, df, lw[TL_FC2], df, w.x, d, L, d, df, EPI_RES, w.x, d);
   }
   norm(w.x, h->w[T_NORM], (bf16_t*)out);
-  hipLaunchKernelGGL(t5_zero_pad_kernel, dim3(grid_for((size_t)L * d)), dim3(256), 0, s, (bf16_t*)out, mask, L, d);
+  chk(mmpl_launch_t5_zero_pad((bf16_t*)out, mask, L, d, s));
   chk(hipGetLastError());
   if (err != hipSuccess) return mmpl_set_error("mmpl_t5_encode", hipGetErrorString(err));
   return 0;

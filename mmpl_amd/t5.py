@@ -52,12 +52,19 @@ class T5Engine:
         def g(k):
             return sd[prefix + k].to(device=self.device, dtype=torch.bfloat16).contiguous()
         w = [g("token_embedding.weight"), g("norm.weight")]
+        if w[0].shape != (self.cfg["vocab"], self.cfg["dim"]):      # t5_gather_kernel trusts ids < vocab to stay inside this table
+            raise ValueError(f"token_embedding.weight is {tuple(w[0].shape)}, the config says [{self.cfg['vocab']}, {self.cfg['dim']}]")
         for i in range(self.cfg["num_layers"]):
             p = f"blocks.{i}."
             w += [g(p + "norm1.weight"),
                   torch.cat([g(p + "attn.q.weight"), g(p + "attn.k.weight"), g(p + "attn.v.weight")]).contiguous(),
                   g(p + "attn.o.weight"), g(p + "pos_embedding.embedding.weight"), g(p + "norm2.weight"),
                   g(p + "ffn.gate.0.weight"), g(p + "ffn.fc1.weight"), g(p + "ffn.fc2.weight")]
+        for i in range(self.cfg["num_layers"]):                    # t5_softmax_kernel reads pos_emb[bucket * num_heads + head]
+            pos = w[2 + 8 * i + 3]
+            if pos.shape != (self.cfg["num_buckets"], self.cfg["num_heads"]):
+                raise ValueError(f"blocks.{i}.pos_embedding.embedding.weight is {tuple(pos.shape)}, the config says "
+                                 f"[{self.cfg['num_buckets']}, {self.cfg['num_heads']}]")
         n = self._lib.mmpl_t5_num_weights(C.byref(self._c))
         assert len(w) == n
         arr = (C.c_void_p * n)(*[t.data_ptr() for t in w])
@@ -68,6 +75,9 @@ class T5Engine:
         """ids, mask: [B, text_len] integer -> [B, text_len, dim] bf16 with padding rows zeroed (WanTextEncoder.forward)."""
         B, L = ids.shape
         assert L == self.text_len
+        # an id outside the embedding table would make t5_gather_kernel read outside it: reject before any launch
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.cfg["vocab"]):
+            raise ValueError(f"token ids must lie in [0, {self.cfg['vocab']}): got {int(ids.min())} .. {int(ids.max())}")
         if self._ws is None:
             self._ws = torch.empty(self._lib.mmpl_t5_workspace_bytes(self._h), dtype=torch.uint8, device=self.device)
         ids = ids.to(device=self.device, dtype=torch.int32).contiguous()

@@ -83,6 +83,13 @@ def test_signatures_follow_header():
         "mmpl_modulation": (ci, [vp, ll, vp, ci, ci, vp, ci, ci, ci, ci, vp]),
         "mmpl_silu": (ci, [vp, vp, sz, vp]),
         "mmpl_rows_equal_last": (ci, [vp, ci, ci, ci, vp, vp]),
+        "mmpl_t5_gather": (ci, [vp, vp, vp, ci, ci, vp]),
+        "mmpl_t5_softmax": (ci, [vp, vp, vp, vp, vp, ci, ci, vp]),
+        "mmpl_t5_transpose": (ci, [vp, ci, vp, ci, ci, ci, vp]),
+        "mmpl_t5_gated": (ci, [vp, vp, sz, vp]),
+        "mmpl_t5_zero_pad": (ci, [vp, vp, ci, ci, vp]),
+        "mmpl_gelu_erf": (ci, [vp, sz, vp]),
+        "mmpl_add": (ci, [vp, vp, sz, vp]),
     }
     assert len(table["mmpl_dit_forward_at"][1]) == 22
     for name, (restype, argtypes) in table.items():

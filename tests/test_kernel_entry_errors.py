@@ -1,4 +1,4 @@
-"""Argument checks of the kernel-level VAE / TAEHV / GEMM / attention / norm / RoPE / elementwise entry points (include/mmpl_hip.h): every rejection happens before the first HIP
+"""Argument checks of the kernel-level VAE / TAEHV / GEMM / attention / norm / RoPE / elementwise / umT5 and CLIP glue entry points (include/mmpl_hip.h): every rejection happens before the first HIP
 call, so this file needs no GPU and no real buffer -- the pointers below are made-up, aligned addresses that nothing dereferences.
 Each call is wrong in exactly one way and is matched against the message of the check that must catch it."""
 import ctypes as C
@@ -371,3 +371,75 @@ def test_small_elementwise_entry_points_reject():
 def test_norm_entries_keep_their_checks():
     """mmpl_layernorm rejects as before."""
     assert "mmpl_layernorm: need (scale, shift) or (w, b)" in _err(_lib.load().mmpl_layernorm(P, 256, P, 256, 4, 256, 1e-6, None, None, 0, 1, None, None, None))
+
+
+def test_glue_entry_points_reject():
+    """mmpl_t5_gather / _softmax / _transpose / _gated / _zero_pad, mmpl_gelu_erf, mmpl_add: every check, one wrong thing per call."""
+    lib = _lib.load()
+    e = lambda rc: _err(rc)
+    assert "mmpl_t5_gather: null argument" in e(lib.mmpl_t5_gather(None, P, P, 64, 128, None))
+    assert "null argument" in e(lib.mmpl_t5_gather(P, None, P, 64, 128, None))
+    assert "null argument" in e(lib.mmpl_t5_gather(P, P, None, 64, 128, None))
+    assert "non-positive" in e(lib.mmpl_t5_gather(P, P, P, 0, 128, None))
+    assert "non-positive" in e(lib.mmpl_t5_gather(P, P, P, 64, -8, None))
+    assert "dim % 8" in e(lib.mmpl_t5_gather(P, P, P, 64, 132, None))
+    assert "emb not 16-byte" in e(lib.mmpl_t5_gather(P, P + 8, P, 64, 128, None))
+    assert "out not 16-byte" in e(lib.mmpl_t5_gather(P, P, P + 2, 64, 128, None))
+    assert "ids not 4-byte" in e(lib.mmpl_t5_gather(P + 2, P, P, 64, 128, None))
+    assert "mmpl_t5_softmax: null argument" in e(lib.mmpl_t5_softmax(None, P, P, P, P, 3, 64, None))
+    assert "null argument" in e(lib.mmpl_t5_softmax(P, None, P, P, P, 3, 64, None))
+    assert "null argument" in e(lib.mmpl_t5_softmax(P, P, None, P, P, 3, 64, None))
+    assert "null argument" in e(lib.mmpl_t5_softmax(P, P, P, None, P, 3, 64, None))
+    assert "null argument" in e(lib.mmpl_t5_softmax(P, P, P, P, None, 3, 64, None))
+    assert "non-positive" in e(lib.mmpl_t5_softmax(P, P, P, P, P, 0, 64, None))
+    assert "non-positive" in e(lib.mmpl_t5_softmax(P, P, P, P, P, 3, 0, None))
+    assert "L % 64" in e(lib.mmpl_t5_softmax(P, P, P, P, P, 3, 96, None))
+    assert "exceeds the grid" in e(lib.mmpl_t5_softmax(P, P, P, P, P, 1 << 16, 1 << 15, None))
+    assert "not 4-byte" in e(lib.mmpl_t5_softmax(P + 2, P, P, P, P, 3, 64, None))
+    assert "not 4-byte" in e(lib.mmpl_t5_softmax(P, P, P + 2, P, P, 3, 64, None))
+    assert "not 4-byte" in e(lib.mmpl_t5_softmax(P, P, P, P + 1, P, 3, 64, None))
+    assert "not 2-byte" in e(lib.mmpl_t5_softmax(P, P + 1, P, P, P, 3, 64, None))
+    assert "not 2-byte" in e(lib.mmpl_t5_softmax(P, P, P, P, P + 1, 3, 64, None))
+    assert "mmpl_t5_transpose: null argument" in e(lib.mmpl_t5_transpose(None, 192, P, 64, 64, 3, None))
+    assert "null argument" in e(lib.mmpl_t5_transpose(P, 192, None, 64, 64, 3, None))
+    assert "non-positive" in e(lib.mmpl_t5_transpose(P, 192, P, 0, 64, 3, None))
+    assert "non-positive" in e(lib.mmpl_t5_transpose(P, 192, P, 64, 0, 3, None))
+    assert "non-positive" in e(lib.mmpl_t5_transpose(P, 192, P, 64, 64, 0, None))
+    assert "ld < H * c" in e(lib.mmpl_t5_transpose(P, 191, P, 64, 64, 3, None))
+    assert "ld < H * c" in e(lib.mmpl_t5_transpose(P, 1 << 30, P, 64, 1 << 20, 1 << 12, None))
+    assert "exceeds the grid" in e(lib.mmpl_t5_transpose(P, 1 << 30, P, 64, 64, 1 << 16, None))
+    assert "exceeds the grid" in e(lib.mmpl_t5_transpose(P, 1 << 30, P, 64, 1 << 22, 2, None))
+    assert "misaligned" in e(lib.mmpl_t5_transpose(P + 1, 192, P, 64, 64, 3, None))
+    assert "misaligned" in e(lib.mmpl_t5_transpose(P, 192, P + 1, 64, 64, 3, None))
+    assert "mmpl_t5_gated: null argument" in e(lib.mmpl_t5_gated(None, P, 16, None))
+    assert "null argument" in e(lib.mmpl_t5_gated(P, None, 16, None))
+    assert "non-positive" in e(lib.mmpl_t5_gated(P, P, 0, None))
+    assert "misaligned" in e(lib.mmpl_t5_gated(P + 1, P, 16, None))
+    assert "misaligned" in e(lib.mmpl_t5_gated(P, P + 1, 16, None))
+    assert "mmpl_t5_zero_pad: null argument" in e(lib.mmpl_t5_zero_pad(None, P, 64, 128, None))
+    assert "null argument" in e(lib.mmpl_t5_zero_pad(P, None, 64, 128, None))
+    assert "non-positive" in e(lib.mmpl_t5_zero_pad(P, P, 0, 128, None))
+    assert "non-positive" in e(lib.mmpl_t5_zero_pad(P, P, 64, 0, None))
+    assert "out not 2-byte" in e(lib.mmpl_t5_zero_pad(P + 1, P, 64, 128, None))
+    assert "mask not 4-byte" in e(lib.mmpl_t5_zero_pad(P, P + 2, 64, 128, None))
+    assert "mmpl_gelu_erf: null argument" in e(lib.mmpl_gelu_erf(None, 16, None))
+    assert "non-positive" in e(lib.mmpl_gelu_erf(P, 0, None))
+    assert "misaligned" in e(lib.mmpl_gelu_erf(P + 1, 16, None))
+    assert "mmpl_add: null argument" in e(lib.mmpl_add(None, P, 16, None))
+    assert "null argument" in e(lib.mmpl_add(P, None, 16, None))
+    assert "non-positive" in e(lib.mmpl_add(P, P, 0, None))
+    assert "misaligned" in e(lib.mmpl_add(P + 1, P, 16, None))
+    assert "misaligned" in e(lib.mmpl_add(P, P + 1, 16, None))
+
+
+def test_unipc_entries_reject_null_tensors():
+    """mmpl_cfg_unipc_step / _table: a null flow_cond, x, m0, m1 or last_sample is rejected before the launch (flow_uncond may be NULL)."""
+    lib = _lib.load()
+    st = _lib.MmplUniPCStep()
+    for bad in (0, 2, 3, 4, 5):
+        a = [P] * 6
+        a[bad] = None
+        assert "mmpl_cfg_unipc_step: null argument" in _err(lib.mmpl_cfg_unipc_step(*a, 16, C.byref(st), None))
+        assert "mmpl_cfg_unipc_step_table: null argument" in _err(lib.mmpl_cfg_unipc_step_table(*a, 16, P, P, P, P, 1, 50, None))
+    assert "null step" in _err(lib.mmpl_cfg_unipc_step(*[P] * 6, 16, None, None))
+    assert "bad arguments" in _err(lib.mmpl_cfg_unipc_step_table(*[P] * 6, 16, None, P, P, P, 1, 50, None))

@@ -62,6 +62,40 @@ def test_t5_text_len_512_vs_oracle_and_padding_invariance():
     assert torch.equal(eng.encode(ids2, mask)[1], out[1])
 
 
+def test_t5_engine_rejects_ids_outside_the_table_and_misshapen_tables():
+    """An id outside [0, vocab) would make t5_gather_kernel read outside the embedding table: T5Engine.encode raises before any
+    launch (nothing faults); load_state_dict checks the two tables the kernels index by ids and by buckets."""
+    from mmpl_amd.synthetic import T5_CONFIGS, t5_state_dict
+    from mmpl_amd.t5 import T5Engine
+    cfg = T5_CONFIGS["tiny"]
+    sd = t5_state_dict(cfg, seed=4)
+    L = 64
+    eng = T5Engine(cfg, text_len=L, device="cuda:0")
+    eng.load_state_dict(sd)
+    mask = torch.ones(1, L, dtype=torch.long)
+    ids = torch.randint(0, cfg["vocab"], (1, L), generator=torch.Generator().manual_seed(1))
+    ids[0, :2] = torch.tensor([0, cfg["vocab"] - 1])               # both ends of the table are fine
+    out = eng.encode(ids, mask)
+    torch.cuda.synchronize()
+    for bad in (cfg["vocab"], -1, 1 << 30):
+        ids2 = ids.clone()
+        ids2[0, L - 1] = bad
+        with pytest.raises(ValueError, match="token ids"):
+            eng.encode(ids2, mask)
+        with pytest.raises(ValueError, match="token ids"):         # also under the mask: the gather reads every row
+            eng.encode(ids2, torch.zeros_like(mask))
+    assert torch.equal(eng.encode(ids, mask), out)                 # the engine is as usable as before
+    short = dict(sd)
+    short["token_embedding.weight"] = sd["token_embedding.weight"][:-1]
+    with pytest.raises(ValueError, match="token_embedding"):
+        T5Engine(cfg, text_len=L, device="cuda:0").load_state_dict(short)
+    wide = dict(sd)
+    k = "blocks.0.pos_embedding.embedding.weight"
+    wide[k] = sd[k][:, :-1]
+    with pytest.raises(ValueError, match="pos_embedding"):
+        T5Engine(cfg, text_len=L, device="cuda:0").load_state_dict(wide)
+
+
 def test_wan_text_encoder_seam():
     """WanTextEncoder(text_prompts) -> {'prompt_embeds'} through tokenizer -> HIP engine (wan_wrapper.py:15-51)."""
     from mmpl_amd.synthetic import T5_CONFIGS, t5_state_dict

@@ -31,23 +31,32 @@ def test_unipc_trajectory_matches_reference_golden():
 
 
 def test_unipc_single_steps_bit_level():
-    """Feed the reference trajectory's own states: each fused step must land within 1 bf16 ulp of the oracle step."""
+    """Feed the reference trajectory's own states: each fused step must land within 1 bf16 ulp of the oracle step, and must equal
+    the bit-level emulation of the kernel's chain (tests/test_scheduler_host.py: emulate_kernel) fed the same states, in every bit
+    of x, m0, m1 and last_sample: every operation of the chain is one IEEE fp32 operation between two bf16 roundings."""
     from mmpl_amd.scheduler import FlowUniPCMultistepScheduler
     from mmpl_amd.synthetic import philox_normal
     from oracle.unipc_ref import FlowUniPCRef
+    from tests.test_scheduler_host import emulate_kernel
     shape = [1, 7, 16, 12, 20]
     o = FlowUniPCRef(1000, 2, 1.0, gpu_scalar_semantics=True)   # the HIP step follows PyTorch's GPU scalar rule
     o.set_timesteps(50, shift=5.0)
     s = FlowUniPCMultistepScheduler(1000, 2, 1.0)
     s.set_timesteps(50, shift=5.0)
+    s2 = FlowUniPCMultistepScheduler(1000, 2, 1.0)              # the same scalars, step by step, for the emulation
+    s2.set_timesteps(50, shift=5.0)
     x = philox_normal(shape, 1, BF)
     xg = x.clone().cuda()
     bad = 0.0
     for i in range(50):
         fc, fu = philox_normal(shape, 100 + i, BF), philox_normal(shape, 200 + i, BF)
         flow = fu + 5.0 * (fc - fu)
+        before = [xg.cpu()] + ([t.cpu() for t in s._state] if s._state is not None else [torch.zeros_like(x)] * 3)
         x = o.step(flow, x)
         xg = s.step_cfg(fc.cuda(), fu.cuda(), 5.0, xg)
+        want = emulate_kernel(s2.step_scalars(5.0), fc, fu, *before)
+        for name, got, w in zip(("x", "m0", "m1", "last_sample"), [xg] + list(s._state), want):
+            assert torch.equal(got.cpu().view(torch.int16), w.view(torch.int16)), (i, name)
         bad = max(bad, bf16_ulp_frac(xg, x, 1))
         xg = x.clone().cuda()                     # re-sync so errors do not compound across steps
         s._state[0].copy_(o.model_outputs[-1])
