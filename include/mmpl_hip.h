@@ -238,6 +238,31 @@ int mmpl_cfg_unipc_step_table(const void* flow_cond, const void* flow_uncond, vo
                               size_t n, const MmplUniPCStep* table_dev, int* step_dev, float* timestep_dev,
                               const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream);
 
+/* CFG combine + FlowDPMSolverMultistepScheduler.step (sample_solver = 'dpm++': casual_fps_inference.py:366-374,
+ * wan/utils/fm_solvers.py:706-797 as the pipeline configures it: DPM-Solver++(2M), midpoint, flow_prediction, final sigma 0).
+ * Per element of n bf16 values, rbf = round to bf16, every other operation one IEEE fp32 operation (DESIGN.md "DPM-Solver++"):
+ *   f  = rbf(fu + rbf(guidance * rbf(fc - fu)))                    (fc when flow_uncond is NULL)
+ *   x0 = rbf(x - rbf(sigma_cur * f));  m1 <- m0;  m0 <- x0
+ *   order 1:  x <- rbf(c1 * x - rbf(c2 * m0))
+ *   order 2:  d1 = rbf(inv_r0 * rbf(m0 - m1));  x <- rbf((c1 * x - rbf(c2 * m0)) - rbf((0.5f * c2) * d1))
+ * The scalars are finite on every step of a schedule (mmpl_amd/scheduler.py computes them); order is 1 or 2. */
+typedef struct MmplDpmppStep {
+  float guidance, sigma_cur;
+  int order;
+  float c1, c2, inv_r0;
+} MmplDpmppStep;
+/* flow_cond, x, m0, m1: dev bf16 [n], none of them NULL (rejected before the launch); flow_uncond NULL = flow_cond is already the
+ * combined flow.  16 bytes per lane when every pointer is 16-byte aligned, element-wise otherwise. */
+int mmpl_cfg_dpmpp_step(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, size_t n,
+                        const MmplDpmppStep* s, mmpl_stream_t stream);
+/* Device-resident form, the protocol of mmpl_cfg_unipc_step_table: the scalars of step *step_dev are read from
+ * table_dev[*step_dev] (n_steps entries, device memory), then *step_dev += 1 and the next step's timestep
+ * (timestep_table_dev[*step_dev]) is written to timestep_dev[0..n_timestep).  Once *step_dev has reached n_steps a launch changes
+ * nothing. */
+int mmpl_cfg_dpmpp_step_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, size_t n,
+                              const MmplDpmppStep* table_dev, int* step_dev, float* timestep_dev,
+                              const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream);
+
 /* Few-step (Self-Forcing / CausVid) latent update of CausalInferencePipeline.inference (pipeline/causal_inference.py:176-197):
  * WanDiffusionWrapper._convert_flow_pred_to_x0 (utils/wan_wrapper.py:172-199) then FlowMatchScheduler.add_noise
  * (utils/scheduler.py:160-176), per element of n bf16 values:

@@ -89,6 +89,15 @@ def preview_refusal(args):
     return None
 
 
+def solver_refusal(args, fewstep: bool):
+    """Why --sample_solver cannot run this command line (None = it can): the multistep solvers (UniPC, DPM-Solver++) sample the
+    50-step pipeline; a few-step config walks its own denoising_step_list and has no solver to choose."""
+    if fewstep and getattr(args, "sample_solver", "unipc") != "unipc":
+        return (f"--sample_solver {args.sample_solver}: the few-step pipeline (config with denoising_step_list) follows its "
+                "denoising_step_list and has no multistep solver; drop --sample_solver or use a 50-step config")
+    return None
+
+
 def build_preview_vae(args, dev, geo):
     """TAEHVWrapper for --preview_vae [PATH]: the checkpoint at PATH (default ../wan_models/taew2_1.pth), or seeded weights with --synthetic."""
     from .wan_wrapper import TAEHVWrapper
@@ -150,6 +159,9 @@ def main(argv=None):
     ap.add_argument("--model", default="14B", choices=list(WAN_CONFIGS))
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights / text embeddings (no checkpoints needed)")
     ap.add_argument("--sampling_steps", type=int, default=50)
+    ap.add_argument("--sample_solver", default="unipc", choices=["unipc", "dpm++"],
+                    help="the multistep solver of the 50-step pipeline: FlowUniPCMultistepScheduler or FlowDPMSolverMultistepScheduler "
+                         "(DPM-Solver++(2M)), as in Wan2.1's generate.py")
     ap.add_argument("--latent_hw", type=int, nargs=2, default=None, help="override the latent size (tests)")
     ap.add_argument("--cfg_split", action="store_true",
                     help="multi-GPU: WORLD/2 chunk lanes x (cond, uncond) rank pairs -- the reference's device_cond/device_uncond "
@@ -185,6 +197,9 @@ def main(argv=None):
     why = rolling_refusal(args, fewstep)
     if why is not None:
         ap.error(why)
+    why = solver_refusal(args, fewstep)
+    if why is not None:
+        ap.error(why)
     if fewstep:
         why = fewstep_refusal(args, world)
         if why is not None:
@@ -209,6 +224,7 @@ def main(argv=None):
     if fewstep:
         return _main_fewstep(config, args, dev, geo, mcfg)
     config.sampling_steps = args.sampling_steps
+    config.sample_solver = args.sample_solver
     clip = None
     if args.i2v_model:
         if not (args.i2v and args.image):

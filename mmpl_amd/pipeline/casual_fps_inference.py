@@ -6,7 +6,8 @@ Same constructor / ``inference()`` signature, attributes (``generator_cond``, ``
 underneath, MI355X-first:
   * one DiT forward = one C call (``mmpl_dit_forward``), K/V read in place through the slot table -- no gather copies,
     no host syncs inside a forward;
-  * CFG + UniPC = one fused kernel per step (``mmpl_cfg_unipc_step``); with hipGraphs on, a whole denoise step (both
+  * CFG + UniPC = one fused kernel per step (``mmpl_cfg_unipc_step``; ``mmpl_cfg_dpmpp_step`` with
+    ``sample_solver = 'dpm++'``, the reference's other solver); with hipGraphs on, a whole denoise step (both
     forwards + that kernel, its scalars and the next timestep read from device tables) is ONE graph replayed 50 times;
   * nothing is shuffled to the CPU (T5 / VAE stay resident: 288 GB HBM);
   * the literals 1560 / 40x128 / 40 blocks are derived from a ``Geometry`` and the model config;
@@ -24,7 +25,8 @@ from typing import Callable, List, Optional
 import torch
 
 from ..geometry import Geometry
-from ..scheduler import FlowUniPCMultistepScheduler
+from ..scheduler import (FlowDPMSolverMultistepScheduler, FlowUniPCMultistepScheduler, get_sampling_sigmas,
+                         retrieve_timesteps)
 from ..stage_plan import StagePlan
 from ..wan_wrapper import WanFPSWrapper, WanTextEncoder, WanVAEWrapper
 
@@ -49,7 +51,7 @@ class CausalFPSInferencePipeline(torch.nn.Module):
 
         self.num_train_timesteps = args.num_train_timestep
         self.sampling_steps = getattr(args, "sampling_steps", 50)
-        self.sample_solver = "unipc"
+        self.sample_solver = getattr(args, "sample_solver", "unipc")     # 'unipc' | 'dpm++' (casual_fps_inference.py:503-523)
         self.shift = args.timestep_shift
         self.num_transformer_blocks = self.generator_cond.engine.L
         self.frame_seq_length = self.geometry.frame_seqlen
@@ -312,7 +314,14 @@ class CausalFPSInferencePipeline(torch.nn.Module):
         return video
 
     def _initialize_sample_scheduler(self, noise):
-        s = FlowUniPCMultistepScheduler(num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
-        s.set_timesteps(self.sampling_steps, device=noise.device, shift=self.shift)
-        self.timesteps = s.timesteps
+        """casual_fps_inference.py:503-524.  Both classes offer the same device-facing interface (mmpl_amd/scheduler.py)."""
+        if self.sample_solver == "unipc":
+            s = FlowUniPCMultistepScheduler(num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
+            s.set_timesteps(self.sampling_steps, device=noise.device, shift=self.shift)
+            self.timesteps = s.timesteps
+        elif self.sample_solver == "dpm++":
+            s = FlowDPMSolverMultistepScheduler(num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
+            self.timesteps, _ = retrieve_timesteps(s, device=noise.device, sigmas=get_sampling_sigmas(self.sampling_steps, self.shift))
+        else:
+            raise NotImplementedError("Unsupported solver.")
         return s

@@ -8,6 +8,10 @@ rho coefficients -- a handful of fp32 values) are computed on the host exactly a
 them, and the whole tensor update (CFG combine, x0 conversion, UniC corrector, UniP predictor, solver-state
 rotation) is ONE fused HIP kernel (``mmpl_cfg_unipc_step``) instead of ~25 tiny PyTorch launches.
 
+``FlowDPMSolverMultistepScheduler`` (with ``get_sampling_sigmas`` / ``retrieve_timesteps``) is the reference's other solver,
+``sample_solver = 'dpm++'`` (MMPL_t2v/wan/utils/fm_solvers.py as configured by pipeline/casual_fps_inference.py:512-521), split the
+same way around ``mmpl_cfg_dpmpp_step`` and with the same device-facing interface, so the stage loop drives either object.
+
 ``FlowMatchScheduler`` is the train-time schedule the pipeline uses for ``add_noise``
 (MMPL_t2v/utils/scheduler.py:103-176).
 """
@@ -192,6 +196,184 @@ class FlowUniPCMultistepScheduler:
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
         """Reference call shape (fm_solvers_unipc.py:655).  `timestep` is accepted and ignored like the reference's
+        internal step counter does after the first call."""
+        out = self.step_cfg(model_output.contiguous(), None, 0.0, sample.contiguous().clone())
+        return (out,) if not return_dict else {"prev_sample": out}
+
+
+def get_sampling_sigmas(sampling_steps: int, shift: float) -> np.ndarray:
+    """fm_solvers.py:22-26: the shifted sigmas of a `sampling_steps`-step schedule from 1 down (fp64, without the trailing 0)."""
+    sigma = np.linspace(1, 0, sampling_steps + 1)[:sampling_steps]
+    return shift * sigma / (1 + (shift - 1) * sigma)
+
+
+def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, timesteps=None, sigmas=None, **kwargs):
+    """fm_solvers.py:29-66 for the one form the pipeline uses: custom `sigmas`.  -> (timesteps, number of steps).  `device` is
+    passed on and ignored there: the timesteps stay on the host."""
+    if timesteps is not None:
+        raise ValueError("retrieve_timesteps: custom `timesteps` are not supported, pass `sigmas`")
+    if sigmas is None:
+        raise ValueError("retrieve_timesteps: pass `sigmas` (get_sampling_sigmas(steps, shift))")
+    scheduler.set_timesteps(sigmas=sigmas, device=device, **kwargs)
+    return scheduler.timesteps, len(scheduler.timesteps)
+
+
+class FlowDPMSolverMultistepScheduler:
+    """DPM-Solver++(2M) for flow matching: the reference's second sampler (MMPL_t2v/wan/utils/fm_solvers.py:69-797) in the one
+    configuration its pipeline builds (pipeline/casual_fps_inference.py:512-521: order 2, dpmsolver++, midpoint, flow_prediction,
+    final sigma 0, no thresholding, config shift 1 with the schedule's shift applied by `get_sampling_sigmas`).  Every other
+    constructor value raises.
+
+    Split like the UniPC class above: the per-step scalars (sigma ratio, alpha_t (exp(-h) - 1), 1 / r0) are computed on the host with
+    the reference's own torch fp32 0-dim tensor operations, the tensor update (CFG combine, x0 conversion, history rotation, first /
+    second order update) is ONE fused HIP kernel (``mmpl_cfg_dpmpp_step``), and the device-facing interface is the UniPC class's, so
+    the stage loop drives either object.  The solver state is two bf16 tensors (m0, m1); there is no corrector and no last sample."""
+    order = 1
+    _SUPPORTED = dict(solver_order=2, prediction_type="flow_prediction", shift=1.0, use_dynamic_shifting=False, thresholding=False,
+                      algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, euler_at_final=False,
+                      final_sigmas_type="zero", lambda_min_clipped=-float("inf"), variance_type=None, invert_sigmas=False)
+
+    def __init__(self, num_train_timesteps: int = 1000, solver_order: int = 2, prediction_type: str = "flow_prediction",
+                 shift: Optional[float] = 1.0, use_dynamic_shifting: bool = False, thresholding: bool = False,
+                 dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0, algorithm_type: str = "dpmsolver++",
+                 solver_type: str = "midpoint", lower_order_final: bool = True, euler_at_final: bool = False,
+                 final_sigmas_type: Optional[str] = "zero", lambda_min_clipped: float = -float("inf"),
+                 variance_type: Optional[str] = None, invert_sigmas: bool = False):
+        given = dict(solver_order=solver_order, prediction_type=prediction_type, shift=shift, use_dynamic_shifting=use_dynamic_shifting,
+                     thresholding=thresholding, algorithm_type=algorithm_type, solver_type=solver_type,
+                     lower_order_final=lower_order_final, euler_at_final=euler_at_final, final_sigmas_type=final_sigmas_type,
+                     lambda_min_clipped=lambda_min_clipped, variance_type=variance_type, invert_sigmas=invert_sigmas)
+        for k, v in given.items():                    # (the two thresholding parameters have no effect without thresholding)
+            if v != self._SUPPORTED[k]:
+                raise NotImplementedError(f"FlowDPMSolverMultistepScheduler: {k}={v!r} is not supported (only {self._SUPPORTED[k]!r}: "
+                                          "the configuration the pipeline builds)")
+        self.num_train_timesteps = num_train_timesteps
+        self.solver_order = solver_order
+        alphas = np.linspace(1, 1 / num_train_timesteps, num_train_timesteps)[::-1].copy()
+        self.sigmas = torch.from_numpy(1.0 - alphas).to(dtype=torch.float32)         # shift 1: unchanged
+        self.sigma_min = self.sigmas[-1].item()
+        self.sigma_max = self.sigmas[0].item()
+        self.timesteps = self.sigmas * num_train_timesteps
+        self.num_inference_steps = None
+        self.step_index = 0
+        self._state = None
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, sigmas=None, mu=None, shift: Optional[float] = None):
+        """fm_solvers.py:226-287.  `sigmas` (fp64, from get_sampling_sigmas: already shifted) are taken as they are -- the config's
+        shift is 1; without them the schedule is the linear one from sigma_max to sigma_min under `shift`.  `device` is accepted for
+        the reference's call shape and ignored: `sigmas` and `timesteps` stay on the host (as in the UniPC class above), the stage
+        loop reads them there without a device sync."""
+        if mu is not None:
+            raise NotImplementedError("FlowDPMSolverMultistepScheduler: dynamic shifting (mu) is not supported")
+        if sigmas is None:
+            if num_inference_steps is None:
+                raise ValueError("set_timesteps: pass num_inference_steps or sigmas")
+            sigmas = np.linspace(self.sigma_max, self.sigma_min, num_inference_steps + 1).copy()[:-1]
+        sigmas = np.asarray(sigmas, dtype=np.float64)
+        if shift is None:
+            shift = 1.0
+        sigmas = shift * sigmas / (1 + (shift - 1) * sigmas)
+        timesteps = sigmas * self.num_train_timesteps
+        sigmas = np.concatenate([sigmas, [0]]).astype(np.float32)
+        self.sigmas = torch.from_numpy(sigmas)                       # stays on the host, like the reference
+        self.timesteps = torch.from_numpy(timesteps).to(dtype=torch.int64)      # truncated: the first one is 1000
+        self.num_inference_steps = len(timesteps)
+        self.step_index = 0
+        self._state = None
+
+    # -- host scalars ------------------------------------------------------------------------------
+    @staticmethod
+    def _lam(sigma):
+        return torch.log(1 - sigma) - torch.log(sigma)
+
+    def step_scalars(self, guidance: float) -> _lib.MmplDpmppStep:
+        """Scalars of the step at the current step_index (fm_solvers.py:457-468, 529-553, 746-783), then step_index += 1.
+        The reference's own fp32 0-dim tensor operations, so the values are its bits; its three infinities stay on the host:
+          step 0      sigma_s0 = 1: lambda_s0 = -inf, h = +inf, exp(-h) = 0                 -> c2 = -(1 - sigma_t)
+          step 1      lambda_s1 = -inf: h_0 = +inf, r0 = +inf                               -> inv_r0 = 0 (D1 = +-0)
+          last step   sigma_t = 0: lambda_t = +inf, h = +inf, c1 = 0                        -> c2 = -1: the result is m0
+        Order: 1 on the first step (no history) and on the last (final sigma 0), else 2; with solver order 2 the reference's
+        `lower_order_second` selects the branch that is taken anyway."""
+        i, n = self.step_index, len(self.timesteps)
+        if i >= n:
+            raise IndexError(f"FlowDPMSolverMultistepScheduler: step {i} of a {n}-step schedule")
+        sigma_t, sigma_s0 = self.sigmas[i + 1], self.sigmas[i]
+        alpha_t = 1 - sigma_t
+        lambda_t, lambda_s0 = self._lam(sigma_t), self._lam(sigma_s0)
+        h = lambda_t - lambda_s0
+        st = _lib.MmplDpmppStep()
+        st.guidance = float(guidance)
+        st.sigma_cur = sigma_s0.item()
+        st.order = 1 if i == 0 or i == n - 1 else 2
+        st.c1 = (sigma_t / sigma_s0).item()
+        st.c2 = (alpha_t * (torch.exp(-h) - 1.0)).item()
+        st.inv_r0 = 0.0
+        if st.order == 2:
+            h_0 = lambda_s0 - self._lam(self.sigmas[i - 1])
+            st.inv_r0 = (1.0 / (h_0 / h)).item()
+        if not all(np.isfinite(v) for v in (st.sigma_cur, st.c1, st.c2, st.inv_r0)):
+            raise FloatingPointError(f"FlowDPMSolverMultistepScheduler: non-finite scalar at step {i}: "
+                                     f"c1={st.c1} c2={st.c2} inv_r0={st.inv_r0}")
+        self.step_index += 1
+        return st
+
+    # -- device update -----------------------------------------------------------------------------
+    def _ensure_state(self, sample: torch.Tensor):
+        if self._state is None or self._state[0].shape != sample.shape or self._state[0].device != sample.device:
+            self._state = [torch.zeros_like(sample) for _ in range(2)]      # m0, m1
+
+    def step_cfg(self, flow_cond: torch.Tensor, flow_uncond: Optional[torch.Tensor], guidance: float,
+                 sample: torch.Tensor) -> torch.Tensor:
+        """CFG combine + scheduler step, fused; `sample` is updated in place and returned."""
+        assert sample.is_contiguous() and sample.dtype == torch.bfloat16 and flow_cond.is_contiguous()
+        self._ensure_state(sample)
+        st = self.step_scalars(guidance)
+        m0, m1 = self._state
+        _lib.check(_lib.load().mmpl_cfg_dpmpp_step(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
+                                                   _lib.ptr(m1), sample.numel(), C.byref(st), _lib.stream_ptr()),
+                   "mmpl_cfg_dpmpp_step")
+        return sample
+
+    # -- device-resident step table: the protocol of FlowUniPCMultistepScheduler.build_step_table ---------------------
+    def build_step_table(self, guidance: float, device) -> None:
+        """Upload the scalars and the timestep of every remaining step; `step_cfg_table` reads entry *counter on the device.  The
+        host-side step_index of THIS object is not advanced (the scalars come from a copy)."""
+        import copy
+        probe = copy.copy(self)
+        probe._state = None
+        n = len(self.timesteps) - self.step_index
+        rows = (_lib.MmplDpmppStep * n)()
+        for i in range(n):
+            rows[i] = probe.step_scalars(guidance)
+        raw = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).clone()
+        self._table = raw.to(device)
+        t_host = [float(t) for t in self.timesteps[self.step_index:]]
+        self._t_table = torch.tensor(t_host, dtype=torch.float32, device=device)
+        self._t_first = t_host[0]          # host copy: reset_step_table must not read the device table (a sync inside timed loops)
+        self._counter = torch.zeros(1, dtype=torch.int32, device=device)
+        self._table_n = n
+
+    def reset_step_table(self, timestep: torch.Tensor) -> None:
+        """Rewind the device step counter, the solver history and `timestep` to the first entry of the uploaded table."""
+        self._counter.zero_()
+        if self._state is not None:
+            for t in self._state:
+                t.zero_()
+        timestep.fill_(self._t_first)
+
+    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor) -> None:
+        """CFG combine + scheduler step with device-resident scalars (capturable: no host value enters the launch);
+        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous)."""
+        assert sample.is_contiguous() and sample.dtype == torch.bfloat16 and timestep.dtype == torch.float32 and timestep.is_contiguous()
+        self._ensure_state(sample)
+        m0, m1 = self._state
+        _lib.check(_lib.load().mmpl_cfg_dpmpp_step_table(
+            _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), sample.numel(),
+            _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep), _lib.ptr(self._t_table), timestep.numel(), self._table_n,
+            _lib.stream_ptr()), "mmpl_cfg_dpmpp_step_table")
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
+        """Reference call shape (fm_solvers.py:706).  `timestep` is accepted and ignored: the steps are counted, as the reference's
         internal step counter does after the first call."""
         out = self.step_cfg(model_output.contiguous(), None, 0.0, sample.contiguous().clone())
         return (out,) if not return_dict else {"prev_sample": out}

@@ -209,6 +209,34 @@ def bench_elem(iters):
             gb = 4.0 * rows * d * 2 / 1e9
             print(f"elem {model} qknorm+rope+kwrite rows={rows} d={d}  {ms * 1e3:8.1f} us  {gb / ms:6.2f} TB/s  sha {h}", flush=True)
             del qkv, qkv0, kc, x, y
+    bench_solver_steps(iters)
+
+
+def bench_solver_steps(iters):
+    """the two fused CFG + solver updates side by side at the same n, alternating (3 rounds, the best of each): mmpl_cfg_unipc_step
+    (6 reads + 4 writes per element at a second-order step with the corrector) and mmpl_cfg_dpmpp_step (4 reads + 3 writes at a
+    second-order step).  n = the largest stage of 720p (7 frames x 16 x 90 x 160) and 2^26 elements (HBM-bound)."""
+    from mmpl_amd.scheduler import FlowDPMSolverMultistepScheduler, FlowUniPCMultistepScheduler, get_sampling_sigmas, retrieve_timesteps
+    u = FlowUniPCMultistepScheduler(1000, 2, 1.0)
+    u.set_timesteps(50, shift=5.0)
+    su = [u.step_scalars(5.0) for _ in range(26)][25]
+    d = FlowDPMSolverMultistepScheduler(num_train_timesteps=1000, shift=1, use_dynamic_shifting=False)
+    retrieve_timesteps(d, sigmas=get_sampling_sigmas(50, 5.0))
+    sd = [d.step_scalars(5.0) for _ in range(26)][25]
+    assert su.use_corrector and su.corr_order == 2 and su.pred_order == 2 and sd.order == 2
+    for n in (7 * 16 * 90 * 160, 1 << 26):
+        torch.manual_seed(1)
+        t = [torch.randn(n, device=dev).to(BF) for _ in range(6)]
+        fu_ = lambda: _lib.check(lib.mmpl_cfg_unipc_step(*[_lib.ptr(b) for b in t], n, C.byref(su), _lib.stream_ptr()))
+        fd_ = lambda: _lib.check(lib.mmpl_cfg_dpmpp_step(*[_lib.ptr(b) for b in t[:5]], n, C.byref(sd), _lib.stream_ptr()))
+        best = {"unipc": float("inf"), "dpm++": float("inf")}
+        for _ in range(3):
+            best["unipc"] = min(best["unipc"], timeit(fu_, iters))
+            best["dpm++"] = min(best["dpm++"], timeit(fd_, iters))
+        for name, passes in (("unipc", 10), ("dpm++", 7)):
+            ms = best[name]
+            print(f"elem cfg+{name} step n={n}  {ms * 1e3:8.1f} us  {passes * n * 2 / 1e9 / ms:6.2f} TB/s", flush=True)
+        del t
 
 
 def bench_cross(iters):
