@@ -129,6 +129,11 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int n_
                         void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
                         mmpl_stream_t stream);
 size_t mmpl_dit_attn_history_bytes(const MmplDit* h, int n_frames);
+/* The handle's RoPE tables (mmpl_dit_create: cos / sin of position * theta^(-2j / dims), theta 1e4, dims 44 | 42 | 42 of the 128-wide
+ * head, computed in double and stored as float32), for tests and tools that make the forward's QK-norm launch themselves
+ * (mmpl_qknorm_ex): copies the two [1024][64] float32 tables into the caller's device buffers cos_out / sin_out (256 KiB each),
+ * asynchronously on `stream`.  A null argument is rejected before the first HIP call. */
+int mmpl_dit_rope_tables(const MmplDit* h, float* cos_out, float* sin_out, mmpl_stream_t stream);
 /* MMPL_CHECK_SHARE=1: number of share_in forwards (eager or replayed) since the last call whose layer-0 K / V fingerprint differed
  * from their share_out forward's; synchronises `stream` and resets the count.  0 when the switch is off. */
 int mmpl_dit_share_check_failures(MmplDit* h, long long* count, mmpl_stream_t stream);

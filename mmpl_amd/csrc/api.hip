@@ -592,6 +592,14 @@ size_t mmpl_dit_attn_history_bytes(const MmplDit* h, int n_frames) {
 }
 size_t mmpl_attn_history_bytes(int Lq, int num_heads) { return mmpl_attention_history_bytes(Lq, num_heads); }
 
+int mmpl_dit_rope_tables(const MmplDit* h, float* cos_out, float* sin_out, mmpl_stream_t stream) {
+  if (!h || !cos_out || !sin_out) return fail("mmpl_dit_rope_tables", "null argument");
+  const size_t bytes = (size_t)1024 * 64 * sizeof(float);
+  HIP_TRY(hipMemcpyAsync(cos_out, h->cos_tab, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "mmpl_dit_rope_tables");
+  HIP_TRY(hipMemcpyAsync(sin_out, h->sin_tab, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "mmpl_dit_rope_tables");
+  return 0;
+}
+
 int mmpl_attn_fwd_history(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
                           int ldk, int ldv, int n_pages, int page_rows, int Lq, int num_heads, float softmax_scale,
                           void* workspace, size_t workspace_bytes, void* history, void* stats_dev, mmpl_stream_t stream) {

@@ -62,6 +62,7 @@ def test_signatures_follow_header():
     fwd = [vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, sz]
     table = {
         "mmpl_dit_workspace_bytes": (sz, [vp, ci]),
+        "mmpl_dit_rope_tables": (ci, [vp, vp, vp, vp]),
         "mmpl_dit_destroy": (None, [vp]),
         "mmpl_dit_weight_name": (ctypes.c_char_p, [ci, ci]),
         "mmpl_last_error": (ctypes.c_char_p, []),
