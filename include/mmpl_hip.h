@@ -129,6 +129,28 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int n_
                         void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
                         mmpl_stream_t stream);
 size_t mmpl_dit_attn_history_bytes(const MmplDit* h, int n_frames);
+/* The non-causal WanModel.forward (model.py, behind WanDiffusionWrapper(is_causal=False).forward, utils/wan_wrapper.py) over a WHOLE
+ * clip: the blocks of mmpl_dit_forward with frame i rotated at temporal position i, every frame attending to every frame, and no
+ * KV cache -- the K and V of the layer being computed live in the workspace as one contiguous [n_frames * S, dim] pair that every
+ * layer reuses (a persistent per-layer cache of a 21-frame 14B / 720p clip would be 40 x 75 600 x 5 120 x 2 B = 31 GB per tensor).
+ *   x_in / out : as mmpl_dit_forward
+ *   t_dev      : dev, ONE float32: the clip's timestep, read when the forward executes.  Its embedding and the modulation vectors
+ *                derived from it are computed once and read by every frame; the bits are those of mmpl_dit_forward given the same
+ *                timestep in every frame.
+ *   n_frames   : 1 .. 24, independent of cfg.max_frames (which stays the largest stage of mmpl_dit_forward)
+ *   cross_k / cross_v / cross_rows / share_out / share_in / attn_history: the contracts of mmpl_dit_forward (attn_history is
+ *                mmpl_dit_attn_history_bytes(h, n_frames) bytes; with no cache there is no layer-0 K / V to differ between the two
+ *                CFG branches, so share_in needs only the same x_in and timestep)
+ *   workspace  : dev, 256-byte aligned, at least mmpl_dit_full_workspace_bytes(h, n_frames) bytes (0 for an n_frames out of range):
+ *                [GEMM tickets | x | LayerNorm out | qkv or ffn hidden | attention out | K | V | patches | timestep embedding,
+ *                modulation vectors (one row each) | head out | split-K partials]
+ * Equal, bit for bit, to mmpl_dit_forward on a zeroed cache with frame_ids = write_slots = visible_slots = 0 .. n_frames-1.
+ * No allocation, no synchronisation and no host read: capturable into a hipGraph.  A null pointer, an n_frames outside 1 .. 24, a
+ * workspace that is too small, both share_* set or a handle without weights are rejected before the first launch. */
+size_t mmpl_dit_full_workspace_bytes(const MmplDit* h, int n_frames);
+int mmpl_dit_forward_full(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const void* cross_k, const void* cross_v,
+                          int cross_rows, void* share_out, const void* share_in, void* attn_history, void* out, void* workspace,
+                          size_t workspace_bytes, mmpl_stream_t stream);
 /* The handle's RoPE tables (mmpl_dit_create: cos / sin of position * theta^(-2j / dims), theta 1e4, dims 44 | 42 | 42 of the 128-wide
  * head, computed in double and stored as float32), for tests and tools that make the forward's QK-norm launch themselves
  * (mmpl_qknorm_ex): copies the two [1024][64] float32 tables into the caller's device buffers cos_out / sin_out (256 KiB each),

@@ -6,7 +6,8 @@
 
 Single process = the reference's sequential rollout (chunk k+1 starts from the last 5 pixel frames of chunk k,
 `Wan_fps_inference_1gpu.py:164-203`); several processes = the parallel scripts' wavefront (chunk c on rank c mod W,
-anchors handed over right after the anchor stage).  `--synthetic` runs without checkpoints (seeded weights and text
+anchors handed over right after the anchor stage).  `--bidirectional` = plain Wan2.1 T2V instead: one whole clip per call
+(the reference's Bidirectional*InferencePipeline).  `--synthetic` runs without checkpoints (seeded weights and text
 embeddings) -- the only mode that can run in this repo's test environments.  Output: per prompt a uint8 tensor
 `[T, H, W, 3]` saved with torch.save (mp4 muxing via torchvision is outside the hot path; fps = 16).
 """
@@ -41,10 +42,40 @@ def is_fewstep(config) -> bool:
     return hasattr(config, "denoising_step_list")
 
 
-def pipeline_class(config):
-    """The pipeline the reference's entry script builds for `config` (Wan_fps_inference_1gpu.py:59-64)."""
-    from .pipeline import CausalFPSInferencePipeline, CausalInferencePipeline
+def pipeline_class(config, bidirectional: bool = False):
+    """The pipeline the reference's entry script builds for `config` (Wan_fps_inference_1gpu.py:59-64); with --bidirectional the
+    whole-clip counterpart of either (pipeline/__init__.py of the reference)."""
+    from .pipeline import (BidirectionalDiffusionInferencePipeline, BidirectionalInferencePipeline, CausalFPSInferencePipeline,
+                           CausalInferencePipeline)
+    if bidirectional:
+        return BidirectionalInferencePipeline if is_fewstep(config) else BidirectionalDiffusionInferencePipeline
     return CausalInferencePipeline if is_fewstep(config) else CausalFPSInferencePipeline
+
+
+def bidirectional_refusal(args, world: int):
+    """Why --bidirectional cannot run this command line (None = it can, or it was not asked for).  The bidirectional pipelines
+    denoise ONE whole clip per call with a text-to-video model on one process: there is no chunk rollout, no image conditioning,
+    no block to stream or to roll a KV window over (there is no KV cache), and no second rank to give a CFG branch to."""
+    if not getattr(args, "bidirectional", False):
+        return None
+    if args.duration > 1:
+        return (f"--duration {args.duration}: --bidirectional generates one {args.num_output_frames}-latent-frame clip per call "
+                "(use --duration 1)")
+    if args.i2v or args.i2v_model:
+        return "--i2v: --bidirectional is text-to-video only"
+    if getattr(args, "stream", False):
+        return "--stream: --bidirectional denoises the whole clip at once; there are no blocks to hand out"
+    if getattr(args, "rolling", False):
+        return "--rolling: --bidirectional has no KV cache to roll a window over"
+    if getattr(args, "preview_vae", None) is not None:
+        return "--preview_vae: the tiny preview decoder serves --stream only; --bidirectional decodes with the Wan VAE"
+    if getattr(args, "cfg_split", False):
+        return "--cfg_split: --bidirectional runs both CFG branches on one process"
+    if world > 1:
+        return "--bidirectional runs on one process (WORLD_SIZE 1)"
+    if args.num_output_frames < 1 or args.num_output_frames > 24:
+        return f"--num_output_frames {args.num_output_frames}: the whole-clip forward takes 1 .. 24 latent frames"
+    return None
 
 
 def fewstep_refusal(args, world: int):
@@ -178,6 +209,10 @@ def main(argv=None):
     ap.add_argument("--rolling", action="store_true",
                     help="few-step configs: rolling KV window (evict the oldest frame that is not a sink frame), so that "
                          "--duration N generates N * num_output_frames latent frames in ONE call, with --stream as well")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="plain (non-causal) Wan2.1 T2V: the whole --num_output_frames clip per forward, every frame attending to "
+                         "every frame -- BidirectionalDiffusionInferencePipeline (--sampling_steps CFG steps of --sample_solver), or "
+                         "BidirectionalInferencePipeline for a few-step config (one with denoising_step_list)")
     ap.add_argument("--local_attn_size", type=int, default=None, help="few-step configs: override model_kwargs.local_attn_size "
                     "(the KV window in latent frames; -1 = 21)")
     ap.add_argument("--sink_size", type=int, default=None, help="few-step configs: override model_kwargs.sink_size (the first "
@@ -188,6 +223,9 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     config = load_config(args.config_path)
     fewstep = is_fewstep(config)
+    why = bidirectional_refusal(args, world)
+    if why is not None:
+        ap.error(why)
     why = stream_refusal(args, fewstep)
     if why is not None:
         ap.error(why)
@@ -200,7 +238,7 @@ def main(argv=None):
     why = solver_refusal(args, fewstep)
     if why is not None:
         ap.error(why)
-    if fewstep:
+    if fewstep and not args.bidirectional:
         why = fewstep_refusal(args, world)
         if why is not None:
             ap.error(why)
@@ -221,6 +259,8 @@ def main(argv=None):
     from .wan_wrapper import SyntheticTextEncoder, WanFPSWrapper, WanVAEWrapper
     geo = Geometry(*args.latent_hw) if args.latent_hw else Geometry.named(args.resolution)
     mcfg = WAN_CONFIGS[args.model]
+    if args.bidirectional:
+        return _main_bidirectional(config, args, dev, geo, mcfg)
     if fewstep:
         return _main_fewstep(config, args, dev, geo, mcfg)
     config.sampling_steps = args.sampling_steps
@@ -382,6 +422,45 @@ def _main_fewstep(config, args, dev, geo, mcfg):
         from .utils.video_io import write_video
         vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)
         print(f"[mmpl_amd.cli] few-step prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
+
+
+def build_bidirectional_pipeline(config, args, dev, geo, mcfg):
+    """WanDiffusionWrapper(is_causal=False) + the bidirectional pipeline `pipeline_class` picks for `config`."""
+    from .wan_wrapper import SyntheticTextEncoder, WanDiffusionWrapper, WanVAEWrapper
+    kw = {k: v for k, v in dict(getattr(config, "model_kwargs", {}) or {}).items() if k in ("model_name", "timestep_shift")}
+    kw.setdefault("model_name", "Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B")
+    gen = WanDiffusionWrapper(**kw, is_causal=False, model_config=mcfg if args.synthetic else None, geometry=geo, device=dev)
+    enc, vae = None, None
+    if args.synthetic:
+        gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
+        enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
+        vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
+    pipe = pipeline_class(config, bidirectional=True)(config, dev, generator=gen, text_encoder=enc, vae=vae)
+    if not is_fewstep(config):
+        pipe.sampling_steps = args.sampling_steps
+        pipe.sample_solver = args.sample_solver
+    if args.checkpoint_path:
+        from .checkpoints import read_mmpl_checkpoint
+        pipe.generator.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
+    return pipe
+
+
+def _main_bidirectional(config, args, dev, geo, mcfg):
+    """--bidirectional: one whole-clip inference() of --num_output_frames latent frames per prompt."""
+    pipe = build_bidirectional_pipeline(config, args, dev, geo, mcfg)
+    os.makedirs(args.output_folder, exist_ok=True)
+    shape = [1, args.num_output_frames, 16, geo.lat_h, geo.lat_w]
+    for idx, prompt in enumerate(_prompts(args)):
+        g = torch.Generator(device="cpu").manual_seed(args.seed)
+        noise = torch.randn(shape, generator=g).to(torch.bfloat16)
+        torch.manual_seed(args.seed)                         # the few-step re-noise draws: the device generator
+        video = pipe.inference(noise.to(dev), [prompt])
+        out = (video * 255.0).clamp(0, 255).to(torch.uint8)[0].permute(0, 2, 3, 1).contiguous().cpu()         # [T, H, W, 3]
+        path = os.path.join(args.output_folder, f"{idx}-0.pt")
+        torch.save(out, path)
+        from .utils.video_io import write_video
+        vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)
+        print(f"[mmpl_amd.cli] bidirectional prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
 
 
 if __name__ == "__main__":

@@ -224,7 +224,10 @@ struct FwdWs {
   float* splitk;         // fp32 partials of the GEMMs' split-K tail launch (mmpl_gemm_splitk_ws_bytes())
   size_t bytes;
 };
-FwdWs carve_fwd(const MmplDit* h, int nF, void* base) {
+// nT: rows of the timestep embedding and of everything derived from it: one per frame (a stage of mmpl_dit_forward), or 1 for
+// mmpl_dit_forward_full, whose clip has ONE timestep that every frame's modulation reads (frame stride 0)
+FwdWs carve_fwd(const MmplDit* h, int nF, void* base, int nT = 0) {
+  if (nT <= 0) nT = nF;
   const MmplDitConfig& c = h->cfg;
   const size_t Lq = (size_t)nF * h->S, d = c.dim;
   const size_t bigw = (size_t)(3 * c.dim > c.ffn_dim ? 3 * c.dim : c.ffn_dim);
@@ -240,13 +243,13 @@ FwdWs carve_fwd(const MmplDit* h, int nF, void* base) {
   w.ksc = k.take(Lq * d);
   w.vsc = k.take(Lq * d);
   w.patch = k.take(Lq * (size_t)h->pe_k);
-  w.sinu = k.take((size_t)nF * c.freq_dim);
-  w.t1 = k.take((size_t)nF * d);
-  w.e = k.take((size_t)nF * d);
-  w.se = k.take((size_t)nF * d);
-  w.e0 = k.take((size_t)nF * 6 * d);
-  w.emod = k.take((size_t)c.num_layers * nF * 6 * d);
-  w.emod_head = k.take((size_t)nF * 2 * d);
+  w.sinu = k.take((size_t)nT * c.freq_dim);
+  w.t1 = k.take((size_t)nT * d);
+  w.e = k.take((size_t)nT * d);
+  w.se = k.take((size_t)nT * d);
+  w.e0 = k.take((size_t)nT * 6 * d);
+  w.emod = k.take((size_t)c.num_layers * nT * 6 * d);
+  w.emod_head = k.take((size_t)nT * 2 * d);
   w.yh = k.take(Lq * 64);
   w.splitk = (float*)k.take(mmpl_gemm_splitk_ws_bytes() / sizeof(bf16_t));
   w.bytes = k.off;
@@ -365,45 +368,52 @@ int mmpl_dit_forward(MmplDit* h, const void* x_in, const float* t_dev, int nF, c
                              cross_v, cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
 }
 
-int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF, const int* frame_ids,
-                        const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
-                        int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
-                        void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
-                        mmpl_stream_t stream) {
-  if (!h || h->w.empty()) return fail("mmpl_dit_forward", "weights not bound");
+// The launches of one forward, for both entries.  full = mmpl_dit_forward_full: the whole clip in one call -- frame i at temporal
+// position i, no cache (frame_ids / write_slots / visible_slots / k_cache / v_cache are NULL, n_visible and n_slots 0: the layer's
+// K / V are the workspace's scratch pair, every frame attends to all of them), n_frames up to MMPL_MAX_PAGES whatever cfg.max_frames,
+// and t_dev is ONE float: the timestep embedding and the modulation vectors are computed for one row and read by every frame
+// through a frame stride of 0 (row i of those GEMMs depends on row i of their input alone, so the bits are the per-frame ones).
+static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_in, const float* t_dev, int nF, const int* frame_ids,
+                           const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
+                           int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
+                           void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                           mmpl_stream_t stream) {
+  if (!h || h->w.empty()) return fail(me, "weights not bound");
   const MmplDitConfig& c = h->cfg;
-  if (nF < 1 || nF > c.max_frames) return fail("mmpl_dit_forward", "n_frames out of range");
+  if (nF < 1 || nF > (full ? MMPL_MAX_PAGES : c.max_frames)) return fail(me, "n_frames out of range");
   int n_write = 0;
-  for (int i = 0; i < nF; ++i) {
-    if (write_slots[i] >= n_slots) return fail("mmpl_dit_forward", "write slot out of range");
+  for (int i = 0; i < nF && !full; ++i) {
+    if (write_slots[i] >= n_slots) return fail(me, "write slot out of range");
     if (write_slots[i] >= 0) ++n_write;
   }
-  if (n_write != 0 && n_write != nF) return fail("mmpl_dit_forward", "write_slots must be all >= 0 or all -1");
-  if (share_out && share_in) return fail("mmpl_dit_forward", "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
+  if (n_write != 0 && n_write != nF) return fail(me, "write_slots must be all >= 0 or all -1");
+  if (share_out && share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
   const bool persist = n_write == nF;
   const int n_pages = n_visible + (persist ? 0 : nF);
-  if (n_pages < 1 || n_pages > MMPL_MAX_PAGES) return fail("mmpl_dit_forward", "too many / no visible KV pages");
+  if (n_pages < 1 || n_pages > MMPL_MAX_PAGES) return fail(me, "too many / no visible KV pages");
   for (int i = 0; i < n_visible; ++i)
-    if (visible_slots[i] < 0 || visible_slots[i] >= n_slots) return fail("mmpl_dit_forward", "visible slot out of range");
-  FwdWs w = carve_fwd(h, nF, workspace);
-  if (workspace_bytes < w.bytes) return fail("mmpl_dit_forward", "workspace too small");
+    if (visible_slots[i] < 0 || visible_slots[i] >= n_slots) return fail(me, "visible slot out of range");
+  const int nT = full ? 1 : nF;                            // timestep rows
+  FwdWs w = carve_fwd(h, nF, workspace, nT);
+  if (workspace_bytes < w.bytes) return fail(me, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int S = h->S, d = c.dim, f = c.ffn_dim, Lq = nF * S, H = c.num_heads, T = c.text_len;
+  const int mfs = full ? 0 : 6 * d, hfs = full ? 0 : 2 * d;   // frame stride of the blocks' / the head's modulation vectors
 
   HIP_TRY(mmpl_launch_zero_ints(w.tile_counter, kTicketInts, s), "tile counter");                  // left zero by every GEMM that uses it
   int* const tc = w.tile_counter;
   // ---- embeddings (causal_fps_model.py:757-776)
   HIP_TRY(mmpl_launch_patchify((const bf16_t*)x_in, w.patch, h->pe_k, nF, c.in_dim, c.lat_h, c.lat_w, s), "patchify");
   TRY(gemm(w.patch, h->pe_k, h->G(G_PE_W), h->pe_k, h->G(G_PE_B), w.x, d, Lq, d, h->pe_k, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-  HIP_TRY(mmpl_launch_sinusoid(t_dev, w.sinu, nF, c.freq_dim, s), "sinusoid");
-  TRY(gemm(w.sinu, c.freq_dim, h->G(G_TE0_W), c.freq_dim, h->G(G_TE0_B), w.t1, d, nF, d, c.freq_dim, EPI_BIAS_SILU, nullptr,
+  HIP_TRY(mmpl_launch_sinusoid(t_dev, w.sinu, nT, c.freq_dim, s), "sinusoid");
+  TRY(gemm(w.sinu, c.freq_dim, h->G(G_TE0_W), c.freq_dim, h->G(G_TE0_B), w.t1, d, nT, d, c.freq_dim, EPI_BIAS_SILU, nullptr,
            0, nullptr, 0, 1, s));
-  TRY(gemm(w.t1, d, h->G(G_TE2_W), d, h->G(G_TE2_B), w.e, d, nF, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-  HIP_TRY(mmpl_launch_silu(w.e, w.se, (size_t)nF * d, s), "silu");
-  TRY(gemm(w.se, d, h->G(G_TP_W), d, h->G(G_TP_B), w.e0, 6 * d, nF, 6 * d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
+  TRY(gemm(w.t1, d, h->G(G_TE2_W), d, h->G(G_TE2_B), w.e, d, nT, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
+  HIP_TRY(mmpl_launch_silu(w.e, w.se, (size_t)nT * d, s), "silu");
+  TRY(gemm(w.se, d, h->G(G_TP_W), d, h->G(G_TP_B), w.e0, 6 * d, nT, 6 * d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
   // e = bf16(modulation + e0) for every layer and for the head (causal_fps_model.py:338, 393)
-  HIP_TRY(mmpl_launch_modulation(h->G(G_BLOCK_MOD), (size_t)6 * d, w.e0, 6 * d, 0, w.emod, c.num_layers, nF, 6, d, s), "modulation");
-  HIP_TRY(mmpl_launch_modulation(h->G(G_HEAD_MOD), 0, w.e, d, 1, w.emod_head, 1, nF, 2, d, s), "head modulation");
+  HIP_TRY(mmpl_launch_modulation(h->G(G_BLOCK_MOD), (size_t)6 * d, w.e0, 6 * d, 0, w.emod, c.num_layers, nT, 6, d, s), "modulation");
+  HIP_TRY(mmpl_launch_modulation(h->G(G_HEAD_MOD), 0, w.e, d, 1, w.emod_head, 1, nT, 2, d, s), "head modulation");
 
   const float scale = 1.0f / sqrtf(128.0f);
   const int self_variant = mmpl_attention_self_variant();
@@ -433,7 +443,7 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
     return 0;
   };
   for (int l = 0; l < c.num_layers; ++l) {
-    const bf16_t* em = w.emod + (size_t)l * nF * 6 * d;  // [nF][6][d]
+    const bf16_t* em = w.emod + (size_t)l * nT * 6 * d;  // [nT][6][d]
     bf16_t* kc = (bf16_t*)k_cache + (size_t)l * layer_stride;
     bf16_t* vc = (bf16_t*)v_cache + (size_t)l * layer_stride;
     // Block 0's self-attention depends on nothing but the latents, the timestep and the cache contents -- none of which differ
@@ -445,7 +455,7 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
     if (!take_shared || persist) {
       // -- self attention (causal_fps_model.py:342-348)
       {
-        LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, em + 1 * d, em + 0 * d, 6 * d, S, nullptr, nullptr};
+        LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, em + 1 * d, em + 0 * d, mfs, S, nullptr, nullptr};
         ProfScope ps(K_LAYERNORM, 0, s);
         HIP_TRY(mmpl_launch_layernorm(a, s), "norm1");
       }
@@ -454,7 +464,13 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
         // causal_fps_model.py:217), so the norm / RoPE pass below only touches q and k
         GemmArgs g{w.xn, d, h->Lw(l, L_QKV_W), d, h->Lw(l, L_QKV_B), w.big, 3 * d, Lq, 3 * d, d, EPI_BIAS_VPAGES, nullptr, 0, nullptr, 0, S,
                    1.0f, 0, 0, 0, 0, 0};
-        for (int i = 0; i < nF; ++i) g.v_dst[i] = persist ? vc + (size_t)write_slots[i] * S * d : w.vsc + (size_t)i * S * d;
+        if (full) {
+          // the clip's V rows are one contiguous [Lq, d] matrix in the workspace: ONE page of Lq rows (GemmArgs::v_dst holds 8)
+          g.rows_per_frame = Lq;
+          g.v_dst[0] = w.vsc;
+        } else {
+          for (int i = 0; i < nF; ++i) g.v_dst[i] = persist ? vc + (size_t)write_slots[i] * S * d : w.vsc + (size_t)i * S * d;
+        }
         g.v_col0 = 2 * d;
         g.v_ld = d;
         g.tile_counter = tc;
@@ -468,8 +484,9 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
         a.wq = h->Lw(l, L_NQ); a.wk = h->Lw(l, L_NK); a.rows = Lq; a.d = d; a.eps = c.eps; a.rope = 1;
         a.q_scale = prescale_q ? scale * 1.4426950408889634f : 0.f;
         a.cos_tab = h->cos_tab; a.sin_tab = h->sin_tab; a.rows_per_frame = S; a.grid_w = h->gw;
+        static_assert(sizeof(a.frame_ids) / sizeof(a.frame_ids[0]) >= MMPL_MAX_PAGES, "a whole clip's frames");
         for (int i = 0; i < nF; ++i) {
-          a.frame_ids[i] = frame_ids[i];                     // relative to *frame_base_dev, which the kernel reads when it runs
+          a.frame_ids[i] = full ? i : frame_ids[i];          // relative to *frame_base_dev, which the kernel reads when it runs
           a.k_dst[i] = persist ? kc + (size_t)write_slots[i] * S * d : w.ksc + (size_t)i * S * d;
           a.v_dst[i] = persist ? vc + (size_t)write_slots[i] * S * d : w.vsc + (size_t)i * S * d;
         }
@@ -506,7 +523,7 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
         ProfScope ps(K_ATTN_SELF, 4.0 * Lq * (double)np * S * d, s);
         HIP_TRY(mmpl_launch_attention(a, s), "self attention");
       }
-      TRY(gemm(w.attn, d, h->Lw(l, L_O_W), d, h->Lw(l, L_O_B), w.x, d, Lq, d, d, EPI_GATE_RES, w.x, d, em + 2 * d, 6 * d, S, s, tc, w.splitk));
+      TRY(gemm(w.attn, d, h->Lw(l, L_O_W), d, h->Lw(l, L_O_B), w.x, d, Lq, d, d, EPI_GATE_RES, w.x, d, em + 2 * d, mfs, S, s, tc, w.splitk));
       if (l == 0 && share_out) HIP_TRY(hipMemcpyAsync(share_out, w.x, (size_t)Lq * d * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "share block-0 x");
     }
     // -- cross attention (causal_fps_model.py:352-353, model.py:161-194)
@@ -547,16 +564,16 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
     TRY(gemm(w.attn, d, h->Lw(l, L_CO_W), d, h->Lw(l, L_CO_B), w.x, d, Lq, d, d, EPI_RES, w.x, d, nullptr, 0, 1, s, tc, w.splitk));
     // -- FFN (causal_fps_model.py:354-360)
     {
-      LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, em + 4 * d, em + 3 * d, 6 * d, S, nullptr, nullptr};
+      LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, em + 4 * d, em + 3 * d, mfs, S, nullptr, nullptr};
       ProfScope ps(K_LAYERNORM, 0, s);
       HIP_TRY(mmpl_launch_layernorm(a, s), "norm2");
     }
     TRY(gemm(w.xn, d, h->Lw(l, L_F0_W), d, h->Lw(l, L_F0_B), w.big, f, Lq, f, d, EPI_BIAS_GELU, nullptr, 0, nullptr, 0, 1, s, tc, w.splitk));
-    TRY(gemm(w.big, f, h->Lw(l, L_F2_W), f, h->Lw(l, L_F2_B), w.x, d, Lq, d, f, EPI_GATE_RES, w.x, d, em + 5 * d, 6 * d, S, s, tc, w.splitk));
+    TRY(gemm(w.big, f, h->Lw(l, L_F2_W), f, h->Lw(l, L_F2_B), w.x, d, Lq, d, f, EPI_GATE_RES, w.x, d, em + 5 * d, mfs, S, s, tc, w.splitk));
   }
   // ---- head + unpatchify (causal_fps_model.py:384-395, 1007-1030)
   {
-    LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, w.emod_head + d, w.emod_head, 2 * d, S, nullptr, nullptr};
+    LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, w.emod_head + d, w.emod_head, hfs, S, nullptr, nullptr};
     HIP_TRY(mmpl_launch_layernorm(a, s), "head norm");
   }
   TRY(gemm(w.xn, d, h->G(G_HEAD_W), d, h->G(G_HEAD_B), w.yh, 64, Lq, 64, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
@@ -572,6 +589,34 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
     }
   }
   return 0;
+}
+
+int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF, const int* frame_ids,
+                        const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
+                        int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
+                        void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                        mmpl_stream_t stream) {
+  return dit_forward_run("mmpl_dit_forward", false, h, x_in, t_dev, nF, frame_ids, write_slots, visible_slots, n_visible, k_cache, v_cache,
+                         n_slots, cross_k, cross_v, cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes,
+                         frame_base_dev, stream);
+}
+
+size_t mmpl_dit_full_workspace_bytes(const MmplDit* h, int n_frames) {
+  return (h && n_frames >= 1 && n_frames <= MMPL_MAX_PAGES) ? carve_fwd(h, n_frames, nullptr, 1).bytes : 0;
+}
+
+int mmpl_dit_forward_full(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const void* cross_k, const void* cross_v,
+                          int cross_rows, void* share_out, const void* share_in, void* attn_history, void* out, void* workspace,
+                          size_t workspace_bytes, mmpl_stream_t stream) {
+  const char* me = "mmpl_dit_forward_full";
+  if (!h) return fail(me, "null handle");
+  if (!x_in || !t_dev || !cross_k || !cross_v || !out || !workspace) return fail(me, "null argument");
+  if (n_frames < 1 || n_frames > MMPL_MAX_PAGES) return fail(me, "n_frames out of range (1 .. 24)");
+  if (share_out && share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
+  if (h->w.empty()) return fail(me, "weights not bound");
+  if (workspace_bytes < mmpl_dit_full_workspace_bytes(h, n_frames)) return fail(me, "workspace too small");
+  return dit_forward_run(me, true, h, x_in, t_dev, n_frames, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, cross_k, cross_v,
+                         cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
 }
 
 int mmpl_dit_share_check_failures(MmplDit* h, long long* count, mmpl_stream_t stream) {

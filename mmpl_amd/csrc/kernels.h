@@ -199,10 +199,11 @@ struct QkNormArgs {
   float q_scale;                      // q is multiplied by this after RoPE, before its (single) rounding to bf16; 0 = 1
   int rope;                           // 0: no rope (cross-attn q / context k)
   const float* cos_tab; const float* sin_tab;  // [1024][64] fp32
-  int frame_ids[8];                   // temporal rope position per local frame (relative to *frame_base when that is set)
+  int frame_ids[MMPL_MAX_PAGES];      // temporal rope position per local frame (relative to *frame_base when that is set); a stage of
+                                      // mmpl_dit_forward uses the first 8 at most, the whole clip of mmpl_dit_forward_full up to all of them
   const int* frame_base;              // device int added to every frame id when the kernel RUNS (a captured launch is replayed at
                                       // another position by rewriting it in stream order); NULL = 0.  The sum is clamped to the tables' 0..1023
-  bf16_t* k_dst[8]; bf16_t* v_dst[8]; // per local frame destination page base (row stride = d); k_out for no-page mode
+  bf16_t* k_dst[MMPL_MAX_PAGES]; bf16_t* v_dst[MMPL_MAX_PAGES]; // per local frame destination page base (row stride = d); k_out for no-page mode
   int rows_per_frame, grid_w;
 };
 RowPassPlan mmpl_qknorm_plan(const QkNormArgs& a, int groups_per_block = 0);

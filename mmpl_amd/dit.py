@@ -96,6 +96,7 @@ class DitEngine:
         self._weights: List[torch.Tensor] = []
         self._ws: Dict[int, torch.Tensor] = {}
         self._ws2: Optional[torch.Tensor] = None
+        self._ws_full: Dict[Tuple[int, bool], torch.Tensor] = {}    # forward_full: (frame count, second) -> scratch
         self._share: Optional[torch.Tensor] = None
         self._ctx_ws: Optional[torch.Tensor] = None
         self._i2v_w: Optional[dict] = None                 # img_emb + per-layer k_img / v_img / norm_k_img (model_type 'i2v')
@@ -313,6 +314,51 @@ class DitEngine:
                 None if share_out is None else _lib.ptr(share_out), None if share_in is None else _lib.ptr(share_in),
                 None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base),
                 _lib.stream_ptr()), "mmpl_dit_forward")
+        return out
+
+    # ------------------------------------------------------------------ whole-clip (bidirectional) forward
+    def full_workspace(self, n_frames: int, second: bool = False) -> torch.Tensor:
+        """Scratch of `forward_full` at `n_frames` frames: one buffer per frame count, allocated on first use (outside any capture).
+        `second`: a private one for a forward that runs CONCURRENTLY with another (the uncond branch of a CFG step on a second
+        stream)."""
+        key = (n_frames, bool(second))
+        if key not in self._ws_full:
+            nbytes = self._lib.mmpl_dit_full_workspace_bytes(self._h, n_frames)
+            if nbytes == 0:
+                raise ValueError(f"DitEngine.forward_full: n_frames = {n_frames} is outside 1 .. 24")
+            self._ws_full[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws_full[key]
+
+    def forward_full(self, x: torch.Tensor, t: torch.Tensor, cross_k: torch.Tensor, cross_v: torch.Tensor,
+                     cross_rows: Optional[int] = None, out: Optional[torch.Tensor] = None, share_out: Optional[torch.Tensor] = None,
+                     share_in: Optional[torch.Tensor] = None, attn_history: Optional[torch.Tensor] = None,
+                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The non-causal forward over a whole clip (mmpl_dit_forward_full): x [nF, in_dim, lat_h, lat_w] bf16 with nF up to 24
+        whatever `max_frames`; t: ONE float32 on the device, the clip's timestep.  Frame i is rotated at temporal position i, every
+        frame attends to every frame, and there is no KV cache: the layer's K / V live in the workspace.  Returns the flow
+        prediction [nF, 16, lat_h, lat_w].  `cross_rows`, `share_out`, `share_in`, `attn_history` as in `forward`; `workspace`: a
+        private scratch (`full_workspace(nF, second=True)`) for a forward that runs concurrently with another one."""
+        nF = x.shape[0]
+        if self.model_type != "t2v":
+            raise RuntimeError("DitEngine.forward_full: only the t2v model type has a whole-clip forward")
+        assert x.is_contiguous() and x.dtype == torch.bfloat16 and x.shape[1:] == (self.in_dim, self.lat_h, self.lat_w)
+        assert t.dtype == torch.float32 and t.numel() == 1 and t.device == x.device
+        for sh in (share_out, share_in):
+            assert sh is None or (sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() >= nF * self.S * self.dim and sh.device == x.device)
+        if attn_history is not None:
+            need = self._lib.mmpl_dit_attn_history_bytes(self._h, nF)
+            assert attn_history.dtype == torch.uint8 and attn_history.is_contiguous() and attn_history.numel() >= need and attn_history.device == x.device
+        ws = self.full_workspace(nF) if workspace is None else workspace
+        if out is None:
+            out = torch.empty(nF, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.shape == (nF, 16, self.lat_h, self.lat_w)
+        with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
+            _lib.check(self._lib.mmpl_dit_forward_full(
+                self._h, _lib.ptr(x), _lib.ptr(t), nF, _lib.ptr(cross_k), _lib.ptr(cross_v),
+                self.text_len if cross_rows is None else int(cross_rows),
+                None if share_out is None else _lib.ptr(share_out), None if share_in is None else _lib.ptr(share_in),
+                None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                "mmpl_dit_forward_full")
         return out
 
     # ------------------------------------------------------------------ hipGraph

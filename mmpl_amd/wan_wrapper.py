@@ -480,25 +480,33 @@ class WanDiffusionWrapper(torch.nn.Module):
       * RoPE: contiguous frame ids ``current_start / S + i`` (causal_rope_apply, causal_model.py:27-57);
       * cache indexing: the block is written at its own frames and attends to the last ``window`` frames up to its end
         (causal_model.py:196-224; window = 21 frames when local_attn_size == -1, the reference's 32760 tokens at 480p).
-    ``forward`` returns (flow_pred, pred_x0); pred_x0 is ``_convert_flow_pred_to_x0`` on the device (mmpl_fewstep_update)."""
+    ``forward`` returns (flow_pred, pred_x0); pred_x0 is ``_convert_flow_pred_to_x0`` on the device (mmpl_fewstep_update).
+
+    ``is_causal=False`` is the reference's other branch: WanModel, the base (bidirectional) Wan2.1-T2V weights.  ``model`` is then a
+    plain handle, ``uniform_timestep`` is True and ``forward(noisy, conditional_dict, timestep)`` -- no caches -- is ONE whole-clip
+    forward at ``timestep[:, 0]`` (DitEngine.forward_full: frame i at position i, every frame sees every frame, no KV cache);
+    ``seq_len`` becomes the call's token count.  The pipelines' graphs use ``flow_full`` / ``fewstep_update``."""
 
     def __init__(self, model_name="Wan2.1-T2V-14B", timestep_shift=8.0, is_causal=False, local_attn_size=-1, sink_size=0,
                  *, model_config: Optional[dict] = None, geometry: Optional[Geometry] = None, device="cuda:0", max_frames: int = 7):
         super().__init__()
-        assert is_causal, "only the causal generator (CausalWanModel) is on the hot path"
+        self.is_causal = bool(is_causal)
         self.geometry = geometry or Geometry.named("480p")
         from .checkpoints import read_diffusers_dir
         cfg = model_config
-        disk_cfg, disk_sd = read_diffusers_dir(f"{local_wan_path}/{model_name}/")    # CausalWanModel.from_pretrained (:127-128)
+        # CausalWanModel.from_pretrained / WanModel.from_pretrained (:127-133)
+        disk_cfg, disk_sd = read_diffusers_dir(f"{local_wan_path}/{model_name}/")
         if cfg is None:
             cfg = disk_cfg
         if cfg is None:
             cfg = WAN_CONFIGS["14B" if "14B" in model_name else "1.3B"]
         self.engine = DitEngine(cfg, self.geometry.lat_h, self.geometry.lat_w, device, max_frames=max_frames)
         if self.engine.model_type != "t2v":
-            raise ValueError("WanDiffusionWrapper: the few-step causal generator is a t2v model")
+            raise ValueError("WanDiffusionWrapper: the generator is a t2v model (the few-step causal one and the bidirectional one alike)")
         self.local_attn_size = int(local_attn_size)
-        self.model = _CausalModelHandle(self.engine, self.local_attn_size, sink_size)
+        # is_causal=False: WanModel, the whole clip in one forward (DitEngine.forward_full); nothing of the causal cache applies
+        self.model = _CausalModelHandle(self.engine, self.local_attn_size, sink_size) if self.is_causal else _ModelHandle(self.engine)
+        self._ctx: List[tuple] = []               # is_causal=False: (prompt_embeds, its version, CrossKV) of the last two prompts
         if disk_sd is not None:
             self.engine.load_state_dict(disk_sd)
         self.model_type = "t2v"
@@ -587,6 +595,38 @@ class WanDiffusionWrapper(torch.nn.Module):
         _lib.check(_lib.load().mmpl_fewstep_update(_lib.ptr(flow), _lib.ptr(x), _lib.ptr(noise), _lib.ptr(x0_out), n,
                                                    float(sigma_t), float(sigma_next), _lib.stream_ptr()), "mmpl_fewstep_update")
 
+    # -- is_causal=False: WanModel.forward over the whole clip (wan/modules/model.py, utils/wan_wrapper.py:277-281) ------------------
+    def flow_full(self, x: torch.Tensor, t: torch.Tensor, crossattn_cache: CrossAttnCache, out: Optional[torch.Tensor] = None,
+                  share_out: Optional[torch.Tensor] = None, share_in: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One whole-clip forward: x [F, 16, h, w] bf16, t ONE float32 on the device (uniform_timestep).  Stateless attention; the
+        text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch: a captured graph
+        serves every later prompt).  share_out / share_in / workspace as in DitEngine.forward_full."""
+        return self.engine.forward_full(x, t, crossattn_cache.k_all, crossattn_cache.v_all, out=out, share_out=share_out,
+                                        share_in=share_in, workspace=workspace)
+
+    def _context_kv(self, prompt_embeds: torch.Tensor):
+        """Per-layer text K / V of `prompt_embeds`, kept for the last two prompts (the cond and the uncond one of a CFG loop) as
+        long as the tensor is the same object and was not written since."""
+        for src, ver, kv in self._ctx:
+            if src is prompt_embeds and ver == prompt_embeds._version:
+                return kv
+        kv = self.engine.precompute_context(prompt_embeds[0] if prompt_embeds.dim() == 3 else prompt_embeds)
+        self._ctx = self._ctx[-1:] + [(prompt_embeds, prompt_embeds._version, kv)]
+        return kv
+
+    def _forward_full(self, noisy_image_or_video: torch.Tensor, conditional_dict: dict, timestep: torch.Tensor):
+        assert noisy_image_or_video.shape[0] == 1, "batch size 1 (as every reference entry point)"
+        x = noisy_image_or_video[0].to(device=self.engine.device, dtype=torch.bfloat16).contiguous()
+        nF = x.shape[0]
+        self.seq_len = nF * self.engine.S                                  # the call's token count: nothing is padded
+        ts = timestep.reshape(noisy_image_or_video.shape[0], -1)[:, 0]      # input_timestep = timestep[:, 0] (:236-237)
+        kv = self._context_kv(conditional_dict["prompt_embeds"])
+        flow = self.engine.forward_full(x, ts.to(device=x.device, dtype=torch.float32), kv[0], kv[1], cross_rows=kv.rows)
+        x0 = torch.empty_like(x)
+        self.fewstep_update(flow, x, None, x0, self.sigma_x0(ts.cpu()[0]))
+        return flow.unsqueeze(0), x0.unsqueeze(0)
+
     # -- the reference's call shape ------------------------------------------------------------------------------------------
     def forward(self, noisy_image_or_video: torch.Tensor, conditional_dict: dict, timestep: torch.Tensor,
                 kv_cache: Optional[KVCache] = None, crossattn_cache: Optional[CrossAttnCache] = None,
@@ -594,11 +634,17 @@ class WanDiffusionWrapper(torch.nn.Module):
                 concat_time_embeddings: Optional[bool] = False, clean_x=None, aug_t=None, cache_start: Optional[int] = None):
         """noisy_image_or_video [1, F, 16, h, w]; timestep [1, F]; current_start in tokens.  -> (flow_pred, pred_x0), both
         [1, F, 16, h, w] bf16.  Reads the timestep on the host (one sync when it lives on the device): the pipeline's graphs use
-        `flow` / `fewstep_update` with host scalars instead."""
-        if kv_cache is None or crossattn_cache is None:
+        `flow` / `fewstep_update` with host scalars instead.  is_causal=False: no caches (a kv_cache is a ValueError), the whole
+        clip at timestep[:, 0]; is_causal=True: the caches are required."""
+        if self.is_causal and (kv_cache is None or crossattn_cache is None):
             raise ValueError("WanDiffusionWrapper: only the KV-cached inference forward is implemented (kv_cache / crossattn_cache)")
         if classify_mode or clean_x is not None:
             raise ValueError("WanDiffusionWrapper: training-only forward modes (classify_mode / clean_x) are not implemented")
+        if not self.is_causal:
+            if kv_cache is not None or crossattn_cache is not None:
+                raise ValueError("WanDiffusionWrapper(is_causal=False): the bidirectional forward runs the whole clip and takes no "
+                                 "kv_cache / crossattn_cache")
+            return self._forward_full(noisy_image_or_video, conditional_dict, timestep)
         assert noisy_image_or_video.shape[0] == 1, "batch size 1 (as every reference entry point)"
         S = self.engine.S
         cs = int(current_start or 0)
