@@ -57,7 +57,8 @@ int mmpl_dit_precompute_context(MmplDit* h, const void* context, void* cross_k, 
                                 size_t workspace_bytes, int* distinct_rows, mmpl_stream_t stream);
 
 /* Wan-I2V model type (WanModel(model_type='i2v'), wan/modules/model.py:563-616,672-712): in_dim = 36 (x and the
- * conditioning video y concatenated on the channel axis, model.py:680-681 -- the caller concatenates) and every block's
+ * conditioning video y concatenated on the channel axis, model.py:680-681 -- the caller concatenates for mmpl_dit_forward;
+ * mmpl_dit_forward_full_i2v takes the two as they are) and every block's
  * cross-attention also attends to the 257 projected CLIP tokens (WanI2VCrossAttention, model.py:224-266).  The image
  * K / V depend only on the image: img_k[l] = norm_k_img(k_img(img_emb(clip_fea))), img_v[l] = v_img(...), built with
  * mmpl_i2v_img_proj + mmpl_i2v_img_kv per layer; dev [num_layers, n_img_tokens, dim], borrowed until replaced.
@@ -151,6 +152,20 @@ size_t mmpl_dit_full_workspace_bytes(const MmplDit* h, int n_frames);
 int mmpl_dit_forward_full(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const void* cross_k, const void* cross_v,
                           int cross_rows, void* share_out, const void* share_in, void* attn_history, void* out, void* workspace,
                           size_t workspace_bytes, mmpl_stream_t stream);
+/* mmpl_dit_forward_full for the Wan-I2V model type (WanModel(model_type='i2v') sampled over the whole clip, wan/image2video.py), with
+ * the two halves of its input as two tensors: the 36-channel cat([x, y]) of model.py:680-681 is never built -- the patch embedding
+ * reads both (mmpl_patchify2) -- so a sampler updates the 16-channel latents in place while y stays where it is.
+ *   x_in       : dev [n_frames, 16, lat_h, lat_w], the latents
+ *   y_in       : dev [n_frames, in_dim - 16, lat_h, lat_w], the conditioning video (mask + encoded first frame), frame-major
+ *   everything else: the contract of mmpl_dit_forward_full, its workspace size included.  Both CFG branches of an I2V step see the
+ *                same image, so block 0's self-attention is still the same computation in both: share_out / share_in keep their
+ *                meaning.  The image cross-attention's output goes to the workspace's K area, which in this layout holds the layer's
+ *                own K and is dead once the self-attention has run.
+ * Equal, bit for bit, to mmpl_dit_forward_full on the same handle given the concatenation.  Also rejected before the first launch:
+ * a handle whose in_dim is not 36, a handle without image K / V (mmpl_dit_set_image_kv first), a null y_in. */
+int mmpl_dit_forward_full_i2v(MmplDit* h, const void* x_in, const void* y_in, const float* t_dev, int n_frames, const void* cross_k,
+                              const void* cross_v, int cross_rows, void* share_out, const void* share_in, void* attn_history,
+                              void* out, void* workspace, size_t workspace_bytes, mmpl_stream_t stream);
 /* The handle's RoPE tables (mmpl_dit_create: cos / sin of position * theta^(-2j / dims), theta 1e4, dims 44 | 42 | 42 of the 128-wide
  * head, computed in double and stored as float32), for tests and tools that make the forward's QK-norm launch themselves
  * (mmpl_qknorm_ex): copies the two [1024][64] float32 tables into the caller's device buffers cos_out / sin_out (256 KiB each),
@@ -589,6 +604,8 @@ int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const
  *   k < nmod.  mod holds (n_layers - 1) * mod_layer_stride + nmod * d elements, e (n_frames - 1) * e_frame_stride + (bcast ? d : nmod * d),
  *   emod n_layers * n_frames * nmod * d.
  * mmpl_patchify: x [F, C, h, w] -> a [F * h/2 * w/2, lda], column c * 4 + ph * 2 + pw; columns >= 4 C are zeroed.  h, w even, lda >= 4 C.
+ * mmpl_patchify2: mmpl_patchify of the channel concatenation of x [F, Cx, h, w] and y [F, Cy, h, w], which is never built: channels
+ *   0 .. Cx-1 are x's, Cx .. Cx+Cy-1 are y's, columns >= 4 (Cx + Cy) are zeroed.  h, w even, lda >= 4 (Cx + Cy).  The same a, bit for bit.
  * mmpl_unpatchify: y [F * h/2 * w/2, ldy], column (ph * 2 + pw) * C + c -> out [F, C, h, w].  h, w even, ldy >= 4 C.
  * mmpl_sinusoid: t dev float32 [F] -> out [F, freq_dim] = [cos | sin] of t * 10000^(-k / (freq_dim / 2)) in double.  freq_dim even.
  * mmpl_silu: y[i] = bf16(x[i] / (1 + exp(-x[i]))), n elements.
@@ -604,6 +621,7 @@ int mmpl_qknorm_ex(void* q, int ldq, const void* k, int ldk, const void* v, int 
 int mmpl_modulation(const void* mod, long long mod_layer_stride, const void* e, int e_frame_stride, int bcast, void* emod, int n_layers,
                     int n_frames, int nmod, int d, mmpl_stream_t stream);
 int mmpl_patchify(const void* x, void* a, int lda, int F, int C, int h, int w, mmpl_stream_t stream);
+int mmpl_patchify2(const void* x, const void* y, void* a, int lda, int F, int Cx, int Cy, int h, int w, mmpl_stream_t stream);
 int mmpl_unpatchify(const void* y, int ldy, void* out, int F, int C, int h, int w, mmpl_stream_t stream);
 int mmpl_sinusoid(const float* t, void* out, int F, int freq_dim, mmpl_stream_t stream);
 int mmpl_silu(const void* x, void* y, size_t n, mmpl_stream_t stream);

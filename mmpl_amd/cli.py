@@ -7,7 +7,8 @@
 Single process = the reference's sequential rollout (chunk k+1 starts from the last 5 pixel frames of chunk k,
 `Wan_fps_inference_1gpu.py:164-203`); several processes = the parallel scripts' wavefront (chunk c on rank c mod W,
 anchors handed over right after the anchor stage).  `--bidirectional` = plain Wan2.1 T2V instead: one whole clip per call
-(the reference's Bidirectional*InferencePipeline).  `--synthetic` runs without checkpoints (seeded weights and text
+(the reference's Bidirectional*InferencePipeline); with `--i2v --i2v_model --image FILE` the Wan2.1-I2V model type sampled the
+same way (upstream WanI2V.generate).  `--synthetic` runs without checkpoints (seeded weights and text
 embeddings) -- the only mode that can run in this repo's test environments.  Output: per prompt a uint8 tensor
 `[T, H, W, 3]` saved with torch.save (mp4 muxing via torchvision is outside the hot path; fps = 16).
 """
@@ -54,15 +55,23 @@ def pipeline_class(config, bidirectional: bool = False):
 
 def bidirectional_refusal(args, world: int):
     """Why --bidirectional cannot run this command line (None = it can, or it was not asked for).  The bidirectional pipelines
-    denoise ONE whole clip per call with a text-to-video model on one process: there is no chunk rollout, no image conditioning,
-    no block to stream or to roll a KV window over (there is no KV cache), and no second rank to give a CFG branch to."""
+    denoise ONE whole clip per call on one process: there is no chunk rollout, no block to stream or to roll a KV window over
+    (there is no KV cache), and no second rank to give a CFG branch to.  Image conditioning exists as the Wan-I2V MODEL TYPE only
+    (--i2v --i2v_model --image FILE): the whole-clip model has no "image latent as frame 0" mode, which is what --i2v alone means."""
     if not getattr(args, "bidirectional", False):
         return None
     if args.duration > 1:
         return (f"--duration {args.duration}: --bidirectional generates one {args.num_output_frames}-latent-frame clip per call "
                 "(use --duration 1)")
-    if args.i2v or args.i2v_model:
-        return "--i2v: --bidirectional is text-to-video only"
+    if args.i2v and not args.i2v_model:
+        return ("--i2v: --bidirectional has no 'image latent as frame 0' mode; its image-to-video is the Wan-I2V model type "
+                "(--i2v --i2v_model --image FILE)")
+    if args.i2v_model and not (args.i2v and getattr(args, "image", None)):
+        return "--i2v_model needs --i2v --image FILE (with --bidirectional as without)"
+    if args.i2v_model and getattr(args, "fewstep", False):
+        return "--i2v --i2v_model: the few-step bidirectional pipeline (config with denoising_step_list) is text-to-video only"
+    if getattr(args, "sample_shift", None) is not None and getattr(args, "fewstep", False):
+        return "--sample_shift: the few-step bidirectional pipeline follows its denoising_step_list and has no sampling shift"
     if getattr(args, "stream", False):
         return "--stream: --bidirectional denoises the whole clip at once; there are no blocks to hand out"
     if getattr(args, "rolling", False):
@@ -189,7 +198,11 @@ def main(argv=None):
     ap.add_argument("--resolution", default="480p", choices=["480p", "720p"])
     ap.add_argument("--model", default="14B", choices=list(WAN_CONFIGS))
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights / text embeddings (no checkpoints needed)")
-    ap.add_argument("--sampling_steps", type=int, default=50)
+    ap.add_argument("--sampling_steps", type=int, default=None,
+                    help="solver steps of the 50-step pipelines: default 50, or 40 for --bidirectional --i2v_model (WanI2V.generate)")
+    ap.add_argument("--sample_shift", type=float, default=None,
+                    help="--bidirectional only: the sampling schedule's shift; default 8.0 (the reference's text-to-video pipeline), or "
+                         "for --i2v_model WanI2V.generate's 5.0 (3.0 at --resolution 480p)")
     ap.add_argument("--sample_solver", default="unipc", choices=["unipc", "dpm++"],
                     help="the multistep solver of the 50-step pipeline: FlowUniPCMultistepScheduler or FlowDPMSolverMultistepScheduler "
                          "(DPM-Solver++(2M)), as in Wan2.1's generate.py")
@@ -212,17 +225,27 @@ def main(argv=None):
     ap.add_argument("--bidirectional", action="store_true",
                     help="plain (non-causal) Wan2.1 T2V: the whole --num_output_frames clip per forward, every frame attending to "
                          "every frame -- BidirectionalDiffusionInferencePipeline (--sampling_steps CFG steps of --sample_solver), or "
-                         "BidirectionalInferencePipeline for a few-step config (one with denoising_step_list)")
+                         "BidirectionalInferencePipeline for a few-step config (one with denoising_step_list).  With --i2v --i2v_model "
+                         "--image FILE: the Wan2.1-I2V-14B-480P / -720P model type sampled the same way (WanI2V.generate)")
     ap.add_argument("--local_attn_size", type=int, default=None, help="few-step configs: override model_kwargs.local_attn_size "
                     "(the KV window in latent frames; -1 = 21)")
     ap.add_argument("--sink_size", type=int, default=None, help="few-step configs: override model_kwargs.sink_size (the first "
                     "frames of the video that --rolling never evicts)")
     args = ap.parse_args(argv)
+    i2v_clip = bool(args.bidirectional and args.i2v_model)               # the whole-clip Wan-I2V model type: WanI2V.generate's defaults
+    if args.sampling_steps is None:
+        args.sampling_steps = 40 if i2v_clip else 50
+    if args.sample_shift is not None and not args.bidirectional:
+        ap.error("--sample_shift: only the --bidirectional pipelines take a sampling shift (the causal ones read timestep_shift "
+                 "from the config)")
+    if args.sample_shift is None and i2v_clip:
+        args.sample_shift = 3.0 if args.resolution == "480p" else 5.0
 
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     config = load_config(args.config_path)
     fewstep = is_fewstep(config)
+    args.fewstep = fewstep
     why = bidirectional_refusal(args, world)
     if why is not None:
         ap.error(why)
@@ -424,21 +447,49 @@ def _main_fewstep(config, args, dev, geo, mcfg):
         print(f"[mmpl_amd.cli] few-step prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
 
 
+def i2v_model_name(args) -> str:
+    """The released whole-clip I2V checkpoints' directories under ../wan_models: one per resolution."""
+    return "Wan2.1-I2V-14B-480P" if args.resolution == "480p" else "Wan2.1-I2V-14B-720P"
+
+
 def build_bidirectional_pipeline(config, args, dev, geo, mcfg):
-    """WanDiffusionWrapper(is_causal=False) + the bidirectional pipeline `pipeline_class` picks for `config`."""
+    """WanDiffusionWrapper(is_causal=False) + the bidirectional pipeline `pipeline_class` picks for `config`; with --i2v_model the
+    generator is the Wan-I2V model type and the pipeline gets `clip`, the CLIP ViT-H tower its image conditioning needs."""
     from .wan_wrapper import SyntheticTextEncoder, WanDiffusionWrapper, WanVAEWrapper
+    i2v = bool(getattr(args, "i2v_model", False))
     kw = {k: v for k, v in dict(getattr(config, "model_kwargs", {}) or {}).items() if k in ("model_name", "timestep_shift")}
+    if i2v:
+        kw["model_name"] = i2v_model_name(args)
+        mcfg = dict(mcfg, model_type="i2v")
     kw.setdefault("model_name", "Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B")
     gen = WanDiffusionWrapper(**kw, is_causal=False, model_config=mcfg if args.synthetic else None, geometry=geo, device=dev)
-    enc, vae = None, None
+    if i2v and gen.model_type != "i2v":
+        raise SystemExit("--i2v_model: the checkpoint directory does not hold a model_type 'i2v' config")
+    enc, vae, clip = None, None, None
+    if i2v:
+        from .i2v_clip import CLIPVisionTower
+        tiny_clip = args.synthetic and args.model in ("tiny", "small")      # tests: 3 blocks instead of ViT-H's 32
+        clip = CLIPVisionTower(num_layers=3 if tiny_clip else 32, device=dev)
     if args.synthetic:
-        gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
+        if i2v:
+            from .synthetic import clip_visual_state_dict, dit_i2v_state_dict
+            gen.load_state_dict(dit_i2v_state_dict(mcfg, seed=1, device=dev))
+            clip.load_state_dict(clip_visual_state_dict(1280, 16, clip.num_layers, seed=3, device=dev))
+        else:
+            gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
         enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
         vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
+    elif i2v:
+        from .checkpoints import read_clip_visual
+        from .wan_wrapper import local_wan_path
+        clip.load_state_dict(read_clip_visual(f"{local_wan_path}/{kw['model_name']}/models_clip_open-clip-xlm-roberta-large-vit-huge-14.pth"))
     pipe = pipeline_class(config, bidirectional=True)(config, dev, generator=gen, text_encoder=enc, vae=vae)
+    pipe.clip = clip
     if not is_fewstep(config):
         pipe.sampling_steps = args.sampling_steps
         pipe.sample_solver = args.sample_solver
+        if getattr(args, "sample_shift", None) is not None:
+            pipe.shift = float(args.sample_shift)
     if args.checkpoint_path:
         from .checkpoints import read_mmpl_checkpoint
         pipe.generator.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
@@ -450,11 +501,22 @@ def _main_bidirectional(config, args, dev, geo, mcfg):
     pipe = build_bidirectional_pipeline(config, args, dev, geo, mcfg)
     os.makedirs(args.output_folder, exist_ok=True)
     shape = [1, args.num_output_frames, 16, geo.lat_h, geo.lat_w]
+    extra = {}
+    if args.i2v_model:
+        # image2video.py:186-246: the image at the clip's pixel size in [-1, 1] -> CLIP tokens + the conditioning video y
+        import numpy as np
+        from PIL import Image
+        from .i2v_condition import build_image_condition
+        H, W = geo.pixel_hw
+        img = Image.open(args.image).convert("RGB").resize((W, H), Image.BILINEAR)
+        px = torch.from_numpy(np.asarray(img).copy()).permute(2, 0, 1).float() / 255.0
+        px = ((px - 0.5) / 0.5).to(device=dev, dtype=torch.bfloat16)                                   # [3, H, W]
+        extra["image_condition"] = build_image_condition(pipe.vae, pipe.clip, px, args.num_output_frames)
     for idx, prompt in enumerate(_prompts(args)):
         g = torch.Generator(device="cpu").manual_seed(args.seed)
         noise = torch.randn(shape, generator=g).to(torch.bfloat16)
         torch.manual_seed(args.seed)                         # the few-step re-noise draws: the device generator
-        video = pipe.inference(noise.to(dev), [prompt])
+        video = pipe.inference(noise.to(dev), [prompt], **extra)
         out = (video * 255.0).clamp(0, 255).to(torch.uint8)[0].permute(0, 2, 3, 1).contiguous().cpu()         # [T, H, W, 3]
         path = os.path.join(args.output_folder, f"{idx}-0.pt")
         torch.save(out, path)

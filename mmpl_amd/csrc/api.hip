@@ -373,7 +373,9 @@ int mmpl_dit_forward(MmplDit* h, const void* x_in, const float* t_dev, int nF, c
 // K / V are the workspace's scratch pair, every frame attends to all of them), n_frames up to MMPL_MAX_PAGES whatever cfg.max_frames,
 // and t_dev is ONE float: the timestep embedding and the modulation vectors are computed for one row and read by every frame
 // through a frame stride of 0 (row i of those GEMMs depends on row i of their input alone, so the bits are the per-frame ones).
-static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_in, const float* t_dev, int nF, const int* frame_ids,
+// y_in (NULL for every entry but mmpl_dit_forward_full_i2v): x_in then holds the first 16 of the in_dim channels and y_in the rest.
+static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_in, const void* y_in, const float* t_dev, int nF,
+                           const int* frame_ids,
                            const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
                            int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
                            void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
@@ -403,7 +405,11 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
   HIP_TRY(mmpl_launch_zero_ints(w.tile_counter, kTicketInts, s), "tile counter");                  // left zero by every GEMM that uses it
   int* const tc = w.tile_counter;
   // ---- embeddings (causal_fps_model.py:757-776)
-  HIP_TRY(mmpl_launch_patchify((const bf16_t*)x_in, w.patch, h->pe_k, nF, c.in_dim, c.lat_h, c.lat_w, s), "patchify");
+  if (y_in)
+    HIP_TRY(mmpl_launch_patchify2((const bf16_t*)x_in, (const bf16_t*)y_in, w.patch, h->pe_k, nF, c.out_dim, c.in_dim - c.out_dim, c.lat_h,
+                                  c.lat_w, s), "patchify (x, y)");
+  else
+    HIP_TRY(mmpl_launch_patchify((const bf16_t*)x_in, w.patch, h->pe_k, nF, c.in_dim, c.lat_h, c.lat_w, s), "patchify");
   TRY(gemm(w.patch, h->pe_k, h->G(G_PE_W), h->pe_k, h->G(G_PE_B), w.x, d, Lq, d, h->pe_k, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
   HIP_TRY(mmpl_launch_sinusoid(t_dev, w.sinu, nT, c.freq_dim, s), "sinusoid");
   TRY(gemm(w.sinu, c.freq_dim, h->G(G_TE0_W), c.freq_dim, h->G(G_TE0_B), w.t1, d, nT, d, c.freq_dim, EPI_BIAS_SILU, nullptr,
@@ -546,8 +552,10 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
       else if (ctx_n >= 0) { a.page_rows = ctx_n + 1; a.last_row_copies = T - ctx_n; }   // padded tail = one key, weighted (precompute_context)
       a.k_pages[0] = (const bf16_t*)cross_k + (size_t)l * T * d;
       a.v_pages[0] = (const bf16_t*)cross_v + (size_t)l * T * d;
-      ProfScope ps(K_ATTN_CROSS, 4.0 * Lq * (double)T * d, s);
-      HIP_TRY(mmpl_launch_attention(a, s), "cross attention");
+      {
+        ProfScope ps(K_ATTN_CROSS, 4.0 * Lq * (double)T * d, s);
+        HIP_TRY(mmpl_launch_attention(a, s), "cross attention");
+      }
       if (h->img_k) {
         // Wan-I2V: the query also attends to the image tokens; the two outputs are summed in bf16 before the o-projection
         // (WanI2VCrossAttention.forward, model.py:254-263).  The scratch K pages are free here: they hold the image output.
@@ -556,8 +564,11 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
         a.last_row_copies = 0;                    // (the text stream's weighted padded key does not apply to the image tokens)
         a.k_pages[0] = h->img_k + (size_t)l * h->n_img * d;
         a.v_pages[0] = h->img_v + (size_t)l * h->n_img * d;
-        ProfScope ps2(K_ATTN_CROSS, 4.0 * Lq * (double)h->n_img * d, s);
-        HIP_TRY(mmpl_launch_attention(a, s), "image cross attention");
+        {
+          ProfScope ps2(K_ATTN_CROSS, 4.0 * Lq * (double)h->n_img * d, s);       // (one scope at a time: they do not nest)
+          HIP_TRY(mmpl_launch_attention(a, s), "image cross attention");
+        }
+        ProfScope ps3(K_ELEMENTWISE, 0, s);
         HIP_TRY(mmpl_launch_add(w.attn, w.ksc, (size_t)Lq * d, s), "x + img_x");
       }
     }
@@ -596,7 +607,7 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
                         int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
                         void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
                         mmpl_stream_t stream) {
-  return dit_forward_run("mmpl_dit_forward", false, h, x_in, t_dev, nF, frame_ids, write_slots, visible_slots, n_visible, k_cache, v_cache,
+  return dit_forward_run("mmpl_dit_forward", false, h, x_in, nullptr, t_dev, nF, frame_ids, write_slots, visible_slots, n_visible, k_cache, v_cache,
                          n_slots, cross_k, cross_v, cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes,
                          frame_base_dev, stream);
 }
@@ -615,7 +626,23 @@ int mmpl_dit_forward_full(MmplDit* h, const void* x_in, const float* t_dev, int 
   if (share_out && share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
   if (h->w.empty()) return fail(me, "weights not bound");
   if (workspace_bytes < mmpl_dit_full_workspace_bytes(h, n_frames)) return fail(me, "workspace too small");
-  return dit_forward_run(me, true, h, x_in, t_dev, n_frames, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, cross_k, cross_v,
+  return dit_forward_run(me, true, h, x_in, nullptr, t_dev, n_frames, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, cross_k, cross_v,
+                         cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
+}
+
+int mmpl_dit_forward_full_i2v(MmplDit* h, const void* x_in, const void* y_in, const float* t_dev, int n_frames, const void* cross_k,
+                              const void* cross_v, int cross_rows, void* share_out, const void* share_in, void* attn_history,
+                              void* out, void* workspace, size_t workspace_bytes, mmpl_stream_t stream) {
+  const char* me = "mmpl_dit_forward_full_i2v";
+  if (!h) return fail(me, "null handle");
+  if (!x_in || !y_in || !t_dev || !cross_k || !cross_v || !out || !workspace) return fail(me, "null argument");
+  if (h->cfg.in_dim != 36 || h->cfg.out_dim != 16) return fail(me, "not an i2v handle (in_dim must be 36: 16 latent + 20 conditioning channels)");
+  if (!h->img_k) return fail(me, "no image K / V attached (mmpl_dit_set_image_kv first)");
+  if (n_frames < 1 || n_frames > MMPL_MAX_PAGES) return fail(me, "n_frames out of range (1 .. 24)");
+  if (share_out && share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
+  if (h->w.empty()) return fail(me, "weights not bound");
+  if (workspace_bytes < mmpl_dit_full_workspace_bytes(h, n_frames)) return fail(me, "workspace too small");
+  return dit_forward_run(me, true, h, x_in, y_in, t_dev, n_frames, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, cross_k, cross_v,
                          cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
 }
 

@@ -336,6 +336,24 @@ __global__ void patchify_kernel(const bf16_t* x, bf16_t* a, int lda, int F, int 
   }
 }
 
+// patchify_kernel on the channel concatenation of x [F, Cx, h, w] and y [F, Cy, h, w], which is never materialised (Wan-I2V's
+// cat([x, y]) in front of the patch embedding, model.py:680-681): channel c < Cx is x's, Cx <= c < Cx + Cy is y's channel c - Cx
+__global__ void patchify2_kernel(const bf16_t* x, const bf16_t* y, bf16_t* a, int lda, int F, int Cx, int Cy, int h, int w) {
+  const int gh = h >> 1, gw = w >> 1;
+  const size_t total = (size_t)F * gh * gw * lda;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int col = (int)(i % lda);
+    const size_t tokg = i / lda;
+    const int c = col >> 2, ph = (col >> 1) & 1, pw = col & 1;
+    const int gx = (int)(tokg % gw), gy = (int)((tokg / gw) % gh), f = (int)(tokg / ((size_t)gw * gh));
+    const size_t pix = (size_t)(2 * gy + ph) * w + 2 * gx + pw;
+    bf16_t v = 0;                                                                                    // columns >= 4 (Cx + Cy): K padding
+    if (c < Cx) v = x[((size_t)f * Cx + c) * h * w + pix];
+    else if (c < Cx + Cy) v = y[((size_t)f * Cy + (c - Cx)) * h * w + pix];
+    a[i] = v;
+  }
+}
+
 __global__ void unpatchify_kernel(const bf16_t* y, int ldy, bf16_t* out, int F, int C, int h, int w) {
   const int gh = h >> 1, gw = w >> 1;
   const size_t total = (size_t)F * C * h * w;
@@ -562,6 +580,11 @@ hipError_t mmpl_launch_modulation(const bf16_t* mod, size_t mod_layer_stride, co
 hipError_t mmpl_launch_patchify(const bf16_t* x, bf16_t* a, int lda, int F, int C, int h, int w, hipStream_t s) {
   const size_t n = (size_t)F * (h / 2) * (w / 2) * lda;
   hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, a, lda, F, C, h, w);
+  return hipGetLastError();
+}
+hipError_t mmpl_launch_patchify2(const bf16_t* x, const bf16_t* y, bf16_t* a, int lda, int F, int Cx, int Cy, int h, int w, hipStream_t s) {
+  const size_t n = (size_t)F * (h / 2) * (w / 2) * lda;
+  hipLaunchKernelGGL(patchify2_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, y, a, lda, F, Cx, Cy, h, w);
   return hipGetLastError();
 }
 hipError_t mmpl_launch_unpatchify(const bf16_t* y, int ldy, bf16_t* out, int F, int C, int h, int w, hipStream_t s) {

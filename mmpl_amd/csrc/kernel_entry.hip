@@ -467,6 +467,17 @@ int mmpl_patchify(const void* x, void* a, int lda, int F, int C, int h, int w, m
   LAUNCH(mmpl_launch_patchify((const bf16_t*)x, (bf16_t*)a, lda, F, C, h, w, (hipStream_t)stream), me);
 }
 
+int mmpl_patchify2(const void* x, const void* y, void* a, int lda, int F, int Cx, int Cy, int h, int w, mmpl_stream_t stream) {
+  const char* me = "mmpl_patchify2";
+  REJECT(!x || !y || !a, me, "null argument");
+  REJECT(F < 1 || Cx < 1 || Cy < 1 || h < 1 || w < 1, me, "non-positive size");
+  REJECT((h | w) & 1, me, "odd h or w");
+  REJECT(Cx > 0x0fffffff || Cy > 0x0fffffff || lda < 4 * (Cx + Cy), me, "lda < 4 (Cx + Cy)");
+  REJECT(too_many(F, h, w), me, "too many pixels");
+  REJECT(misaligned(x, 2) || misaligned(y, 2) || misaligned(a, 2), me, "misaligned pointer");
+  LAUNCH(mmpl_launch_patchify2((const bf16_t*)x, (const bf16_t*)y, (bf16_t*)a, lda, F, Cx, Cy, h, w, (hipStream_t)stream), me);
+}
+
 int mmpl_unpatchify(const void* y, int ldy, void* out, int F, int C, int h, int w, mmpl_stream_t stream) {
   const char* me = "mmpl_unpatchify";
   REJECT(!y || !out, me, "null argument");

@@ -218,6 +218,8 @@ hipError_t mmpl_launch_modulation(const bf16_t* mod, size_t mod_layer_stride, co
                                   bf16_t* emod, int n_layers, int n_frames, int nmod, int d, hipStream_t s);
 // patchify: x[F, C, h, w] -> A[F*gh*gw, lda]  (col = c*4 + ph*2 + pw; columns >= 4 C are zero: K padded to a multiple of 64)
 hipError_t mmpl_launch_patchify(const bf16_t* x, bf16_t* a, int lda, int F, int C, int h, int w, hipStream_t s);
+// patchify2: patchify of cat([x[F, Cx, h, w], y[F, Cy, h, w]], channel axis) without the concatenated tensor: the same A, bit for bit
+hipError_t mmpl_launch_patchify2(const bf16_t* x, const bf16_t* y, bf16_t* a, int lda, int F, int Cx, int Cy, int h, int w, hipStream_t s);
 // unpatchify: y[F*gh*gw, 4*C] (col = (ph*2+pw)*C + c) -> out[F, C, h, w]
 // a = bf16(a + b), n elements (i2v.hip)
 hipError_t mmpl_launch_add(bf16_t* a, const bf16_t* b, size_t n, hipStream_t s);

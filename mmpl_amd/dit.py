@@ -7,7 +7,7 @@ forward against a per-layer KV cache.  PyTorch only owns the device memory here;
 ``model_type='i2v'`` (wan/modules/model.py:563-616: in_dim 36, ``img_emb`` = MLPProj(1280, dim), every block's
 cross-attention a ``WanI2VCrossAttention``) adds the image stream: ``precompute_image_context(clip_fea)`` builds the
 per-layer image K / V once per image, ``set_image_kv`` attaches them, and ``forward`` takes x with the conditioning video
-``y`` concatenated on the channel axis (model.py:680-681).
+``y`` concatenated on the channel axis (model.py:680-681); ``forward_full`` takes the two as separate tensors.
 """
 from __future__ import annotations
 
@@ -206,10 +206,12 @@ class DitEngine:
                                                              self._ctx_ws.numel(), C.byref(rows), _lib.stream_ptr()), "precompute_context")
         return CrossKV(ck, cv, rows.value)
 
-    def precompute_image_context(self, clip_fea: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def precompute_image_context(self, clip_fea: torch.Tensor,
+                                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """clip_fea: [257, clip_dim] (CLIP ViT-H penultimate-block tokens, clip.py:541) -> per-layer image (K, V)
         [num_layers, 257, dim]: img_emb (MLPProj, model.py:469-481), then k_img / norm_k_img and v_img of every block
-        (model.py:251-252).  Once per image, like precompute_context once per prompt."""
+        (model.py:251-252).  Once per image, like precompute_context once per prompt.  `out`: write into these two buffers instead
+        of new ones -- the pair a captured graph holds by address (`set_image_kv`) is refreshed in place for the next image."""
         if self._i2v_w is None:
             raise RuntimeError("DitEngine: not an i2v model (or weights not loaded)")
         lib, d = self._lib, self.dim
@@ -219,8 +221,13 @@ class DitEngine:
         ctx_img = torch.empty(n, d, dtype=torch.bfloat16, device=self.device)
         ws = torch.empty(lib.mmpl_i2v_img_proj_workspace_bytes(n, self.clip_dim, d), dtype=torch.uint8, device=self.device)
         arr = (C.c_void_p * 8)(*[t.data_ptr() for t in self._i2v_w["img_emb"]])
-        img_k = torch.empty(self.L, n, d, dtype=torch.bfloat16, device=self.device)
-        img_v = torch.empty_like(img_k)
+        if out is None:
+            img_k = torch.empty(self.L, n, d, dtype=torch.bfloat16, device=self.device)
+            img_v = torch.empty_like(img_k)
+        else:
+            img_k, img_v = out
+            for t in (img_k, img_v):
+                assert t.shape == (self.L, n, d) and t.dtype == torch.bfloat16 and t.is_contiguous() and t.device == self.device
         with torch.cuda.device(self.device):
             _lib.check(lib.mmpl_i2v_img_proj(_lib.ptr(fea), n, self.clip_dim, d, arr, _lib.ptr(ctx_img), _lib.ptr(ws), ws.numel(),
                                              _lib.stream_ptr()), "mmpl_i2v_img_proj")
@@ -332,16 +339,25 @@ class DitEngine:
     def forward_full(self, x: torch.Tensor, t: torch.Tensor, cross_k: torch.Tensor, cross_v: torch.Tensor,
                      cross_rows: Optional[int] = None, out: Optional[torch.Tensor] = None, share_out: Optional[torch.Tensor] = None,
                      share_in: Optional[torch.Tensor] = None, attn_history: Optional[torch.Tensor] = None,
-                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The non-causal forward over a whole clip (mmpl_dit_forward_full): x [nF, in_dim, lat_h, lat_w] bf16 with nF up to 24
+                     workspace: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The non-causal forward over a whole clip (mmpl_dit_forward_full): x [nF, 16, lat_h, lat_w] bf16 with nF up to 24
         whatever `max_frames`; t: ONE float32 on the device, the clip's timestep.  Frame i is rotated at temporal position i, every
         frame attends to every frame, and there is no KV cache: the layer's K / V live in the workspace.  Returns the flow
         prediction [nF, 16, lat_h, lat_w].  `cross_rows`, `share_out`, `share_in`, `attn_history` as in `forward`; `workspace`: a
-        private scratch (`full_workspace(nF, second=True)`) for a forward that runs concurrently with another one."""
+        private scratch (`full_workspace(nF, second=True)`) for a forward that runs concurrently with another one.
+        `y`: the i2v model type's conditioning video, [nF, in_dim - 16, lat_h, lat_w] bf16, frame-major like x and read next to it
+        (mmpl_dit_forward_full_i2v: x and y are never concatenated); required there -- with `set_image_kv` done --, None for t2v."""
         nF = x.shape[0]
-        if self.model_type != "t2v":
-            raise RuntimeError("DitEngine.forward_full: only the t2v model type has a whole-clip forward")
-        assert x.is_contiguous() and x.dtype == torch.bfloat16 and x.shape[1:] == (self.in_dim, self.lat_h, self.lat_w)
+        i2v = self.model_type == "i2v"
+        if i2v and y is None:
+            raise ValueError("DitEngine.forward_full: an i2v model needs y, the conditioning video [nF, in_dim - 16, lat_h, lat_w]")
+        if not i2v and y is not None:
+            raise ValueError("DitEngine.forward_full: y belongs to the i2v model type; this is a t2v model")
+        if i2v and self._img_kv is None:
+            raise RuntimeError("DitEngine: an i2v model needs set_image_kv(*precompute_image_context(clip_fea)) before forward_full")
+        assert x.is_contiguous() and x.dtype == torch.bfloat16 and x.shape[1:] == (16, self.lat_h, self.lat_w)
+        if i2v:
+            assert y.is_contiguous() and y.dtype == torch.bfloat16 and y.shape == (nF, self.in_dim - 16, self.lat_h, self.lat_w) and y.device == x.device
         assert t.dtype == torch.float32 and t.numel() == 1 and t.device == x.device
         for sh in (share_out, share_in):
             assert sh is None or (sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() >= nF * self.S * self.dim and sh.device == x.device)
@@ -352,13 +368,16 @@ class DitEngine:
         if out is None:
             out = torch.empty(nF, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=x.device)
         assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.shape == (nF, 16, self.lat_h, self.lat_w)
-        with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
-            _lib.check(self._lib.mmpl_dit_forward_full(
-                self._h, _lib.ptr(x), _lib.ptr(t), nF, _lib.ptr(cross_k), _lib.ptr(cross_v),
-                self.text_len if cross_rows is None else int(cross_rows),
+        tail = (nF, _lib.ptr(cross_k), _lib.ptr(cross_v), self.text_len if cross_rows is None else int(cross_rows),
                 None if share_out is None else _lib.ptr(share_out), None if share_in is None else _lib.ptr(share_in),
-                None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-                "mmpl_dit_forward_full")
+                None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel())
+        with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
+            if i2v:
+                _lib.check(self._lib.mmpl_dit_forward_full_i2v(self._h, _lib.ptr(x), _lib.ptr(y), _lib.ptr(t), *tail, _lib.stream_ptr()),
+                           "mmpl_dit_forward_full_i2v")
+            else:
+                _lib.check(self._lib.mmpl_dit_forward_full(self._h, _lib.ptr(x), _lib.ptr(t), *tail, _lib.stream_ptr()),
+                           "mmpl_dit_forward_full")
         return out
 
     # ------------------------------------------------------------------ hipGraph

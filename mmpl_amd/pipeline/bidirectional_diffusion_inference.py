@@ -14,6 +14,17 @@ is not read --, ``args``) and the same semantics.  What changed underneath:
     forward (share_out / share_in) where the two run back to back; where ``concurrent_cfg_pays`` says so they run as parallel
     branches of the graph instead (second stream, private workspace);
   * the frame count is ``noise.shape[1]`` where the reference writes the literal 21; batch size 1.
+
+Over a ``model_type='i2v'`` generator (the released Wan2.1-I2V-14B-480P / -720P weights) this is upstream ``WanI2V.generate``
+(wan/image2video.py): ``inference(..., image_condition={"clip_fea": [257, 1280], "y": [20, F, h, w]})`` from
+``i2v_condition.build_image_condition(vae, clip, image, n_latent_frames=F)``, the argument ``CausalFPSInferencePipeline.inference``
+has.  The step state gains a static frame-major ``y`` buffer that every forward of the step graph reads next to the latents
+(``mmpl_dit_forward_full_i2v``: no concatenation, no copy inside the graph); per call ``y`` is copied in and the generator's
+image K / V are rebuilt in place, so another image replays the SAME graph.  Both CFG branches see the image (upstream's
+``arg_null`` carries ``clip_fea`` and ``y`` too), so block 0 is still shared.  The latent chain stays this project's: bf16 latents
+and the fused ``step_cfg_table``, like the text-to-video path; upstream ``WanI2V.generate`` keeps its latents in fp32.  ``shift``
+and ``sampling_steps`` keep the defaults above -- ``WanI2V.generate``'s own (40 steps, shift 5.0, or 3.0 at 480p) are the caller's
+to set, as ``mmpl_amd.cli`` does.
 """
 from __future__ import annotations
 
@@ -33,6 +44,7 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
                                              device=device) if generator is None else generator
         if getattr(self.generator, "is_causal", False):
             raise ValueError("BidirectionalDiffusionInferencePipeline needs WanDiffusionWrapper(is_causal=False)")
+        self.i2v = getattr(self.generator, "model_type", "t2v") == "i2v"
         self.geometry = self.generator.geometry
         self.text_encoder = WanTextEncoder(device=device) if text_encoder is None else text_encoder
         self.vae = WanVAEWrapper(geometry=self.geometry, device=device) if vae is None else vae
@@ -96,7 +108,9 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
             st = dict(latents=latents, flow=torch.empty((2,) + shape, dtype=torch.bfloat16, device=dev),
                       t=torch.empty(1, dtype=torch.float32, device=dev), sched=sched, n=len(sched.timesteps), graph=None,
                       timesteps=self.timesteps,
-                      concurrent=bool(concurrent), share=engine.shared_block0_buffer(F) if share else None, ws2=None)
+                      concurrent=bool(concurrent), share=engine.shared_block0_buffer(F) if share else None, ws2=None,
+                      # i2v: the conditioning video, frame-major, read by both forwards of every step and never written by them
+                      y=torch.empty((F, engine.in_dim - 16, g.lat_h, g.lat_w), dtype=torch.bfloat16, device=dev) if self.i2v else None)
             engine.full_workspace(F)                                      # allocations and the stream: outside any capture
             if concurrent:
                 st["ws2"] = engine.full_workspace(F, second=True)
@@ -109,21 +123,30 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
         """One denoise step's launches (bidirectional_diffusion_inference.py:62-76): eager, or recorded into the step graph."""
         gen, pos, neg = self.generator, self.crossattn_cache_pos, self.crossattn_cache_neg
         x, t, flow = st["latents"], st["t"], st["flow"]
+        kw = {} if st["y"] is None else {"y": st["y"]}                    # i2v: both branches see the image (image2video.py arg_null)
         if st["concurrent"]:
             main, side = torch.cuda.current_stream(self.device), self._side_stream
             side.wait_stream(main)                                        # fork
-            gen.flow_full(x, t, pos, out=flow[0])
+            gen.flow_full(x, t, pos, out=flow[0], **kw)
             with torch.cuda.stream(side):
-                gen.flow_full(x, t, neg, out=flow[1], workspace=st["ws2"])
+                gen.flow_full(x, t, neg, out=flow[1], workspace=st["ws2"], **kw)
             main.wait_stream(side)                                        # join: the CFG / solver update needs both
         else:
-            gen.flow_full(x, t, pos, out=flow[0], share_out=st["share"])
-            gen.flow_full(x, t, neg, out=flow[1], share_in=st["share"])
+            gen.flow_full(x, t, pos, out=flow[0], share_out=st["share"], **kw)
+            gen.flow_full(x, t, neg, out=flow[1], share_in=st["share"], **kw)
         # flow = uncond + g (cond - uncond); latents = scheduler.step(flow): one fused kernel, scalars and next t from device tables
         st["sched"].step_cfg_table(flow[0], flow[1], x, t)
 
-    def inference(self, noise: torch.Tensor, text_prompts: List[str], return_latents=False) -> torch.Tensor:
-        """noise [1, F, 16, h, w] (F up to 24).  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the latents [1, F, 16, h, w])."""
+    def inference(self, noise: torch.Tensor, text_prompts: List[str], return_latents=False,
+                  image_condition: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+        """noise [1, F, 16, h, w] (F up to 24).  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the latents [1, F, 16, h, w]).
+        `image_condition`: {"clip_fea": [257, 1280], "y": [20, F, h, w]} (i2v_condition.build_image_condition) -- required over an
+        i2v generator, a ValueError over a t2v one."""
+        if image_condition is not None and not self.i2v:
+            raise ValueError("BidirectionalDiffusionInferencePipeline: image_condition needs a model_type 'i2v' generator; this one is t2v")
+        if self.i2v and (image_condition is None or image_condition.get("clip_fea") is None or image_condition.get("y") is None):
+            raise ValueError("BidirectionalDiffusionInferencePipeline: a model_type 'i2v' generator needs image_condition = "
+                             "{'clip_fea', 'y'} (i2v_condition.build_image_condition)")
         batch_size, num_frames, num_channels, height, width = noise.shape
         assert batch_size == 1, "batch size 1"
         assert (num_channels, height, width) == (16, self.geometry.lat_h, self.geometry.lat_w), tuple(noise.shape)
@@ -141,6 +164,12 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
             st = self._step_state(noise)
             self.timesteps = st["timesteps"]
             st["latents"].copy_(noise[0].to(device=dev, dtype=torch.bfloat16))
+            if self.i2v:                                                  # in place: the step graph holds these addresses
+                y = self.generator.frame_major_y(image_condition["y"])
+                if y.shape[0] != num_frames:
+                    raise ValueError(f"image_condition['y'] holds {y.shape[0]} latent frames, the noise {num_frames}")
+                st["y"].copy_(y)
+                self.generator.set_image(image_condition["clip_fea"])
             st["sched"].reset_step_table(st["t"])
             n = st["n"]
             if st["graph"] is not None:

@@ -29,6 +29,9 @@ class BidirectionalInferencePipeline(torch.nn.Module):
                                              device=device) if generator is None else generator
         if getattr(self.generator, "is_causal", False):
             raise ValueError("BidirectionalInferencePipeline needs WanDiffusionWrapper(is_causal=False)")
+        if getattr(self.generator, "model_type", "t2v") != "t2v":
+            raise ValueError("BidirectionalInferencePipeline is text-to-video only (no few-step i2v checkpoint exists); sample a "
+                             "model_type 'i2v' generator with BidirectionalDiffusionInferencePipeline(image_condition=...)")
         self.geometry = self.generator.geometry
         self.text_encoder = WanTextEncoder(device=device) if text_encoder is None else text_encoder
         self.vae = WanVAEWrapper(geometry=self.geometry, device=device) if vae is None else vae

@@ -485,7 +485,12 @@ class WanDiffusionWrapper(torch.nn.Module):
     ``is_causal=False`` is the reference's other branch: WanModel, the base (bidirectional) Wan2.1-T2V weights.  ``model`` is then a
     plain handle, ``uniform_timestep`` is True and ``forward(noisy, conditional_dict, timestep)`` -- no caches -- is ONE whole-clip
     forward at ``timestep[:, 0]`` (DitEngine.forward_full: frame i at position i, every frame sees every frame, no KV cache);
-    ``seq_len`` becomes the call's token count.  The pipelines' graphs use ``flow_full`` / ``fewstep_update``."""
+    ``seq_len`` becomes the call's token count.  The pipelines' graphs use ``flow_full`` / ``fewstep_update``.
+
+    ``is_causal=False`` also serves the Wan-I2V model type (``model_type`` 'i2v' in the config: the released Wan2.1-I2V-14B-480P /
+    -720P weights, sampled over the whole clip as ``WanI2V.generate`` does): ``forward`` then takes ``clip_fea`` and ``y`` from
+    ``conditional_dict`` (as ``WanFPSWrapper`` does), ``flow_full`` takes the frame-major ``y`` next to x, and ``set_image``
+    rebuilds the per-layer image K / V IN PLACE -- one pair per wrapper, whose addresses a captured step graph holds."""
 
     def __init__(self, model_name="Wan2.1-T2V-14B", timestep_shift=8.0, is_causal=False, local_attn_size=-1, sink_size=0,
                  *, model_config: Optional[dict] = None, geometry: Optional[Geometry] = None, device="cuda:0", max_frames: int = 7):
@@ -501,15 +506,18 @@ class WanDiffusionWrapper(torch.nn.Module):
         if cfg is None:
             cfg = WAN_CONFIGS["14B" if "14B" in model_name else "1.3B"]
         self.engine = DitEngine(cfg, self.geometry.lat_h, self.geometry.lat_w, device, max_frames=max_frames)
-        if self.engine.model_type != "t2v":
-            raise ValueError("WanDiffusionWrapper: the generator is a t2v model (the few-step causal one and the bidirectional one alike)")
+        if self.engine.model_type != "t2v" and self.is_causal:
+            raise ValueError("WanDiffusionWrapper: the few-step causal generator is a t2v model (the i2v model type is bidirectional: "
+                             "is_causal=False)")
         self.local_attn_size = int(local_attn_size)
         # is_causal=False: WanModel, the whole clip in one forward (DitEngine.forward_full); nothing of the causal cache applies
         self.model = _CausalModelHandle(self.engine, self.local_attn_size, sink_size) if self.is_causal else _ModelHandle(self.engine)
         self._ctx: List[tuple] = []               # is_causal=False: (prompt_embeds, its version, CrossKV) of the last two prompts
         if disk_sd is not None:
             self.engine.load_state_dict(disk_sd)
-        self.model_type = "t2v"
+        self.model_type = self.engine.model_type
+        self._clip_src = None                 # i2v: (clip_fea tensor, its version counter) the image K / V were built from
+        self._img_kv = None                   # i2v: the wrapper's one (img_k, img_v) pair, refreshed in place by set_image
         self.uniform_timestep = not is_causal
         self.scheduler = FlowMatchScheduler(shift=timestep_shift, sigma_min=0.0, extra_one_step=True)
         self.scheduler.set_timesteps(1000, training=True)
@@ -598,12 +606,40 @@ class WanDiffusionWrapper(torch.nn.Module):
     # -- is_causal=False: WanModel.forward over the whole clip (wan/modules/model.py, utils/wan_wrapper.py:277-281) ------------------
     def flow_full(self, x: torch.Tensor, t: torch.Tensor, crossattn_cache: CrossAttnCache, out: Optional[torch.Tensor] = None,
                   share_out: Optional[torch.Tensor] = None, share_in: Optional[torch.Tensor] = None,
-                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  workspace: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One whole-clip forward: x [F, 16, h, w] bf16, t ONE float32 on the device (uniform_timestep).  Stateless attention; the
         text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch: a captured graph
-        serves every later prompt).  share_out / share_in / workspace as in DitEngine.forward_full."""
+        serves every later prompt).  share_out / share_in / workspace as in DitEngine.forward_full.  i2v model type: `y`
+        [F, 20, h, w] bf16 (frame-major) is required and `set_image` must have run; the image K / V it fills keep their address, so
+        a captured graph serves every later image too."""
         return self.engine.forward_full(x, t, crossattn_cache.k_all, crossattn_cache.v_all, out=out, share_out=share_out,
-                                        share_in=share_in, workspace=workspace)
+                                        share_in=share_in, workspace=workspace, y=y)
+
+    def set_image(self, clip_fea: torch.Tensor) -> None:
+        """i2v model type: (re)build the per-layer image K / V of `clip_fea` ([257, 1280] or [1, 257, 1280]) into the wrapper's one
+        static pair -- allocated and attached to the engine on first use, written in place afterwards -- unless they were built from
+        this very tensor and it was not written since."""
+        if self.model_type != "i2v":
+            raise ValueError("WanDiffusionWrapper.set_image: the generator is a t2v model")
+        if self._clip_src is not None and self._clip_src[0] is clip_fea and self._clip_src[1] == clip_fea._version:
+            return
+        fea = clip_fea[0] if clip_fea.dim() == 3 else clip_fea
+        if self._img_kv is not None and self._img_kv[0].shape[1] != fea.shape[0]:
+            raise ValueError(f"WanDiffusionWrapper.set_image: {fea.shape[0]} image tokens, the attached K / V hold {self._img_kv[0].shape[1]}")
+        first = self._img_kv is None
+        self._img_kv = self.engine.precompute_image_context(fea, out=self._img_kv)
+        if first:
+            self.engine.set_image_kv(*self._img_kv)
+        self._clip_src = (clip_fea, clip_fea._version)
+
+    def frame_major_y(self, y) -> torch.Tensor:
+        """The conditioning video as the reference passes it ([20, F, h, w], a list of one such, or [1, 20, F, h, w]) -> [F, 20, h, w]
+        bf16 on the engine's device, the layout `flow_full` reads."""
+        yy = y[0] if isinstance(y, (list, tuple)) or y.dim() == 5 else y
+        e = self.engine
+        if yy.dim() != 4 or yy.shape[0] != e.in_dim - 16 or tuple(yy.shape[2:]) != (e.lat_h, e.lat_w):
+            raise ValueError(f"WanDiffusionWrapper: y is {tuple(yy.shape)}, expected [{e.in_dim - 16}, F, {e.lat_h}, {e.lat_w}]")
+        return yy.to(device=e.device, dtype=torch.bfloat16).permute(1, 0, 2, 3).contiguous()
 
     def _context_kv(self, prompt_embeds: torch.Tensor):
         """Per-layer text K / V of `prompt_embeds`, kept for the last two prompts (the cond and the uncond one of a CFG loop) as
@@ -617,12 +653,23 @@ class WanDiffusionWrapper(torch.nn.Module):
 
     def _forward_full(self, noisy_image_or_video: torch.Tensor, conditional_dict: dict, timestep: torch.Tensor):
         assert noisy_image_or_video.shape[0] == 1, "batch size 1 (as every reference entry point)"
+        clip_fea = y = None
+        if self.model_type == "i2v":                                        # model.py:672-673: clip_fea and y are required
+            clip_fea, y = conditional_dict.get("clip_fea"), conditional_dict.get("y")
+            if clip_fea is None or y is None:
+                raise ValueError("WanDiffusionWrapper: an i2v model needs clip_fea and y in conditional_dict (model.py:672-673)")
         x = noisy_image_or_video[0].to(device=self.engine.device, dtype=torch.bfloat16).contiguous()
         nF = x.shape[0]
         self.seq_len = nF * self.engine.S                                  # the call's token count: nothing is padded
         ts = timestep.reshape(noisy_image_or_video.shape[0], -1)[:, 0]      # input_timestep = timestep[:, 0] (:236-237)
+        ys = None
+        if self.model_type == "i2v":
+            ys = self.frame_major_y(y)
+            if ys.shape[0] != nF:
+                raise ValueError(f"WanDiffusionWrapper: y holds {ys.shape[0]} frames, the latents {nF}")
+            self.set_image(clip_fea)
         kv = self._context_kv(conditional_dict["prompt_embeds"])
-        flow = self.engine.forward_full(x, ts.to(device=x.device, dtype=torch.float32), kv[0], kv[1], cross_rows=kv.rows)
+        flow = self.engine.forward_full(x, ts.to(device=x.device, dtype=torch.float32), kv[0], kv[1], cross_rows=kv.rows, y=ys)
         x0 = torch.empty_like(x)
         self.fewstep_update(flow, x, None, x0, self.sigma_x0(ts.cpu()[0]))
         return flow.unsqueeze(0), x0.unsqueeze(0)
