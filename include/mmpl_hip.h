@@ -398,7 +398,9 @@ int mmpl_taehv_decode(MmplTaehv* v, const void* z, int n_frames, void* out, int 
  * [norm1.weight, pack:attn.{q,k,v}.weight[3*dim_attn,dim], attn.o.weight, pos_embedding.embedding.weight[num_buckets,heads],
  *  norm2.weight, ffn.gate.0.weight, ffn.fc1.weight, ffn.fc2.weight].
  * mmpl_t5_encode: ids / mask dev int32 [text_len]; bucket dev int32 [2*text_len-1] = relative-position bucket of (j - i)
- * at index j - i + text_len - 1 (t5.py:240-264, computed host-side); out dev bf16 [text_len, dim], padding rows zeroed. */
+ * at index j - i + text_len - 1 (t5.py:240-264, computed host-side); out dev bf16 [text_len, dim], padding rows zeroed.
+ * Unbound weights, a null ids / mask / bucket / out / workspace ("null argument") and a workspace that is too small are rejected
+ * before the first HIP call.  mmpl_t5_workspace_bytes(NULL) is 0. */
 typedef struct MmplT5Config {
   int vocab, dim, dim_attn, dim_ffn, num_heads, num_layers, num_buckets, text_len;
   float eps;

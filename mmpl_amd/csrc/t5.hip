@@ -183,11 +183,12 @@ int mmpl_t5_bind_weights(MmplT5* h, const void* const* ptrs, int n) {
   return 0;
 }
 
-size_t mmpl_t5_workspace_bytes(const MmplT5* h) { return carve(h->cfg, nullptr).bytes; }
+size_t mmpl_t5_workspace_bytes(const MmplT5* h) { return h ? carve(h->cfg, nullptr).bytes : 0; }
 
 int mmpl_t5_encode(MmplT5* h, const int* ids, const int* mask, const int* bucket, void* out, void* workspace, size_t workspace_bytes,
                    mmpl_stream_t stream) {
   if (!h || h->w.empty()) return mmpl_set_error("mmpl_t5_encode", "weights not bound");
+  if (!ids || !mask || !bucket || !out || !workspace) return mmpl_set_error("mmpl_t5_encode", "null argument");
   const MmplT5Config& c = h->cfg;
   Ws w = carve(c, workspace);
   if (workspace_bytes < w.bytes) return mmpl_set_error("mmpl_t5_encode", "workspace too small");

@@ -18,15 +18,16 @@ def mlp_proj(p: Dict[str, torch.Tensor], image_embeds: torch.Tensor) -> torch.Te
 
 
 def i2v_cross_attention(p: Dict[str, torch.Tensor], x: torch.Tensor, context: torch.Tensor, num_heads: int, eps: float = 1e-6,
-                        attn_fn=sdpa) -> torch.Tensor:
-    """model.py:238-266.  x: [B, L1, C]; context: [B, 257 + L2, C] (image tokens first)."""
+                        attn_fn=sdpa, acc=torch.float32) -> torch.Tensor:
+    """model.py:238-266.  x: [B, L1, C]; context: [B, 257 + L2, C] (image tokens first).  acc: the dtype of the RMS norms (float64
+    with a float64 attn_fn runs the oracle unrounded on float64 weights)."""
     context_img, context = context[:, :257], context[:, 257:]
     b, n, d = x.size(0), num_heads, x.size(-1) // num_heads
     lin = lambda t, name: F.linear(t, p[name + ".weight"], p[name + ".bias"])
-    q = rms_norm(lin(x, "q"), p["norm_q.weight"], eps).view(b, -1, n, d)
-    k = rms_norm(lin(context, "k"), p["norm_k.weight"], eps).view(b, -1, n, d)
+    q = rms_norm(lin(x, "q"), p["norm_q.weight"], eps, acc).view(b, -1, n, d)
+    k = rms_norm(lin(context, "k"), p["norm_k.weight"], eps, acc).view(b, -1, n, d)
     v = lin(context, "v").view(b, -1, n, d)
-    k_img = rms_norm(lin(context_img, "k_img"), p["norm_k_img.weight"], eps).view(b, -1, n, d)
+    k_img = rms_norm(lin(context_img, "k_img"), p["norm_k_img.weight"], eps, acc).view(b, -1, n, d)
     v_img = lin(context_img, "v_img").view(b, -1, n, d)
     img_x = attn_fn(q, k_img, v_img)
     x = attn_fn(q, k, v)

@@ -85,9 +85,9 @@ def fps_rope_apply(x: torch.Tensor, frame_ids: Sequence[int], gh: int, gw: int, 
 
 
 # --------------------------------------------------------------------------- norms
-def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
-    """model.py:78-86: fp32 norm over the FULL last dim, cast back, then * weight."""
-    xf = x.float()
+def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float, acc=torch.float32) -> torch.Tensor:
+    """model.py:78-86: fp32 (`acc`) norm over the FULL last dim, cast back, then * weight."""
+    xf = x.to(acc)
     return (xf * torch.rsqrt(xf.pow(2).mean(dim=-1, keepdim=True) + eps)).type_as(x) * w
 
 

@@ -39,6 +39,11 @@ ATTN_AUTO, ATTN_LOCKSTEP, ATTN_W64 = 0, 1, 3                                    
 GEMM_SCRATCH = {"qkv": True, "o": True, "cross_q": True, "cross_o": True, "ffn0": True, "ffn2": True,
                 "patch": False, "time0": False, "time2": False, "time_proj": False, "head": False,
                 "text0": False, "text2": False, "ctx_k": False, "ctx_v": False}
+# The encoder compositions (tests/encoder_chain.py: mmpl_t5_encode, mmpl_clip_visual, mmpl_i2v_*) pass neither to any of their GEMMs.
+GEMM_SCRATCH.update({name: False for name in (
+    "t5_qkv", "t5_scores", "t5_pv", "t5_o", "t5_gate", "t5_fc1", "t5_fc2",
+    "clip_patch", "clip_qkv", "clip_proj", "clip_mlp0", "clip_mlp2",
+    "proj_fc1", "proj_fc2", "img_k", "img_v", "i2v_q", "i2v_o")})
 
 # The wiring of one forward (causal_fps_model.py:338-360: e = (modulation + e0).chunk(6); norm1 * (1 + e[1]) + e[0]; y * e[2];
 # norm2 * (1 + e[4]) + e[3]; y * e[5]; :393: head e = (head.modulation + e).chunk(2), norm * (1 + e[1]) + e[0]).

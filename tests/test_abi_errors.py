@@ -49,6 +49,32 @@ def test_t5_and_vae_argument_errors():
     assert lib.mmpl_dit_attn_history_bytes(None, 3) == 0 and lib.mmpl_attn_history_bytes(256 * 3 + 1, 12) == 256 + 12 * 4 * 4 * 128 * 2
 
 
+def test_t5_encode_rejects_null_arguments_before_any_launch():
+    """mmpl_t5_bind_weights only stores pointers, so a bound handle is built here with placeholder addresses that nothing reads: each
+    of ids, mask, bucket, out and workspace missing is a "null argument" (and no launch: there is no GPU here to launch on), and the
+    size query of a null handle is 0."""
+    lib = _lib.load()
+    cfg = _lib.MmplT5Config(vocab=1000, dim=256, dim_attn=256, dim_ffn=512, num_heads=4, num_layers=2, num_buckets=32, text_len=64, eps=1e-6)
+    h = C.c_void_p()
+    assert lib.mmpl_t5_create(C.byref(cfg), C.byref(h)) == 0
+    try:
+        nb = lib.mmpl_t5_workspace_bytes(h)
+        assert nb > 0 and lib.mmpl_t5_workspace_bytes(None) == 0
+        P = C.c_void_p(0x10000)
+        assert "weights not bound" in _err(lib.mmpl_t5_encode(h, P, P, P, P, P, nb, None))
+        n = lib.mmpl_t5_num_weights(C.byref(cfg))
+        assert n == 2 + 8 * 2
+        assert lib.mmpl_t5_bind_weights(h, (C.c_void_p * n)(*([0x10000] * n)), n) == 0
+        for missing in range(5):                           # ids, mask, bucket, out, workspace
+            args = [P] * 5
+            args[missing] = None
+            assert "null argument" in _err(lib.mmpl_t5_encode(h, *args, nb, None)), missing
+        assert "null argument" in _err(lib.mmpl_t5_encode(h, None, None, None, None, None, 0, None))
+        assert "workspace too small" in _err(lib.mmpl_t5_encode(h, P, P, P, P, P, nb - 1, None))
+    finally:
+        lib.mmpl_t5_destroy(h)
+
+
 def test_kernel_entry_points_reject_bad_shapes():
     lib = _lib.load()
     # K must be a multiple of 64, leading dimensions of 8 elements: rejected before any launch
