@@ -393,6 +393,36 @@ int mmpl_taehv_reset(MmplTaehv* v);
 int mmpl_taehv_decode(MmplTaehv* v, const void* z, int n_frames, void* out, int out_format, int* n_px_frames_out, void* workspace,
                       size_t workspace_bytes, mmpl_stream_t stream);
 
+/* ---- TAEHV encoder: the other half of demo_utils/taehv.py (TAEHV.encode_video), pixels -> the streamed block's latents ----
+ * A handle of its own.  Weights: mmpl_taehv_enc_num_weights() dev pointers in the order of mmpl_taehv_enc_weight_name(i) = exactly
+ * the reference's "encoder.*" state-dict keys.  Every "*.weight" is bound fragment-major as for the decoder (a MemBlock's first conv
+ * and TPool(2) keep the reference's input-channel order, [x, past] and [frame 2t, frame 2t + 1]); encoder.0.weight is bound as the
+ * packed matrix [64, 32], column k = (3 ky + kx) * 3 + c, columns 27 .. 31 zero, as ONE fragment-major chunk with ntaps = 1;
+ * encoder.17.weight has 16 rows; biases are bf16 [Cout].  mmpl_amd/taehv.py is the reference packer.  mmpl_taehv_enc_create and
+ * mmpl_taehv_enc_workspace_bytes make no HIP call.
+ * mmpl_taehv_encode CONTINUES the current video: px are its NEXT n_frames pixel frames, in_format 0: dev float32
+ * [n_frames, 3, 8 lat_h, 8 lat_w] in [0, 1]; in_format 1: dev uint8 [n_frames, 8 lat_h, 8 lat_w, 3], read as bf16(u / 255).
+ * n_frames must be >= 4 and a multiple of 4 (4 pixel frames per latent frame; a frame pair of the temporal pooling never straddles
+ * two calls); anything else is an error.  z_out receives dev bf16 [n_frames / 4, 16, lat_h, lat_w] in the pipeline's normalised
+ * latent space (no mean / std); the count goes to *n_latents_out (may be NULL).  The first call after create / reset starts from
+ * zero memories.  A video encoded in any split is bit-identical to the one-shot encode.
+ * workspace: caller-owned, mmpl_taehv_enc_workspace_bytes(e) bytes, holds the nine MemBlock memories: the SAME pointer from one
+ * reset to the next (another pointer or a smaller size is an error), written by nothing else in between, cleared (asynchronously,
+ * on `stream`) by the first encode after create / reset only.  All argument checks run before the first HIP call.  Everything is
+ * queued on `stream`: no host synchronisation, no read-back, no allocation; the launch sequence and every address are the same from
+ * call to call, so a call (not a video's first) can be captured into a hipGraph and replayed as "the next frames". */
+typedef struct MmplTaehvEnc MmplTaehvEnc;
+int mmpl_taehv_enc_num_weights(void);
+const char* mmpl_taehv_enc_weight_name(int i);
+int mmpl_taehv_enc_create(int lat_h, int lat_w, MmplTaehvEnc** out);
+void mmpl_taehv_enc_destroy(MmplTaehvEnc* e);
+int mmpl_taehv_enc_bind_weights(MmplTaehvEnc* e, const void* const* dev_ptrs, int n);
+size_t mmpl_taehv_enc_workspace_bytes(MmplTaehvEnc* e);
+/* The next mmpl_taehv_encode starts a new video (and may bind another workspace).  Host-side only. */
+int mmpl_taehv_enc_reset(MmplTaehvEnc* e);
+int mmpl_taehv_encode(MmplTaehvEnc* e, const void* px, int in_format, int n_frames, void* z_out, int* n_latents_out, void* workspace,
+                      size_t workspace_bytes, mmpl_stream_t stream);
+
 /* ---- umT5 text encoder (wan/modules/t5.py:267-312 behind WanTextEncoder, utils/wan_wrapper.py:15-51) ----
  * Weights (bf16 dev pointers): [token_embedding.weight, norm.weight] then per block
  * [norm1.weight, pack:attn.{q,k,v}.weight[3*dim_attn,dim], attn.o.weight, pos_embedding.embedding.weight[num_buckets,heads],
@@ -509,6 +539,19 @@ int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long
                     int Nsplit, int relu, const void* skip, long long fss, void* keep, mmpl_stream_t stream);
 /* taehv_prep_kernel: z [16, h, w] -> bf16(tanh(z / 3) * 3) -> channels [0, 16) of the interior of dst [h + 2, w + 2, 32] (16-byte aligned). */
 int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream);
+/* taehv_conv_in_kernel (taehv_enc_kernels.hip), the encoder's input layer: conv 3->64 3x3 (zero padding 1) + bias + ReLU straight
+ * from the caller's pixels.  px: in_format 0 dev float32 [T, 3, H, W] (4-byte aligned); 1 dev uint8 [T, H, W, 3], read as
+ * bf16(u / 255).  Wfrag: the packed [64, 32] matrix (k = (3 ky + kx) * 3 + c, k >= 27 zero) fragment-major, 2048 elements; bias [64].
+ * dst: T frames [H + 2, W + 2, 64] of stride fsd (elements, % 4), interiors only. */
+int mmpl_taehv_conv_in(const void* px, int in_format, const void* Wfrag, const void* bias, int T, int H, int W, void* dst,
+                       long long fsd, mmpl_stream_t stream);
+/* taehv_conv_s2_kernel: 3x3 stride-2 conv without bias, out = bf16(relu?(acc)): output (y, x) reads padded source rows 2y .. 2y + 2,
+ * columns 2x .. 2x + 2.  src: T frames [2 Ho + 2, 2 Wo + 2, C] of stride fs (elements, % 8), C % 32 == 0; Wfrag: the fragment-major
+ * packing of [Nw, 9 C], Nw % 64 == 0; dst: T frames [Ho + 2, Wo + 2, Nw] of stride fsd (% 4), interiors only. */
+int mmpl_taehv_conv_s2(const void* src, long long fs, int C, const void* Wfrag, int Nw, int T, int Ho, int Wo, void* dst,
+                       long long fsd, int relu, mmpl_stream_t stream);
+/* taehv_z_out_kernel: head frames src [T, h + 2, w + 2, 16] (16-byte aligned) -> out bf16 [>= f_out + T, 16, h, w] at frame f_out. */
+int mmpl_taehv_z_out(const void* src, void* out, int T, int h, int w, int f_out, mmpl_stream_t stream);
 /* The GEMM (gemm.hip) in every form the DiT forward, T5, CLIP and the VAE launch it, for tests/test_gemm_forms_gpu.py: the arguments
  * of mmpl_gemm_scratch plus what only the internal callers could set.  mmpl_gemm / _tickets / _scratch are unchanged.
  *   epi     0-4 as mmpl_gemm; 5: C is dev float32 [M, ldc], C = float(alpha * acc), 16-byte aligned, bias must be NULL; 6: bias, and the columns

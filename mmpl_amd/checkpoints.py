@@ -111,6 +111,16 @@ def read_taehv(path: str) -> Dict[str, torch.Tensor]:
     return out
 
 
+def read_taehv_encoder(path: str) -> Dict[str, torch.Tensor]:
+    """The ENCODER of a ``taew2_1.pth``-style file: its ``encoder.*`` tensors under their own keys (what
+    ``TaehvEncoderEngine.load_state_dict`` takes)."""
+    sd = read_state_dict(path)
+    out = {k: v for k, v in sd.items() if k.startswith("encoder.")}
+    if not out:
+        raise ValueError(f"{path}: no 'encoder.*' tensors (a decoder-only TAEHV file has no encoder to load)")
+    return out
+
+
 def infer_t5_config(sd: Dict[str, torch.Tensor]) -> dict:
     """Encoder dimensions from the tensors of a umT5 state dict (wan/modules/t5.py:267-312 key layout)."""
     vocab, dim = sd["token_embedding.weight"].shape

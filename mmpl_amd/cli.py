@@ -138,12 +138,74 @@ def solver_refusal(args, fewstep: bool):
     return None
 
 
+def read_clip(path: str) -> torch.Tensor:
+    """A clip as this CLI writes it -> uint8 [T, H, W, 3] on the host: the ``.pt`` tensor, or the MJPEG ``.avi`` of
+    utils/video_io.py."""
+    if path.lower().endswith(".avi"):
+        from .utils.video_io import read_mjpeg_avi
+        return torch.from_numpy(read_mjpeg_avi(path).copy())
+    clip = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(clip, torch.Tensor) or clip.dtype != torch.uint8 or clip.dim() != 4 or clip.shape[-1] != 3:
+        raise ValueError("not a uint8 [T, H, W, 3] tensor")
+    return clip
+
+
+def extend_context_frames(args) -> int:
+    """--extend_context in latent frames (default: one block, num_frame_per_block)."""
+    n = getattr(args, "extend_context", None)
+    return int(getattr(args, "num_frame_per_block", 1)) if n is None else int(n)
+
+
+def extend_refusal(args, fewstep: bool):
+    """Why --extend FILE cannot run this command line (None = it can, or it was not asked for).  The clip's last 4 N frames are
+    encoded by the tiny autoencoder's encoder (TAEHVWrapper.encode_stream) into N latent frames, handed to the few-step pipeline
+    as ``initial_latent``, and the new blocks are streamed and decoded by the same autoencoder: hence a few-step config, --stream
+    and --preview_vae.  ``main`` puts num_frame_per_block, kv_window (the KV window in latent frames) and pixel_hw on ``args``."""
+    path = getattr(args, "extend", None)
+    if path is None:
+        if getattr(args, "extend_context", None) is not None:
+            return "--extend_context: only with --extend FILE"
+        return None
+    if not fewstep:
+        return ("--extend: continuing a clip needs a few-step config (one with denoising_step_list, e.g. self_forcing_dmd.yaml); "
+                "the 50-step pipeline rolls over its own chunks")
+    if getattr(args, "bidirectional", False):
+        return "--extend: --bidirectional denoises one whole clip; there is no earlier video to continue"
+    if getattr(args, "i2v", False) or getattr(args, "i2v_model", False):
+        return "--extend: the few-step pipeline (config with denoising_step_list) is text-to-video only; drop --i2v"
+    if not getattr(args, "stream", False) or getattr(args, "preview_vae", None) is None:
+        return ("--extend: the context is encoded, and the new blocks decoded, by the tiny preview autoencoder on the streaming "
+                "path: add --stream --preview_vae [PATH] (a Wan-VAE-encoded context is not supported)")
+    block = int(getattr(args, "num_frame_per_block", 1))
+    n = extend_context_frames(args)
+    if n < block or n % block:
+        return f"--extend_context {n}: a positive multiple of num_frame_per_block ({block}) latent frames"
+    new = int(getattr(args, "num_output_frames", 21)) * int(getattr(args, "duration", 1))
+    window = int(getattr(args, "kv_window", 21))
+    if not getattr(args, "rolling", False) and n + new > window:
+        return (f"--extend: {n} context + {new} new latent frames do not fit the KV window of {window} frames; add --rolling or "
+                f"use a smaller --num_output_frames (at most {window - n})")
+    if not os.path.isfile(path):
+        return f"--extend {path}: no such file"
+    try:
+        clip = read_clip(path)
+    except Exception as e:
+        return f"--extend {path}: not a clip this CLI wrote (.pt uint8 [T, H, W, 3], or its MJPEG .avi): {e}"
+    if clip.shape[0] < 4 * n:
+        return f"--extend {path}: {clip.shape[0]} frames, the context of {n} latent frames needs {4 * n}"
+    hw = getattr(args, "pixel_hw", None)
+    if hw is not None and tuple(clip.shape[1:3]) != tuple(hw):
+        return f"--extend {path}: frames of {clip.shape[1]} x {clip.shape[2]} pixels, this run generates {hw[0]} x {hw[1]}"
+    return None
+
+
 def build_preview_vae(args, dev, geo):
-    """TAEHVWrapper for --preview_vae [PATH]: the checkpoint at PATH (default ../wan_models/taew2_1.pth), or seeded weights with --synthetic."""
+    """TAEHVWrapper for --preview_vae [PATH]: the checkpoint at PATH (default ../wan_models/taew2_1.pth), or seeded weights with
+    --synthetic (both halves: the decoder, and the encoder --extend needs)."""
     from .wan_wrapper import TAEHVWrapper
     if args.synthetic:
-        from .synthetic import taehv_state_dict
-        return TAEHVWrapper(geometry=geo, device=dev, state_dict=taehv_state_dict(seed=4))
+        from .synthetic import taehv_encoder_state_dict, taehv_state_dict
+        return TAEHVWrapper(geometry=geo, device=dev, state_dict={**taehv_state_dict(seed=4), **taehv_encoder_state_dict(seed=5)})
     path = args.preview_vae or None
     if path is not None and not os.path.exists(path):
         raise SystemExit(f"--preview_vae {path}: no such file")
@@ -231,6 +293,12 @@ def main(argv=None):
                     "(the KV window in latent frames; -1 = 21)")
     ap.add_argument("--sink_size", type=int, default=None, help="few-step configs: override model_kwargs.sink_size (the first "
                     "frames of the video that --rolling never evicts)")
+    ap.add_argument("--extend", type=str, default=None, metavar="FILE",
+                    help="few-step configs with --stream --preview_vae: continue FILE, a clip this CLI wrote (.pt uint8 [T, H, W, 3] or "
+                         "its MJPEG .avi) -- its last frames are encoded by the tiny autoencoder into the pipeline's initial_latent "
+                         "and --num_output_frames NEW latent frames follow; the written clip is the context frames plus the new ones")
+    ap.add_argument("--extend_context", type=int, default=None, metavar="N",
+                    help="with --extend: latent frames of context (the clip's last 4 N frames); default num_frame_per_block, a multiple of it")
     args = ap.parse_args(argv)
     i2v_clip = bool(args.bidirectional and args.i2v_model)               # the whole-clip Wan-I2V model type: WanI2V.generate's defaults
     if args.sampling_steps is None:
@@ -265,6 +333,14 @@ def main(argv=None):
         why = fewstep_refusal(args, world)
         if why is not None:
             ap.error(why)
+    geo = Geometry(*args.latent_hw) if args.latent_hw else Geometry.named(args.resolution)
+    las = args.local_attn_size if args.local_attn_size is not None else (getattr(config, "model_kwargs", None) or {}).get("local_attn_size", -1)
+    args.num_frame_per_block = int(getattr(config, "num_frame_per_block", 1))
+    args.kv_window = geo.frames_per_chunk if int(las) == -1 else int(las)
+    args.pixel_hw = tuple(geo.pixel_hw)
+    why = extend_refusal(args, fewstep)
+    if why is not None:
+        ap.error(why)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.dist_backend == "gloo":
         local_rank %= max(torch.cuda.device_count(), 1)
@@ -280,7 +356,6 @@ def main(argv=None):
 
     from .pipeline import CausalFPSInferencePipeline
     from .wan_wrapper import SyntheticTextEncoder, WanFPSWrapper, WanVAEWrapper
-    geo = Geometry(*args.latent_hw) if args.latent_hw else Geometry.named(args.resolution)
     mcfg = WAN_CONFIGS[args.model]
     if args.bidirectional:
         return _main_bidirectional(config, args, dev, geo, mcfg)
@@ -424,6 +499,15 @@ def _main_fewstep(config, args, dev, geo, mcfg):
     pipe = build_fewstep_pipeline(config, args, dev, geo, mcfg)
     os.makedirs(args.output_folder, exist_ok=True)
     shape = [1, args.num_output_frames * args.duration, 16, geo.lat_h, geo.lat_w]
+    context_px, initial = None, None
+    if getattr(args, "extend", None):
+        # --extend FILE: the clip's last 4 N frames -> N latent frames (a video of their own, from zero memories) = initial_latent
+        if pipe.preview_vae.encoder is None:
+            raise SystemExit("--extend: the --preview_vae checkpoint has no 'encoder.*' tensors to encode the context with")
+        context_px = read_clip(args.extend)[-4 * extend_context_frames(args):].contiguous()
+        pipe.preview_vae.encoder.clear_cache()
+        initial = pipe.preview_vae.encode_stream(context_px.to(dev)).unsqueeze(0)                              # [1, N, 16, h, w]
+        pipe.preview_vae.encoder.clear_cache()
     for idx, prompt in enumerate(_prompts(args)):
         g = torch.Generator(device="cpu").manual_seed(args.seed)
         noise = torch.randn(shape, generator=g).to(torch.bfloat16)
@@ -432,7 +516,12 @@ def _main_fewstep(config, args, dev, geo, mcfg):
             import time
             parts, t0 = [], time.perf_counter()
             decoder = "preview" if pipe.preview_vae is not None else "vae"
-            for first, frames in pipe.inference_stream(noise.to(dev), [prompt], output="uint8", decoder=decoder):
+            for first, frames in pipe.inference_stream(noise.to(dev), [prompt], initial_latent=initial, output="uint8", decoder=decoder):
+                if context_px is not None and not parts:     # the context's own decode: the clip keeps the file's frames instead
+                    parts.append(context_px)
+                    continue
+                if context_px is not None:                   # frame numbers of the written clip: the context keeps all 4 N frames
+                    first = sum(p.shape[0] for p in parts)
                 print(f"[mmpl_amd.cli] few-step prompt {idx}: frames {first}..{first + frames.shape[0] - 1} after "
                       f"{time.perf_counter() - t0:.3f} s" + (" (time to the first frames)" if not parts else ""))
                 parts.append(frames)

@@ -340,6 +340,43 @@ int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream
   LAUNCH(taehv_launch_prep((const bf16_t*)z, (bf16_t*)dst, h, w, (hipStream_t)stream), me);
 }
 
+int mmpl_taehv_conv_in(const void* px, int in_format, const void* Wfrag, const void* bias, int T, int H, int W, void* dst,
+                       long long fsd, mmpl_stream_t stream) {
+  const char* me = "mmpl_taehv_conv_in";
+  REJECT(!px || !Wfrag || !bias || !dst, me, "null argument");
+  REJECT(in_format != 0 && in_format != 1, me, "unknown in_format");
+  REJECT(T < 1 || H < 1 || W < 1 || too_many(T, H, W), me, "non-positive size");
+  REJECT(fsd < 0 || fsd % 4, me, "frame stride not a multiple of the access width");
+  REJECT(misaligned(px, in_format == 0 ? 4 : 1) || misaligned(Wfrag, 16) || misaligned(bias, 8) || misaligned(dst, 8), me,
+         "misaligned pointer");
+  TaehvConvInArgs g = {};
+  g.px = px; g.fmt = in_format; g.Wfrag = (const bf16_t*)Wfrag; g.bias = (const bf16_t*)bias; g.T = T; g.H = H; g.W = W;
+  g.dst = (bf16_t*)dst; g.fsd = (long)fsd;
+  LAUNCH(taehv_launch_conv_in(g, (hipStream_t)stream), me);
+}
+
+int mmpl_taehv_conv_s2(const void* src, long long fs, int C, const void* Wfrag, int Nw, int T, int Ho, int Wo, void* dst,
+                       long long fsd, int relu, mmpl_stream_t stream) {
+  const char* me = "mmpl_taehv_conv_s2";
+  REJECT(!src || !Wfrag || !dst, me, "null argument");
+  REJECT(T < 1 || Ho < 1 || Wo < 1 || C < 32 || Nw < 64 || too_many(T, 2L * Ho + 2, 2L * Wo + 2), me, "non-positive size");
+  REJECT(C % 32 || Nw % 64, me, "invalid argument");
+  REJECT(fs < 0 || fsd < 0 || fs % 8 || fsd % 4, me, "frame stride not a multiple of the access width");
+  REJECT(misaligned(src, 16) || misaligned(Wfrag, 16) || misaligned(dst, 8), me, "misaligned pointer");
+  TaehvConvS2Args g = {};
+  g.src = (const bf16_t*)src; g.fs = (long)fs; g.C = C; g.Wfrag = (const bf16_t*)Wfrag; g.Nw = Nw; g.T = T; g.Ho = Ho; g.Wo = Wo;
+  g.dst = (bf16_t*)dst; g.fsd = (long)fsd; g.relu = relu ? 1 : 0;
+  LAUNCH(taehv_launch_conv_s2(g, (hipStream_t)stream), me);
+}
+
+int mmpl_taehv_z_out(const void* src, void* out, int T, int h, int w, int f_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_taehv_z_out";
+  REJECT(!src || !out, me, "null argument");
+  REJECT(T < 1 || h < 1 || w < 1 || f_out < 0 || too_many(T, h + 2L, w + 2L), me, "non-positive size");
+  REJECT(misaligned(src, 16) || misaligned(out, 2), me, "misaligned pointer");
+  LAUNCH(taehv_launch_z_out((const bf16_t*)src, (bf16_t*)out, T, h, w, f_out, (hipStream_t)stream), me);
+}
+
 // One launch of mmpl_launch_layernorm (include/mmpl_hip.h).  The plan is the launcher's own (mmpl_ln_plan, which mmpl_launch_layernorm
 // consults for every choice); it is computed after the checks, because a pipelined kernel's plan asks the device for its occupancy.
 int mmpl_layernorm_ex(const void* x, int ldx, void* y, int ldy, int rows, int d, float eps, const void* scale, const void* shift,

@@ -34,3 +34,29 @@ hipError_t taehv_launch_prep(const bf16_t* z, bf16_t* dst, int h, int w, hipStre
 // head frames [T][H + 2][W + 2][4] bf16 -> fmt 0: float32 [T, 3, H, W] raw; fmt 1: uint8 [T, H, W, 3] = (x.clamp(0, 1) * 255) truncated;
 // frames written at t_out of out
 hipError_t taehv_launch_px_out(const bf16_t* src, void* out, int fmt, int T, int H, int W, int t_out, hipStream_t s);
+
+// ---- the encoder's own kernels (taehv_enc_kernels.hip), used by taehv_enc.hip
+// input layer: pixels -> conv 3->64 3x3 + bias + ReLU -> interiors of T frames [H + 2][W + 2][64] of stride fsd (elements)
+struct TaehvConvInArgs {
+  const void* px; int fmt;   // fmt 0: float32 [T, 3, H, W] in [0, 1]; 1: uint8 [T, H, W, 3], read as bf16(u / 255)
+  const bf16_t* Wfrag;       // the packed [64, 32] matrix, k = (3 ky + kx) * 3 + c, k >= 27 zero: one fragment-major chunk, ntaps 1
+  const bf16_t* bias;        // [64]
+  int T, H, W;
+  bf16_t* dst; long fsd;
+};
+hipError_t taehv_launch_conv_in(const TaehvConvInArgs& g, hipStream_t s);
+
+// 3x3 stride-2 conv without bias: source frames [2 Ho + 2][2 Wo + 2][C] of stride fs -> interiors of frames [Ho + 2][Wo + 2][Nw] of
+// stride fsd; output (y, x) reads padded source rows 2y .. 2y + 2, columns 2x .. 2x + 2
+struct TaehvConvS2Args {
+  const bf16_t* src; long fs; int C;
+  const bf16_t* Wfrag;       // [C / 32][9][Nw / 16][64 lanes][8], as TaehvConvArgs::Wfrag
+  int Nw;                    // output channels, a multiple of 64
+  int T, Ho, Wo;
+  bf16_t* dst; long fsd;
+  int relu;
+};
+hipError_t taehv_launch_conv_s2(const TaehvConvS2Args& g, hipStream_t s);
+
+// head frames [T][h + 2][w + 2][16] bf16 -> planar bf16 [T, 16, h, w] written at frame f_out of out
+hipError_t taehv_launch_z_out(const bf16_t* src, bf16_t* out, int T, int h, int w, int f_out, hipStream_t s);

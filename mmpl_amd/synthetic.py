@@ -272,6 +272,43 @@ def taehv_state_dict(seed: int = 0, dtype=torch.bfloat16, device="cpu") -> "Orde
     return sd
 
 
+def taehv_encoder_layout():
+    """(key, shape, kind) of every tensor of the TAEHV ENCODER (``TAEHV.encoder``, an nn.Sequential of 18 modules), in state_dict
+    order.  kind: 'conv' | 'last' (a MemBlock's third conv) | 'pool' (TPool's 1x1) | 'head' | 'bias'."""
+    c = 64
+    out = [("encoder.0.weight", (c, 3, 3, 3), "conv"), ("encoder.0.bias", (c,), "bias")]
+    i = 2
+    for stride in (2, 2, 1):
+        out.append((f"encoder.{i}.conv.weight", (c, c * stride, 1, 1), "pool"))
+        out.append((f"encoder.{i + 1}.weight", (c, c, 3, 3), "conv"))
+        i += 2
+        for _ in range(3):
+            for j, (cin, kind) in enumerate([(2 * c, "conv"), (c, "conv"), (c, "last")]):
+                out.append((f"encoder.{i}.conv.{2 * j}.weight", (c, cin, 3, 3), kind))
+                out.append((f"encoder.{i}.conv.{2 * j}.bias", (c,), "bias"))
+            i += 1
+    out += [("encoder.17.weight", (16, c, 3, 3), "head"), ("encoder.17.bias", (16,), "bias")]
+    return out
+
+
+def taehv_encoder_state_dict(seed: int = 0, dtype=torch.bfloat16, device="cpu") -> "OrderedDict[str, torch.Tensor]":
+    """Seeded encoder weights in the reference's key layout, activations O(1) through all 41 convolutions: 3x3 convs std
+    sqrt(2 / fan_in), a MemBlock's last conv sqrt(0.5 / fan_in), TPool's 1x1 sqrt(1 / fan_in), the head 1 / sqrt(fan_in), biases
+    std 0.1."""
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape, kind in taehv_encoder_layout():
+        fan_in = 1
+        for s in shape[1:]:
+            fan_in *= s
+        t = torch.randn(*shape, generator=g, device=device)
+        t = t * {"bias": 0.1, "conv": math.sqrt(2.0 / fan_in), "last": math.sqrt(0.5 / fan_in), "pool": math.sqrt(1.0 / fan_in),
+                 "head": 1.0 / math.sqrt(fan_in)}[kind]
+        sd[name] = t.to(dtype)
+    return sd
+
+
 # ---------------------------------------------------------------------------------------------- umT5 encoder weights
 T5_CONFIGS = {
     "umt5-xxl": dict(vocab=256384, dim=4096, dim_attn=4096, dim_ffn=10240, num_heads=64, num_layers=24, num_buckets=32),

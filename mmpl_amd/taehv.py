@@ -1,9 +1,9 @@
-"""Host-side handle of the HIP TAEHV preview decoder (libmmpl_hip.so: mmpl_taehv_*), the engine behind ``TAEHVWrapper``.
+"""Host-side handles of the HIP TAEHV preview autoencoder (libmmpl_hip.so: mmpl_taehv_*), the engines behind ``TAEHVWrapper``.
 
-The "Tiny AutoEncoder" of the reference's demo (demo_utils/taehv.py, checkpoint ``taew2_1.pth`` for Wan 2.1), decoder half: 35
-plain 2-D convolutions, causal in time with one frame of memory per MemBlock.  Takes the reference's state dict as it is
-(``decoder.N...`` keys; encoder keys are ignored), repacks the conv weights once into the kernels' fragment-major layout and
-keeps them on the GPU.  Latents are the pipeline's normalised latents (no mean / std); the output is the network's, nominally
+The "Tiny AutoEncoder" of the reference's demo (demo_utils/taehv.py, checkpoint ``taew2_1.pth`` for Wan 2.1).  ``TaehvEngine`` is
+the decoder half: 35 plain 2-D convolutions, causal in time with one frame of memory per MemBlock.  It takes the reference's
+state dict as it is (``decoder.N...`` keys; encoder keys are ignored), repacks the conv weights once into the kernels'
+fragment-major layout and keeps them on the GPU.  ``TaehvEncoderEngine`` (below) is the encoder half, built the same way.  Latents are the pipeline's normalised latents (no mean / std); the output is the network's, nominally
 [0, 1], and UNTRIMMED like this reference's ``decode_video``: 4 frames per latent frame (``TAEHVWrapper`` drops the first 3).
 """
 from __future__ import annotations
@@ -115,3 +115,90 @@ class TaehvEngine:
             raise ValueError(f"out_format {out_format!r}: 'float' or 'uint8'")
         self.clear_cache()
         return self.decode_stream(latent, out_format=out_format)
+
+
+class TaehvEncoderEngine:
+    """The ENCODER half (``TAEHV.encode_video``; libmmpl_hip.so: mmpl_taehv_enc_* / mmpl_taehv_encode): pixels in [0, 1] -> the
+    pipeline's normalised latents, 4 pixel frames per latent frame, causal in time with one frame of memory per MemBlock.  Takes
+    the reference's state dict as it is (``encoder.N...`` keys; decoder keys are ignored)."""
+
+    def __init__(self, lat_h: int, lat_w: int, device="cuda:0"):
+        self.lat_h, self.lat_w = lat_h, lat_w
+        self.device = torch.device(device)
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._lib.mmpl_taehv_enc_create(lat_h, lat_w, C.byref(h)), "mmpl_taehv_enc_create")
+        self._h = h
+        self._weights: List[torch.Tensor] = []
+        self._ws: Optional[torch.Tensor] = None
+        self.frames_done = 0                                         # pixel frames encoded since clear_cache()
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.mmpl_taehv_enc_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @staticmethod
+    def weight_names() -> List[str]:
+        lib = _lib.load()
+        return [lib.mmpl_taehv_enc_weight_name(i).decode() for i in range(lib.mmpl_taehv_enc_num_weights())]
+
+    @staticmethod
+    def _repack(name: str, t: torch.Tensor) -> torch.Tensor:
+        if name == "encoder.0.weight":
+            # the input layer's packed K: [64, 3, 3, 3] -> [64, 32], column (3 ky + kx) * 3 + c, columns 27 .. 31 zero: one chunk
+            t = t.to(torch.bfloat16).permute(0, 2, 3, 1).reshape(t.shape[0], 27)
+            return VaeEngine._frag_pack(torch.cat([t, t.new_zeros(t.shape[0], 5)], dim=1), 32)
+        return TaehvEngine._repack(name, t)
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        names = self.weight_names()
+        missing = [n for n in names if n not in sd]
+        if missing:
+            raise KeyError(f"TAEHV state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}")
+        ws = [self._repack(n, sd[n]).contiguous().to(self.device) for n in names]
+        arr = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+        _lib.check(self._lib.mmpl_taehv_enc_bind_weights(self._h, arr, len(ws)), "mmpl_taehv_enc_bind_weights")
+        self._weights = ws
+
+    def clear_cache(self) -> None:
+        """Ends the streamed video: the next ``encode_stream`` call starts from zero memories."""
+        _lib.check(self._lib.mmpl_taehv_enc_reset(self._h), "mmpl_taehv_enc_reset")
+        self.frames_done = 0
+
+    def _check_px(self, px: torch.Tensor) -> bool:
+        """-> whether ``px`` is the uint8 format; ValueError before the device is touched."""
+        H, W = 8 * self.lat_h, 8 * self.lat_w
+        u8 = px.dtype == torch.uint8
+        want = (H, W, 3) if u8 else (3, H, W)
+        if px.dim() != 4 or tuple(px.shape[1:]) != want or not (u8 or px.dtype.is_floating_point):
+            raise ValueError(f"pixels {tuple(px.shape)} {px.dtype}: float [T, 3, {H}, {W}] in [0, 1] or uint8 [T, {H}, {W}, 3]")
+        if px.shape[0] < 4 or px.shape[0] % 4:
+            raise ValueError(f"{px.shape[0]} frames: the encoder takes a multiple of 4 (4 pixel frames per latent frame)")
+        return u8
+
+    def encode_stream(self, px: torch.Tensor) -> torch.Tensor:
+        """px = the NEXT T frames of the streamed video, float [T, 3, 8h, 8w] in [0, 1] or uint8 [T, 8h, 8w, 3], T a multiple of 4
+        -> bf16 [T / 4, 16, h, w], the pipeline's normalised latents, on the current stream."""
+        u8 = self._check_px(px)
+        px = px.to(device=self.device, dtype=torch.uint8 if u8 else torch.float32).contiguous()
+        T = px.shape[0]
+        if self._ws is None:
+            self._ws = torch.empty(self._lib.mmpl_taehv_enc_workspace_bytes(self._h), dtype=torch.uint8, device=self.device)
+        ws = self._ws
+        z = torch.empty(T // 4, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=self.device)
+        n_out = C.c_int(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mmpl_taehv_encode(self._h, _lib.ptr(px), int(u8), T, _lib.ptr(z), C.byref(n_out), _lib.ptr(ws),
+                                                   ws.numel(), _lib.stream_ptr()), "mmpl_taehv_encode")
+        self.frames_done += T
+        return z[:n_out.value]
+
+    def encode(self, px: torch.Tensor) -> torch.Tensor:
+        """One-shot: a whole video from zero memories (see ``encode_stream``)."""
+        self._check_px(px)
+        self.clear_cache()
+        return self.encode_stream(px)

@@ -368,32 +368,75 @@ class WanVAEWrapper(torch.nn.Module):
 
 
 class TAEHVWrapper(torch.nn.Module):
-    """The tiny preview decoder (demo_utils/taehv.py, ``taew2_1.pth``) behind ``WanVAEWrapper``'s DECODE contract, on the HIP
-    engine of mmpl_amd/taehv.py: ``decode_to_pixel`` (frames in [-1, 1]), ``model.clear_cache()``, ``model.decode_stream(...)``.
-    Decoder only: there is no ``encode_to_latent``.
+    """The tiny preview autoencoder (demo_utils/taehv.py, ``taew2_1.pth``) behind ``WanVAEWrapper``'s contract, on the HIP engines
+    of mmpl_amd/taehv.py: ``decode_to_pixel`` (frames in [-1, 1]), ``model.clear_cache()``, ``model.decode_stream(...)`` and, when
+    the weights hold the encoder half (``encoder.*`` keys), ``encode_to_latent`` / ``encode_stream`` on ``self.encoder``.  Without
+    them ``self.encoder`` is None and the encode methods raise.
 
-    The engine, like this reference's ``decode_video``, returns 4 frames per latent frame; the wrapper drops the first 3 frames of
-    a VIDEO (where upstream put the trim), so frame counts equal the Wan VAE's -- ``1 + 4(F - 1)`` for a video's first call, ``4F``
-    after -- and the two decoders are interchangeable."""
+    The decoder engine, like this reference's ``decode_video``, returns 4 frames per latent frame; the wrapper drops the first 3
+    frames of a VIDEO (where upstream put the trim), so frame counts equal the Wan VAE's -- ``1 + 4(F - 1)`` for a video's first
+    call, ``4F`` after -- and the two decoders are interchangeable.  ``encode_to_latent`` mirrors that on the way in."""
 
     TRIM = 3
 
     def __init__(self, geometry: Optional[Geometry] = None, device="cuda:0", state_dict: Optional[dict] = None,
                  pretrained_path: Optional[str] = None):
         super().__init__()
-        from .taehv import TaehvEngine
+        from .taehv import TaehvEncoderEngine, TaehvEngine
         self.geometry = geometry or Geometry.named("480p")
         self.model = TaehvEngine(self.geometry.lat_h, self.geometry.lat_w, device)
-        self.mean, self.std = None, None                             # the decoder reads the normalised latent
+        self.encoder = None                                          # TaehvEncoderEngine once encoder weights are loaded
+        self.mean, self.std = None, None                             # both halves work in the normalised latent space
         path = pretrained_path or f"{local_wan_path}/taew2_1.pth"
         if state_dict is None and os.path.exists(path):
-            from .checkpoints import read_taehv
-            state_dict = read_taehv(path)
+            from .checkpoints import read_state_dict
+            state_dict = read_state_dict(path)
         if state_dict is not None:
             self.model.load_state_dict(state_dict)
+            if any(k.startswith("encoder.") for k in state_dict):
+                self.encoder = TaehvEncoderEngine(self.geometry.lat_h, self.geometry.lat_w, device)
+                self.encoder.load_state_dict(state_dict)
 
     def to(self, *args, **kwargs):
         return self
+
+    def _need_encoder(self):
+        if self.encoder is None:
+            raise RuntimeError("TAEHVWrapper: no encoder weights (the state dict / checkpoint has no 'encoder.*' tensors); "
+                               "only the decode methods are available")
+        return self.encoder
+
+    def encode_stream(self, px: torch.Tensor) -> torch.Tensor:
+        """The encoder engine's ``encode_stream``: the NEXT T frames (float [T, 3, H, W] in [0, 1] or uint8 [T, H, W, 3], T a
+        multiple of 4) of the streamed video -> bf16 [T / 4, 16, h, w]; ``self.encoder.clear_cache()`` starts a new video."""
+        return self._need_encoder().encode_stream(px)
+
+    @staticmethod
+    def latent_frames(T: int) -> int:
+        """Latent frames ``encode_to_latent`` returns for T pixel frames; ValueError for a count it does not take."""
+        if T >= 4 and T % 4 == 0:
+            return T // 4
+        if T >= 1 and T % 4 == 1:
+            return (T - 1) // 4 + 1
+        raise ValueError(f"{T} frames: encode_to_latent takes 4k frames (k latents) or the Wan VAE's 1 + 4k (k + 1 latents)")
+
+    def encode_to_latent(self, pixel: torch.Tensor) -> torch.Tensor:
+        """pixel [1, 3, T, H, W] in [-1, 1] -> latent [1, F, 16, h, w] float32, a whole video from zero memories
+        (``WanVAEWrapper.encode_to_latent``'s signature).  T = 4k gives k latents, the tiny encoder's own grid.  T = 1 + 4k, the
+        Wan VAE's grid, gives k + 1 latents: the first frame is repeated three times in front -- the mirror of ``TRIM`` on the decode
+        side.  That front padding is this wrapper's choice and has no counterpart in the reference, whose ``encode_video`` takes
+        multiples of 4 only.  Any other T raises ValueError."""
+        if pixel.dim() != 5 or pixel.shape[0] != 1 or pixel.shape[1] != 3:
+            raise ValueError(f"pixel {tuple(pixel.shape)}: expected [1, 3, T, H, W]")
+        T = pixel.shape[2]
+        self.latent_frames(T)
+        enc = self._need_encoder()
+        px = (pixel[0].permute(1, 0, 2, 3).float() + 1) * 0.5                # [T, 3, H, W] in [0, 1]
+        if T % 4 == 1:
+            px = torch.cat([px[:1].expand(self.TRIM, -1, -1, -1), px], 0)
+        z = enc.encode(px)
+        enc.clear_cache()
+        return z.float().unsqueeze(0)
 
     def decode_stream(self, latent: torch.Tensor, out_format: str = "float") -> torch.Tensor:
         """The engine's ``decode_stream`` ([F, 16, h, w] -> frames in the network's [0, 1] scale, "float" unclamped) minus the

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the two MFMA kernels on the 14B/720p shapes (dev tool).
     python tools/bench_kernels.py attn|gemm|all|gemmref|attnref|elem|cross [--iters N]
-    python tools/bench_kernels.py taehv [--iters N] [--out FILE]     # the TAEHV preview decoder against the Wan VAE's streamed decode"""
+    python tools/bench_kernels.py taehv [--iters N] [--out FILE]     # the TAEHV preview decoder against the Wan VAE's streamed decode
+    python tools/bench_kernels.py taehvenc [--iters N] [--out FILE]  # the TAEHV encoder against the Wan VAE's encode"""
 import ctypes as C
 import math
 import os
@@ -324,6 +325,87 @@ def bench_taehv(iters, out_path=None):
             f.write("\n".join(lines) + "\n")
 
 
+def taehv_enc_macs_per_latent(h, w):
+    """Multiply-accumulates of the TAEHV encoder per latent frame (= 4 pixel frames), from the layer shapes as the engine runs them
+    (the input layer counted as its 27 real products, not the 32 the MFMA computes)."""
+    c, hw = 64, h * w
+    macs = 4 * 64 * hw * 27 * c                                              # input layer, 4 full-resolution frames
+    t, px = 4, 64 * hw
+    for stride in (2, 2, 1):
+        t //= stride
+        macs += t * px * stride * c * c                                      # TPool 1x1 at the incoming resolution
+        px //= 4
+        macs += t * px * 9 * c * c                                           # stride-2 3x3 conv
+        macs += 3 * t * px * 9 * (2 * c * c + c * c + c * c)                 # 3 MemBlocks
+    return macs + t * px * 9 * c * 16                                        # head
+
+
+def bench_taehvenc(iters, out_path=None):
+    """Same process, alternating, warm, event-timed: the tiny encoder on 12 pixel frames (a streamed group that is not the video's
+    first) against WanVAEWrapper.encode_to_latent on 13 frames of the same size, at 480p and 720p; then the input layer alone
+    against the same layer through the generic conv on a zero-padded 32-channel frame (whose staging is not even counted)."""
+    from mmpl_amd.geometry import Geometry
+    from mmpl_amd.synthetic import taehv_encoder_state_dict, vae_state_dict
+    from mmpl_amd.taehv import TaehvEncoderEngine, TaehvEngine
+    from mmpl_amd.wan_wrapper import WanVAEWrapper
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"# tools/bench_kernels.py taehvenc --iters {iters}: min of 3 windows of {iters} calls each, hipEvent-timed, alternating encoders")
+    sd = taehv_encoder_state_dict(seed=5)
+    for name, (h, w) in (("480p", (60, 104)), ("720p", (90, 160))):
+        H, W = 8 * h, 8 * w
+        wan = WanVAEWrapper(geometry=Geometry(h, w), device=dev, state_dict=vae_state_dict(seed=2))
+        tiny = TaehvEncoderEngine(h, w, dev)
+        tiny.load_state_dict(sd)
+        g = torch.Generator(device=dev).manual_seed(3)
+        u8 = torch.randint(0, 256, (24, H, W, 3), generator=g, device=dev, dtype=torch.uint8)
+        video = (u8[:13].permute(3, 0, 1, 2).float() / 127.5 - 1).to(BF).unsqueeze(0).contiguous()        # [1, 3, 13, H, W] in [-1, 1]
+        gmac = taehv_enc_macs_per_latent(h, w) / 1e9
+        say(f"{name} ({h} x {w} latents): TAEHV encoder {gmac:.1f} GMAC = {2 * gmac / 1e3:.3f} TFLOP per latent frame")
+        tiny.clear_cache()
+        tiny.encode_stream(u8[:12])                                          # the video's first group
+        fv = lambda: wan.encode_to_latent(video)
+        ft = lambda: tiny.encode_stream(u8[12:24])
+        tv, tt = [], []
+        for _ in range(3):
+            tv.append(timeit(fv, iters)); tt.append(timeit(ft, iters))
+        v, t = min(tv), min(tt)
+        say(f"{name} wan_vae encode_to_latent, 13 frames: {v:8.3f} ms = {v / 13:7.3f} ms / frame   taehv encode_stream, 12 frames (uint8, not "
+            f"the first): {t:8.3f} ms = {t / 12:7.3f} ms / frame   ratio per frame {(v / 13) / (t / 12):5.2f}x   taehv {3 * 2 * gmac / t:6.1f} TFLOP/s"
+            f"   (windows: vae {' '.join(f'{x:.3f}' for x in tv)} | taehv {' '.join(f'{x:.3f}' for x in tt)})")
+        del wan, tiny
+        torch.cuda.empty_cache()
+        # the input layer alone, 4 frames: the packed-K kernel against taehv_conv_kernel on a [H + 2, W + 2, 32] frame
+        w0, b0 = sd["encoder.0.weight"], sd["encoder.0.bias"].to(dev)
+        wp = TaehvEncoderEngine._repack("encoder.0.weight", w0).to(dev)
+        wg = TaehvEngine._repack("encoder.0.weight", w0).to(dev)             # Cin 3 zero-padded to 32, 9 taps
+        dst = torch.zeros(4, H + 2, W + 2, 64, device=dev, dtype=BF)
+        src = torch.zeros(4, H + 2, W + 2, 32, device=dev, dtype=BF)
+        src[:, 1:-1, 1:-1, :3] = (u8[:4].float() / 255).to(BF)
+        fsd, fs = dst[0].numel(), src[0].numel()
+        fp = lambda: _lib.check(lib.mmpl_taehv_conv_in(_lib.ptr(u8), 1, _lib.ptr(wp), _lib.ptr(b0), 4, H, W, _lib.ptr(dst), fsd, _lib.stream_ptr()))
+        fg = lambda: _lib.check(lib.mmpl_taehv_conv(_lib.ptr(src), None, fs, 0, 32, 0, 0, 9, _lib.ptr(wg), _lib.ptr(b0), 64, 64, 4, H, W,
+                                                    _lib.ptr(dst), fsd, 64, 64, 1, None, 0, None, _lib.stream_ptr()))
+        fg()
+        a = dst.clone()
+        fp()
+        diff = float((a.float() - dst.float()).abs().max())                  # two summation orders of the same 27 products
+        tp, tg = [], []
+        for _ in range(3):
+            tp.append(timeit(fp, iters)); tg.append(timeit(fg, iters))
+        say(f"{name} input layer, 4 frames: packed-K conv_in {min(tp):7.3f} ms   generic 3x3 conv on a padded 32-channel frame {min(tg):7.3f} ms   "
+            f"ratio {min(tg) / min(tp):5.2f}x   max |d| between them {diff:.3g}   ({4 * dst[0].numel() * 2 / 1e6 / min(tp):.0f} GB/s of output)")
+        del dst, src, u8, video
+        torch.cuda.empty_cache()
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     iters = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 5
@@ -344,3 +426,5 @@ if __name__ == "__main__":
         bench_cross(iters)
     if what == "taehv":
         bench_taehv(iters, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+    if what == "taehvenc":
+        bench_taehvenc(iters, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
