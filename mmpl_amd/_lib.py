@@ -95,6 +95,13 @@ def ptr(t) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def bind_weights(fn, handle, tensors, what: str) -> None:
+    """Hand the device pointers of `tensors`, in order, to the mmpl_*_bind_weights entry `fn`.  The library borrows them: the
+    caller keeps the tensors alive."""
+    arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    check(fn(handle, arr, len(tensors)), what)
+
+
 def stream_ptr() -> C.c_void_p:
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

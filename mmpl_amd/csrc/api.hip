@@ -11,9 +11,8 @@
 #include <vector>
 
 #include "../../include/mmpl_hip.h"
-#include "kernels.h"
+#include "host_util.h"
 #include "mmpl_config.h"
-#include "mmpl_error.h"
 
 static thread_local std::string g_err;
 static int fail(const char* where, const char* what) {
@@ -21,11 +20,6 @@ static int fail(const char* where, const char* what) {
   return 1;
 }
 int mmpl_set_error(const char* where, const char* what) { return fail(where, what); }
-#define HIP_TRY(expr, where)                                     \
-  do {                                                           \
-    hipError_t e__ = (expr);                                     \
-    if (e__ != hipSuccess) return fail(where, hipGetErrorString(e__)); \
-  } while (0)
 
 // ---- optional per-kernel-class timing (bench / profiling only; per host thread, off by default; launches recorded
 // while the stream is being captured into a hipGraph are not timed -- an event pair inside a graph cannot be read back)
@@ -192,30 +186,14 @@ void mmpl_dit_destroy(MmplDit* h) {
 }
 
 int mmpl_dit_bind_weights(MmplDit* h, const void* const* ptrs, int n) {
-  if (!h || !ptrs) return fail("mmpl_dit_bind_weights", "null argument");
-  if (n != NG + h->cfg.num_layers * NL) return fail("mmpl_dit_bind_weights", "wrong pointer count");
-  h->w.resize(n);
-  for (int i = 0; i < n; ++i) {
-    if (!ptrs[i]) return fail("mmpl_dit_bind_weights", "null weight pointer");
-    h->w[i] = (const bf16_t*)ptrs[i];
-  }
-  return 0;
+  if (!h) return fail("mmpl_dit_bind_weights", "null argument");
+  return bind_weight_ptrs(h->w, ptrs, n, NG + h->cfg.num_layers * NL, "mmpl_dit_bind_weights");
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ workspace
 namespace {
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  bf16_t* take(size_t elems) {
-    bf16_t* p = (bf16_t*)(base + off);
-    off += (elems * 2 + 255) & ~(size_t)255;
-    return p;
-  }
-};
 constexpr int kTicketInts = 64 + 256;     // 8 per-XCD tile tickets (padded to 64 ints) + 256 split-K tile counters: what a forward zeroes
 struct FwdWs {
   bf16_t *x, *xn, *big, *attn, *ksc, *vsc, *patch, *sinu, *t1, *e, *se, *e0, *emod, *emod_head, *yh;
@@ -233,25 +211,35 @@ FwdWs carve_fwd(const MmplDit* h, int nF, void* base, int nT = 0) {
   const size_t bigw = (size_t)(3 * c.dim > c.ffn_dim ? 3 * c.dim : c.ffn_dim);
   Carver k(base);
   FwdWs w;
-  // first: the same place for every stage shape, so no other shape's activations ever land on it.  take() counts bf16 elements
-  static_assert(kTicketInts * sizeof(int) % sizeof(bf16_t) == 0, "ticket area");
-  w.tile_counter = (int*)k.take(kTicketInts * sizeof(int) / sizeof(bf16_t));
-  w.x = k.take(Lq * d);
-  w.xn = k.take(Lq * d);
-  w.big = k.take(Lq * bigw);
-  w.attn = k.take(Lq * d);
-  w.ksc = k.take(Lq * d);
-  w.vsc = k.take(Lq * d);
-  w.patch = k.take(Lq * (size_t)h->pe_k);
-  w.sinu = k.take((size_t)nT * c.freq_dim);
-  w.t1 = k.take((size_t)nT * d);
-  w.e = k.take((size_t)nT * d);
-  w.se = k.take((size_t)nT * d);
-  w.e0 = k.take((size_t)nT * 6 * d);
-  w.emod = k.take((size_t)c.num_layers * nT * 6 * d);
-  w.emod_head = k.take((size_t)nT * 2 * d);
-  w.yh = k.take(Lq * 64);
-  w.splitk = (float*)k.take(mmpl_gemm_splitk_ws_bytes() / sizeof(bf16_t));
+  // first: the same place for every stage shape, so no other shape's activations ever land on it
+  w.tile_counter = k.take<int>(kTicketInts);
+  w.x = k.take<bf16_t>(Lq * d);
+  w.xn = k.take<bf16_t>(Lq * d);
+  w.big = k.take<bf16_t>(Lq * bigw);
+  w.attn = k.take<bf16_t>(Lq * d);
+  w.ksc = k.take<bf16_t>(Lq * d);
+  w.vsc = k.take<bf16_t>(Lq * d);
+  w.patch = k.take<bf16_t>(Lq * (size_t)h->pe_k);
+  w.sinu = k.take<bf16_t>((size_t)nT * c.freq_dim);
+  w.t1 = k.take<bf16_t>((size_t)nT * d);
+  w.e = k.take<bf16_t>((size_t)nT * d);
+  w.se = k.take<bf16_t>((size_t)nT * d);
+  w.e0 = k.take<bf16_t>((size_t)nT * 6 * d);
+  w.emod = k.take<bf16_t>((size_t)c.num_layers * nT * 6 * d);
+  w.emod_head = k.take<bf16_t>((size_t)nT * 2 * d);
+  w.yh = k.take<bf16_t>(Lq * 64);
+  w.splitk = k.take<float>(mmpl_gemm_splitk_ws_bytes() / sizeof(float));   // (a whole number of fp32 partials)
+  w.bytes = k.off;
+  return w;
+}
+
+// What mmpl_dit_precompute_context takes from its workspace (mmpl_dit_context_workspace_bytes is the dry carve): the text embedding's
+// hidden layer and its output, [text_len, dim] each, and rows_equal_last's one int per row.
+struct CtxWs { bf16_t *t0, *ctx; int* flags; size_t bytes; };
+CtxWs carve_ctx(const MmplDit* h, void* base) {
+  const size_t T = h->cfg.text_len;
+  Carver k(base);
+  CtxWs w{k.take<bf16_t>(T * h->cfg.dim), k.take<bf16_t>(T * h->cfg.dim), k.take<int>(T), 0};   // (a braced list: left to right)
   w.bytes = k.off;
   return w;
 }
@@ -259,7 +247,8 @@ FwdWs carve_fwd(const MmplDit* h, int nF, void* base, int nT = 0) {
 int gemm(const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, bf16_t* C, int ldc, int M, int N, int K,
          int epi, const bf16_t* res, int ldres, const bf16_t* gate, int gfs, int rpf, hipStream_t s, int* tile_counter = nullptr,
          float* splitk_ws = nullptr) {
-  GemmArgs g{A, lda, W, ldw, bias, C, ldc, M, N, K, epi, res, ldres, gate, gfs, rpf > 0 ? rpf : 1, 1.0f, 0, 0, 0, 0, 0};
+  GemmArgs g = gemm_args(A, lda, W, ldw, bias, C, ldc, M, N, K, epi);
+  g.res = res; g.ldres = ldres; g.gate = gate; g.gate_frame_stride = gfs; g.rows_per_frame = rpf > 0 ? rpf : 1;
   g.tile_counter = tile_counter;
   g.splitk_ws = splitk_ws;                               // with the forward's scratch: counters 64 ints behind the tile tickets
   g.splitk_cnt = splitk_ws ? tile_counter + 64 : nullptr;
@@ -293,19 +282,16 @@ AttnArgs attn_entry_args(const void* q, int ldq, void* o, int ldo, const void* c
 extern "C" {
 
 size_t mmpl_dit_workspace_bytes(const MmplDit* h, int n_frames) { return carve_fwd(h, n_frames, nullptr).bytes; }
-size_t mmpl_dit_context_workspace_bytes(const MmplDit* h) {
-  return 2 * (((size_t)h->cfg.text_len * h->cfg.dim * 2 + 255) & ~(size_t)255) + (((size_t)h->cfg.text_len * sizeof(int) + 255) & ~(size_t)255);
-}
+size_t mmpl_dit_context_workspace_bytes(const MmplDit* h) { return carve_ctx(h, nullptr).bytes; }
 
 int mmpl_dit_precompute_context(MmplDit* h, const void* context, void* cross_k, void* cross_v, void* workspace,
                                 size_t workspace_bytes, int* distinct_rows, mmpl_stream_t stream) {
   if (!h || h->w.empty()) return fail("mmpl_dit_precompute_context", "weights not bound");
-  if (workspace_bytes < mmpl_dit_context_workspace_bytes(h)) return fail("mmpl_dit_precompute_context", "workspace too small");
+  const CtxWs cw = carve_ctx(h, workspace);
+  if (workspace_bytes < cw.bytes) return fail("mmpl_dit_precompute_context", "workspace too small");
   const MmplDitConfig& c = h->cfg;
   hipStream_t s = (hipStream_t)stream;
-  Carver k(workspace);
-  bf16_t* t0 = k.take((size_t)c.text_len * c.dim);
-  bf16_t* ctx = k.take((size_t)c.text_len * c.dim);
+  bf16_t *t0 = cw.t0, *ctx = cw.ctx;
   const int T = c.text_len, d = c.dim;
   TRY(gemm((const bf16_t*)context, c.text_dim, h->G(G_TXT0_W), c.text_dim, h->G(G_TXT0_B), t0, d, T, d, c.text_dim,
            EPI_BIAS_GELU, nullptr, 0, nullptr, 0, 1, s));
@@ -323,11 +309,11 @@ int mmpl_dit_precompute_context(MmplDit* h, const void* context, void* cross_k, 
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cs);
     if (cs == hipStreamCaptureStatusNone && T >= 2) {
-      int* flags = (int*)k.take(((size_t)T * sizeof(int) + 1) / sizeof(bf16_t));
+      int* flags = cw.flags;
       std::vector<int> hf(T);
-      HIP_TRY(mmpl_launch_rows_equal_last(ctx, d, T, d, flags, s), "rows_equal_last");
-      HIP_TRY(hipMemcpyAsync(hf.data(), flags, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s), "context flags");
-      HIP_TRY(hipStreamSynchronize(s), "context flags");
+      MMPL_HIP_TRY(mmpl_launch_rows_equal_last(ctx, d, T, d, flags, s), "rows_equal_last");
+      MMPL_HIP_TRY(hipMemcpyAsync(hf.data(), flags, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s), "context flags");
+      MMPL_HIP_TRY(hipStreamSynchronize(s), "context flags");
       int n = T - 1;
       while (n > 0 && hf[n - 1]) --n;                      // rows n .. T-1 are identical
       if (T - n >= 2) *distinct_rows = n;
@@ -337,7 +323,7 @@ int mmpl_dit_precompute_context(MmplDit* h, const void* context, void* cross_k, 
     bf16_t* kl = (bf16_t*)cross_k + (size_t)l * T * d;
     bf16_t* vl = (bf16_t*)cross_v + (size_t)l * T * d;
     TRY(gemm(ctx, d, h->Lw(l, L_CK_W), d, h->Lw(l, L_CK_B), kl, d, T, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-    HIP_TRY(mmpl_launch_rmsnorm(kl, d, h->Lw(l, L_CNK), T, d, c.eps, s), "rmsnorm(ctx k)");
+    MMPL_HIP_TRY(mmpl_launch_rmsnorm(kl, d, h->Lw(l, L_CNK), T, d, c.eps, s), "rmsnorm(ctx k)");
     TRY(gemm(ctx, d, h->Lw(l, L_CV_W), d, h->Lw(l, L_CV_B), vl, d, T, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
   }
   return 0;
@@ -368,18 +354,34 @@ int mmpl_dit_forward(MmplDit* h, const void* x_in, const float* t_dev, int nF, c
                              cross_v, cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
 }
 
-// The launches of one forward, for both entries.  full = mmpl_dit_forward_full: the whole clip in one call -- frame i at temporal
+}  // extern "C"
+
+namespace {
+
+// The launches of one forward, for every entry.  full = mmpl_dit_forward_full: the whole clip in one call -- frame i at temporal
 // position i, no cache (frame_ids / write_slots / visible_slots / k_cache / v_cache are NULL, n_visible and n_slots 0: the layer's
 // K / V are the workspace's scratch pair, every frame attends to all of them), n_frames up to MMPL_MAX_PAGES whatever cfg.max_frames,
 // and t_dev is ONE float: the timestep embedding and the modulation vectors are computed for one row and read by every frame
 // through a frame stride of 0 (row i of those GEMMs depends on row i of their input alone, so the bits are the per-frame ones).
 // y_in (NULL for every entry but mmpl_dit_forward_full_i2v): x_in then holds the first 16 of the in_dim channels and y_in the rest.
-static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_in, const void* y_in, const float* t_dev, int nF,
-                           const int* frame_ids,
-                           const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
-                           int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
-                           void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
-                           mmpl_stream_t stream) {
+//
+// FwdCall: one forward as its entry states it -- the arguments of include/mmpl_hip.h under their names there.  An entry starts from
+// FwdCall{} and names what it has; the rest stays NULL / 0.  run() is the launch sequence.
+struct FwdCall {
+  const char* me;              // the entry's name in the error text
+  bool full;
+  MmplDit* h;
+  const void *x_in, *y_in, *cross_k, *cross_v, *share_in;
+  const float* t_dev;
+  const int *frame_ids, *write_slots, *visible_slots, *frame_base_dev;
+  int nF, n_visible, n_slots, cross_rows;
+  void *k_cache, *v_cache, *share_out, *attn_history, *out, *workspace;
+  size_t workspace_bytes;
+  mmpl_stream_t stream;
+  int run() const;
+};
+
+int FwdCall::run() const {
   if (!h || h->w.empty()) return fail(me, "weights not bound");
   const MmplDitConfig& c = h->cfg;
   if (nF < 1 || nF > (full ? MMPL_MAX_PAGES : c.max_frames)) return fail(me, "n_frames out of range");
@@ -402,24 +404,24 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
   const int S = h->S, d = c.dim, f = c.ffn_dim, Lq = nF * S, H = c.num_heads, T = c.text_len;
   const int mfs = full ? 0 : 6 * d, hfs = full ? 0 : 2 * d;   // frame stride of the blocks' / the head's modulation vectors
 
-  HIP_TRY(mmpl_launch_zero_ints(w.tile_counter, kTicketInts, s), "tile counter");                  // left zero by every GEMM that uses it
+  MMPL_HIP_TRY(mmpl_launch_zero_ints(w.tile_counter, kTicketInts, s), "tile counter");                  // left zero by every GEMM that uses it
   int* const tc = w.tile_counter;
   // ---- embeddings (causal_fps_model.py:757-776)
   if (y_in)
-    HIP_TRY(mmpl_launch_patchify2((const bf16_t*)x_in, (const bf16_t*)y_in, w.patch, h->pe_k, nF, c.out_dim, c.in_dim - c.out_dim, c.lat_h,
+    MMPL_HIP_TRY(mmpl_launch_patchify2((const bf16_t*)x_in, (const bf16_t*)y_in, w.patch, h->pe_k, nF, c.out_dim, c.in_dim - c.out_dim, c.lat_h,
                                   c.lat_w, s), "patchify (x, y)");
   else
-    HIP_TRY(mmpl_launch_patchify((const bf16_t*)x_in, w.patch, h->pe_k, nF, c.in_dim, c.lat_h, c.lat_w, s), "patchify");
+    MMPL_HIP_TRY(mmpl_launch_patchify((const bf16_t*)x_in, w.patch, h->pe_k, nF, c.in_dim, c.lat_h, c.lat_w, s), "patchify");
   TRY(gemm(w.patch, h->pe_k, h->G(G_PE_W), h->pe_k, h->G(G_PE_B), w.x, d, Lq, d, h->pe_k, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-  HIP_TRY(mmpl_launch_sinusoid(t_dev, w.sinu, nT, c.freq_dim, s), "sinusoid");
+  MMPL_HIP_TRY(mmpl_launch_sinusoid(t_dev, w.sinu, nT, c.freq_dim, s), "sinusoid");
   TRY(gemm(w.sinu, c.freq_dim, h->G(G_TE0_W), c.freq_dim, h->G(G_TE0_B), w.t1, d, nT, d, c.freq_dim, EPI_BIAS_SILU, nullptr,
            0, nullptr, 0, 1, s));
   TRY(gemm(w.t1, d, h->G(G_TE2_W), d, h->G(G_TE2_B), w.e, d, nT, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-  HIP_TRY(mmpl_launch_silu(w.e, w.se, (size_t)nT * d, s), "silu");
+  MMPL_HIP_TRY(mmpl_launch_silu(w.e, w.se, (size_t)nT * d, s), "silu");
   TRY(gemm(w.se, d, h->G(G_TP_W), d, h->G(G_TP_B), w.e0, 6 * d, nT, 6 * d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
   // e = bf16(modulation + e0) for every layer and for the head (causal_fps_model.py:338, 393)
-  HIP_TRY(mmpl_launch_modulation(h->G(G_BLOCK_MOD), (size_t)6 * d, w.e0, 6 * d, 0, w.emod, c.num_layers, nT, 6, d, s), "modulation");
-  HIP_TRY(mmpl_launch_modulation(h->G(G_HEAD_MOD), 0, w.e, d, 1, w.emod_head, 1, nT, 2, d, s), "head modulation");
+  MMPL_HIP_TRY(mmpl_launch_modulation(h->G(G_BLOCK_MOD), (size_t)6 * d, w.e0, 6 * d, 0, w.emod, c.num_layers, nT, 6, d, s), "modulation");
+  MMPL_HIP_TRY(mmpl_launch_modulation(h->G(G_HEAD_MOD), 0, w.e, d, 1, w.emod_head, 1, nT, 2, d, s), "head modulation");
 
   const float scale = 1.0f / sqrtf(128.0f);
   const int self_variant = mmpl_attention_self_variant();
@@ -442,10 +444,10 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
     }
     pk.n = pv.n = n_visible;
     if (n_visible < 1) return 0;
-    HIP_TRY(mmpl_launch_share_check_zero(h->share_chk, which, s), "share check");
-    HIP_TRY(mmpl_launch_pages_fingerprint(pk, (size_t)S * d * sizeof(bf16_t), h->share_chk, which, s), "share check (K)");
-    HIP_TRY(mmpl_launch_pages_fingerprint(pv, (size_t)S * d * sizeof(bf16_t), h->share_chk, which, s), "share check (V)");
-    if (which == 1) HIP_TRY(mmpl_launch_share_check_compare(h->share_chk, s), "share check (compare)");
+    MMPL_HIP_TRY(mmpl_launch_share_check_zero(h->share_chk, which, s), "share check");
+    MMPL_HIP_TRY(mmpl_launch_pages_fingerprint(pk, (size_t)S * d * sizeof(bf16_t), h->share_chk, which, s), "share check (K)");
+    MMPL_HIP_TRY(mmpl_launch_pages_fingerprint(pv, (size_t)S * d * sizeof(bf16_t), h->share_chk, which, s), "share check (V)");
+    if (which == 1) MMPL_HIP_TRY(mmpl_launch_share_check_compare(h->share_chk, s), "share check (compare)");
     return 0;
   };
   for (int l = 0; l < c.num_layers; ++l) {
@@ -461,15 +463,16 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
     if (!take_shared || persist) {
       // -- self attention (causal_fps_model.py:342-348)
       {
-        LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, em + 1 * d, em + 0 * d, mfs, S, nullptr, nullptr};
+        LnArgs a = ln_args(w.x, d, w.xn, d, Lq, d, c.eps);
+        a.scale = em + 1 * d; a.shift = em + 0 * d; a.mod_frame_stride = mfs; a.rows_per_frame = S;
         ProfScope ps(K_LAYERNORM, 0, s);
-        HIP_TRY(mmpl_launch_layernorm(a, s), "norm1");
+        MMPL_HIP_TRY(mmpl_launch_layernorm(a, s), "norm1");
       }
       {
         // fused q|k|v projection; the V third goes straight into its KV-cache pages (V is cached unchanged,
         // causal_fps_model.py:217), so the norm / RoPE pass below only touches q and k
-        GemmArgs g{w.xn, d, h->Lw(l, L_QKV_W), d, h->Lw(l, L_QKV_B), w.big, 3 * d, Lq, 3 * d, d, EPI_BIAS_VPAGES, nullptr, 0, nullptr, 0, S,
-                   1.0f, 0, 0, 0, 0, 0};
+        GemmArgs g = gemm_args(w.xn, d, h->Lw(l, L_QKV_W), d, h->Lw(l, L_QKV_B), w.big, 3 * d, Lq, 3 * d, d, EPI_BIAS_VPAGES);
+        g.rows_per_frame = S;
         if (full) {
           // the clip's V rows are one contiguous [Lq, d] matrix in the workspace: ONE page of Lq rows (GemmArgs::v_dst holds 8)
           g.rows_per_frame = Lq;
@@ -482,7 +485,7 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
         g.tile_counter = tc;
         g.splitk_ws = w.splitk; g.splitk_cnt = tc + 64;
         ProfScope ps(K_GEMM, 2.0 * Lq * 3.0 * d * d, s);
-        HIP_TRY(mmpl_launch_gemm(g, s), "qkv gemm");
+        MMPL_HIP_TRY(mmpl_launch_gemm(g, s), "qkv gemm");
       }
       {
         QkNormArgs a = {};
@@ -498,12 +501,12 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
         }
         a.frame_base = frame_base_dev;
         ProfScope ps(K_QKNORM, 0, s);
-        HIP_TRY(mmpl_launch_qknorm(a, s), "qk norm + rope + kv write");
+        MMPL_HIP_TRY(mmpl_launch_qknorm(a, s), "qk norm + rope + kv write");
       }
     }
     if (l == 0 && check_share) TRY(fingerprint_layer0(share_in ? 1 : 0));
     if (take_shared) {
-      HIP_TRY(hipMemcpyAsync(w.x, share_in, (size_t)Lq * d * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "shared block-0 x");
+      MMPL_HIP_TRY(hipMemcpyAsync(w.x, share_in, (size_t)Lq * d * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "shared block-0 x");
     } else {
     {
         AttnArgs a = {};
@@ -527,21 +530,22 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
         a.redo_stats = h->attn_stats;
         a.history = attn_history ? (unsigned char*)attn_history + (size_t)l * hist_layer : nullptr;
         ProfScope ps(K_ATTN_SELF, 4.0 * Lq * (double)np * S * d, s);
-        HIP_TRY(mmpl_launch_attention(a, s), "self attention");
+        MMPL_HIP_TRY(mmpl_launch_attention(a, s), "self attention");
       }
       TRY(gemm(w.attn, d, h->Lw(l, L_O_W), d, h->Lw(l, L_O_B), w.x, d, Lq, d, d, EPI_GATE_RES, w.x, d, em + 2 * d, mfs, S, s, tc, w.splitk));
-      if (l == 0 && share_out) HIP_TRY(hipMemcpyAsync(share_out, w.x, (size_t)Lq * d * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "share block-0 x");
+      if (l == 0 && share_out) MMPL_HIP_TRY(hipMemcpyAsync(share_out, w.x, (size_t)Lq * d * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "share block-0 x");
     }
     // -- cross attention (causal_fps_model.py:352-353, model.py:161-194)
     {
-      LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, nullptr, nullptr, 0, S, h->Lw(l, L_N3_W), h->Lw(l, L_N3_B)};
+      LnArgs a = ln_args(w.x, d, w.xn, d, Lq, d, c.eps);
+      a.rows_per_frame = S; a.w = h->Lw(l, L_N3_W); a.b = h->Lw(l, L_N3_B);
       ProfScope ps(K_LAYERNORM, 0, s);
-      HIP_TRY(mmpl_launch_layernorm(a, s), "norm3");
+      MMPL_HIP_TRY(mmpl_launch_layernorm(a, s), "norm3");
     }
     TRY(gemm(w.xn, d, h->Lw(l, L_CQ_W), d, h->Lw(l, L_CQ_B), w.big, d, Lq, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s, tc, w.splitk));
     {
       ProfScope ps(K_QKNORM, 0, s);
-      HIP_TRY(mmpl_launch_rmsnorm(w.big, d, h->Lw(l, L_CNQ), Lq, d, c.eps, s, cross_w64 ? scale * 1.4426950408889634f : 0.f), "cross q norm");
+      MMPL_HIP_TRY(mmpl_launch_rmsnorm(w.big, d, h->Lw(l, L_CNQ), Lq, d, c.eps, s, cross_w64 ? scale * 1.4426950408889634f : 0.f), "cross q norm");
     }
     {
       AttnArgs a = {};
@@ -554,7 +558,7 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
       a.v_pages[0] = (const bf16_t*)cross_v + (size_t)l * T * d;
       {
         ProfScope ps(K_ATTN_CROSS, 4.0 * Lq * (double)T * d, s);
-        HIP_TRY(mmpl_launch_attention(a, s), "cross attention");
+        MMPL_HIP_TRY(mmpl_launch_attention(a, s), "cross attention");
       }
       if (h->img_k) {
         // Wan-I2V: the query also attends to the image tokens; the two outputs are summed in bf16 before the o-projection
@@ -566,29 +570,31 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
         a.v_pages[0] = h->img_v + (size_t)l * h->n_img * d;
         {
           ProfScope ps2(K_ATTN_CROSS, 4.0 * Lq * (double)h->n_img * d, s);       // (one scope at a time: they do not nest)
-          HIP_TRY(mmpl_launch_attention(a, s), "image cross attention");
+          MMPL_HIP_TRY(mmpl_launch_attention(a, s), "image cross attention");
         }
         ProfScope ps3(K_ELEMENTWISE, 0, s);
-        HIP_TRY(mmpl_launch_add(w.attn, w.ksc, (size_t)Lq * d, s), "x + img_x");
+        MMPL_HIP_TRY(mmpl_launch_add(w.attn, w.ksc, (size_t)Lq * d, s), "x + img_x");
       }
     }
     TRY(gemm(w.attn, d, h->Lw(l, L_CO_W), d, h->Lw(l, L_CO_B), w.x, d, Lq, d, d, EPI_RES, w.x, d, nullptr, 0, 1, s, tc, w.splitk));
     // -- FFN (causal_fps_model.py:354-360)
     {
-      LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, em + 4 * d, em + 3 * d, mfs, S, nullptr, nullptr};
+      LnArgs a = ln_args(w.x, d, w.xn, d, Lq, d, c.eps);
+      a.scale = em + 4 * d; a.shift = em + 3 * d; a.mod_frame_stride = mfs; a.rows_per_frame = S;
       ProfScope ps(K_LAYERNORM, 0, s);
-      HIP_TRY(mmpl_launch_layernorm(a, s), "norm2");
+      MMPL_HIP_TRY(mmpl_launch_layernorm(a, s), "norm2");
     }
     TRY(gemm(w.xn, d, h->Lw(l, L_F0_W), d, h->Lw(l, L_F0_B), w.big, f, Lq, f, d, EPI_BIAS_GELU, nullptr, 0, nullptr, 0, 1, s, tc, w.splitk));
     TRY(gemm(w.big, f, h->Lw(l, L_F2_W), f, h->Lw(l, L_F2_B), w.x, d, Lq, d, f, EPI_GATE_RES, w.x, d, em + 5 * d, mfs, S, s, tc, w.splitk));
   }
   // ---- head + unpatchify (causal_fps_model.py:384-395, 1007-1030)
   {
-    LnArgs a{w.x, d, w.xn, d, Lq, d, c.eps, w.emod_head + d, w.emod_head, hfs, S, nullptr, nullptr};
-    HIP_TRY(mmpl_launch_layernorm(a, s), "head norm");
+    LnArgs a = ln_args(w.x, d, w.xn, d, Lq, d, c.eps);
+    a.scale = w.emod_head + d; a.shift = w.emod_head; a.mod_frame_stride = hfs; a.rows_per_frame = S;
+    MMPL_HIP_TRY(mmpl_launch_layernorm(a, s), "head norm");
   }
   TRY(gemm(w.xn, d, h->G(G_HEAD_W), d, h->G(G_HEAD_B), w.yh, 64, Lq, 64, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-  HIP_TRY(mmpl_launch_unpatchify(w.yh, 64, (bf16_t*)out, nF, c.out_dim, c.lat_h, c.lat_w, s), "unpatchify");
+  MMPL_HIP_TRY(mmpl_launch_unpatchify(w.yh, 64, (bf16_t*)out, nF, c.out_dim, c.lat_h, c.lat_w, s), "unpatchify");
   if (check_share && share_in) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cs);
@@ -602,14 +608,40 @@ static int dit_forward_run(const char* me, bool full, MmplDit* h, const void* x_
   return 0;
 }
 
+// What the two whole-clip entries check before the launch sequence (the i2v entry's own two between the arguments and the
+// frame count), then the sequence.
+int run_whole_clip(const FwdCall& a, bool i2v) {
+  const char* me = a.me;
+  MmplDit* h = a.h;
+  if (!h) return fail(me, "null handle");
+  if (!a.x_in || (i2v && !a.y_in) || !a.t_dev || !a.cross_k || !a.cross_v || !a.out || !a.workspace) return fail(me, "null argument");
+  if (i2v) {
+    if (h->cfg.in_dim != 36 || h->cfg.out_dim != 16) return fail(me, "not an i2v handle (in_dim must be 36: 16 latent + 20 conditioning channels)");
+    if (!h->img_k) return fail(me, "no image K / V attached (mmpl_dit_set_image_kv first)");
+  }
+  if (a.nF < 1 || a.nF > MMPL_MAX_PAGES) return fail(me, "n_frames out of range (1 .. 24)");
+  if (a.share_out && a.share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
+  if (h->w.empty()) return fail(me, "weights not bound");
+  if (a.workspace_bytes < mmpl_dit_full_workspace_bytes(h, a.nF)) return fail(me, "workspace too small");
+  return a.run();
+}
+
+}  // namespace
+
+extern "C" {
+
 int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF, const int* frame_ids,
                         const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
                         int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
                         void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
                         mmpl_stream_t stream) {
-  return dit_forward_run("mmpl_dit_forward", false, h, x_in, nullptr, t_dev, nF, frame_ids, write_slots, visible_slots, n_visible, k_cache, v_cache,
-                         n_slots, cross_k, cross_v, cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes,
-                         frame_base_dev, stream);
+  FwdCall a = {};
+  a.me = "mmpl_dit_forward"; a.h = h; a.x_in = x_in; a.t_dev = t_dev; a.nF = nF; a.frame_ids = frame_ids; a.write_slots = write_slots;
+  a.visible_slots = visible_slots; a.n_visible = n_visible; a.k_cache = k_cache; a.v_cache = v_cache; a.n_slots = n_slots;
+  a.cross_k = cross_k; a.cross_v = cross_v; a.cross_rows = cross_rows; a.share_out = share_out; a.share_in = share_in;
+  a.attn_history = attn_history; a.out = out; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  a.frame_base_dev = frame_base_dev; a.stream = stream;
+  return a.run();
 }
 
 size_t mmpl_dit_full_workspace_bytes(const MmplDit* h, int n_frames) {
@@ -619,31 +651,23 @@ size_t mmpl_dit_full_workspace_bytes(const MmplDit* h, int n_frames) {
 int mmpl_dit_forward_full(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const void* cross_k, const void* cross_v,
                           int cross_rows, void* share_out, const void* share_in, void* attn_history, void* out, void* workspace,
                           size_t workspace_bytes, mmpl_stream_t stream) {
-  const char* me = "mmpl_dit_forward_full";
-  if (!h) return fail(me, "null handle");
-  if (!x_in || !t_dev || !cross_k || !cross_v || !out || !workspace) return fail(me, "null argument");
-  if (n_frames < 1 || n_frames > MMPL_MAX_PAGES) return fail(me, "n_frames out of range (1 .. 24)");
-  if (share_out && share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
-  if (h->w.empty()) return fail(me, "weights not bound");
-  if (workspace_bytes < mmpl_dit_full_workspace_bytes(h, n_frames)) return fail(me, "workspace too small");
-  return dit_forward_run(me, true, h, x_in, nullptr, t_dev, n_frames, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, cross_k, cross_v,
-                         cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
+  FwdCall a = {};
+  a.me = "mmpl_dit_forward_full"; a.full = true;
+  a.h = h; a.x_in = x_in; a.t_dev = t_dev; a.nF = n_frames; a.cross_k = cross_k; a.cross_v = cross_v;
+  a.cross_rows = cross_rows; a.share_out = share_out; a.share_in = share_in; a.attn_history = attn_history; a.out = out;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = stream;
+  return run_whole_clip(a, false);
 }
 
 int mmpl_dit_forward_full_i2v(MmplDit* h, const void* x_in, const void* y_in, const float* t_dev, int n_frames, const void* cross_k,
                               const void* cross_v, int cross_rows, void* share_out, const void* share_in, void* attn_history,
                               void* out, void* workspace, size_t workspace_bytes, mmpl_stream_t stream) {
-  const char* me = "mmpl_dit_forward_full_i2v";
-  if (!h) return fail(me, "null handle");
-  if (!x_in || !y_in || !t_dev || !cross_k || !cross_v || !out || !workspace) return fail(me, "null argument");
-  if (h->cfg.in_dim != 36 || h->cfg.out_dim != 16) return fail(me, "not an i2v handle (in_dim must be 36: 16 latent + 20 conditioning channels)");
-  if (!h->img_k) return fail(me, "no image K / V attached (mmpl_dit_set_image_kv first)");
-  if (n_frames < 1 || n_frames > MMPL_MAX_PAGES) return fail(me, "n_frames out of range (1 .. 24)");
-  if (share_out && share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
-  if (h->w.empty()) return fail(me, "weights not bound");
-  if (workspace_bytes < mmpl_dit_full_workspace_bytes(h, n_frames)) return fail(me, "workspace too small");
-  return dit_forward_run(me, true, h, x_in, y_in, t_dev, n_frames, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, cross_k, cross_v,
-                         cross_rows, share_out, share_in, attn_history, out, workspace, workspace_bytes, nullptr, stream);
+  FwdCall a = {};
+  a.me = "mmpl_dit_forward_full_i2v"; a.full = true;
+  a.h = h; a.x_in = x_in; a.y_in = y_in; a.t_dev = t_dev; a.nF = n_frames; a.cross_k = cross_k; a.cross_v = cross_v;
+  a.cross_rows = cross_rows; a.share_out = share_out; a.share_in = share_in; a.attn_history = attn_history; a.out = out;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = stream;
+  return run_whole_clip(a, true);
 }
 
 int mmpl_dit_share_check_failures(MmplDit* h, long long* count, mmpl_stream_t stream) {
@@ -652,9 +676,9 @@ int mmpl_dit_share_check_failures(MmplDit* h, long long* count, mmpl_stream_t st
   if (!h->share_chk) return 0;                               // MMPL_CHECK_SHARE not set when the handle was created: nothing is checked
   unsigned long long n = 0;
   hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(hipMemcpyAsync(&n, h->share_chk + 4, sizeof(n), hipMemcpyDeviceToHost, s), "share check read");
-  HIP_TRY(hipStreamSynchronize(s), "share check read");
-  if (n) HIP_TRY(hipMemsetAsync(h->share_chk + 4, 0, sizeof(n), s), "share check reset");
+  MMPL_HIP_TRY(hipMemcpyAsync(&n, h->share_chk + 4, sizeof(n), hipMemcpyDeviceToHost, s), "share check read");
+  MMPL_HIP_TRY(hipStreamSynchronize(s), "share check read");
+  if (n) MMPL_HIP_TRY(hipMemsetAsync(h->share_chk + 4, 0, sizeof(n), s), "share check reset");
   *count = (long long)n;
   return 0;
 }
@@ -667,8 +691,8 @@ size_t mmpl_attn_history_bytes(int Lq, int num_heads) { return mmpl_attention_hi
 int mmpl_dit_rope_tables(const MmplDit* h, float* cos_out, float* sin_out, mmpl_stream_t stream) {
   if (!h || !cos_out || !sin_out) return fail("mmpl_dit_rope_tables", "null argument");
   const size_t bytes = (size_t)1024 * 64 * sizeof(float);
-  HIP_TRY(hipMemcpyAsync(cos_out, h->cos_tab, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "mmpl_dit_rope_tables");
-  HIP_TRY(hipMemcpyAsync(sin_out, h->sin_tab, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "mmpl_dit_rope_tables");
+  MMPL_HIP_TRY(hipMemcpyAsync(cos_out, h->cos_tab, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "mmpl_dit_rope_tables");
+  MMPL_HIP_TRY(hipMemcpyAsync(sin_out, h->sin_tab, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "mmpl_dit_rope_tables");
   return 0;
 }
 
@@ -683,7 +707,7 @@ int mmpl_attn_fwd_history(const void* q, int ldq, void* o, int ldo, const void* 
   a.q_prescaled = 1;
   a.history = (unsigned char*)history;
   a.redo_stats = (unsigned long long*)stats_dev;
-  HIP_TRY(mmpl_launch_attention(a, (hipStream_t)stream), "mmpl_attn_fwd_history");
+  MMPL_HIP_TRY(mmpl_launch_attention(a, (hipStream_t)stream), "mmpl_attn_fwd_history");
   return 0;
 }
 
@@ -701,7 +725,7 @@ int mmpl_attn_fwd_variant(const void* q, int ldq, void* o, int ldo, const void* 
   a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
   a.q_prescaled = variant == ATTN_W64 + 1;
   a.cross = cross != 0;
-  HIP_TRY(mmpl_launch_attention(a, (hipStream_t)stream), "mmpl_attn_fwd");
+  MMPL_HIP_TRY(mmpl_launch_attention(a, (hipStream_t)stream), "mmpl_attn_fwd");
   return 0;
 }
 
@@ -751,9 +775,10 @@ int mmpl_layernorm(const void* x, int ldx, void* y, int ldy, int rows, int d, fl
                    const void* shift, int mod_frame_stride, int rows_per_frame, const void* w, const void* b,
                    mmpl_stream_t stream) {
   if (!w && (!scale || !shift)) return fail("mmpl_layernorm", "need (scale, shift) or (w, b)");
-  LnArgs a{(const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, d, eps, (const bf16_t*)scale, (const bf16_t*)shift, mod_frame_stride,
-           rows_per_frame > 0 ? rows_per_frame : 1, (const bf16_t*)w, (const bf16_t*)b};
-  HIP_TRY(mmpl_launch_layernorm(a, (hipStream_t)stream), "mmpl_layernorm");
+  LnArgs a = ln_args((const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, d, eps);
+  a.scale = (const bf16_t*)scale; a.shift = (const bf16_t*)shift; a.mod_frame_stride = mod_frame_stride;
+  a.rows_per_frame = rows_per_frame > 0 ? rows_per_frame : 1; a.w = (const bf16_t*)w; a.b = (const bf16_t*)b;
+  MMPL_HIP_TRY(mmpl_launch_layernorm(a, (hipStream_t)stream), "mmpl_layernorm");
   return 0;
 }
 
@@ -774,7 +799,7 @@ int mmpl_qknorm_rope_at(MmplDit* h, void* q, int ldq, const void* k, int ldk, co
   a.cos_tab = h->cos_tab; a.sin_tab = h->sin_tab; a.rows_per_frame = h->S; a.grid_w = h->gw;
   for (int i = 0; i < n_frames; ++i) { a.frame_ids[i] = frame_ids[i]; a.k_dst[i] = (bf16_t*)k_dst[i]; a.v_dst[i] = (bf16_t*)v_dst[i]; }
   a.frame_base = frame_base_dev;
-  HIP_TRY(mmpl_launch_qknorm(a, (hipStream_t)stream), "mmpl_qknorm_rope");
+  MMPL_HIP_TRY(mmpl_launch_qknorm(a, (hipStream_t)stream), "mmpl_qknorm_rope");
   return 0;
 }
 
@@ -789,7 +814,7 @@ int mmpl_cfg_unipc_step(const void* flow_cond, const void* flow_uncond, void* x,
   a.c_inv_rk = st->c_inv_rk; a.c_rho0 = st->c_rho0; a.c_rho_last = st->c_rho_last; a.pred_order = st->pred_order;
   a.p_c1 = st->p_c1; a.p_c2 = st->p_c2; a.p_c3 = st->p_c3; a.p_inv_rk = st->p_inv_rk;
   ProfScope ps(K_UNIPC, 0, (hipStream_t)stream);
-  HIP_TRY(mmpl_launch_unipc(a, (hipStream_t)stream), "mmpl_cfg_unipc_step");
+  MMPL_HIP_TRY(mmpl_launch_unipc(a, (hipStream_t)stream), "mmpl_cfg_unipc_step");
   return 0;
 }
 
@@ -803,7 +828,7 @@ int mmpl_cfg_unipc_step_table(const void* flow_cond, const void* flow_uncond, vo
   UniPCArgs a = {};
   a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.x = (bf16_t*)x;
   a.m0 = (bf16_t*)m0; a.m1 = (bf16_t*)m1; a.last_sample = (bf16_t*)last_sample; a.n = n;
-  HIP_TRY(mmpl_launch_unipc_table(a, (const UniPCStepDev*)table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps,
+  MMPL_HIP_TRY(mmpl_launch_unipc_table(a, (const UniPCStepDev*)table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps,
                                   (hipStream_t)stream), "mmpl_cfg_unipc_step_table");
   return 0;
 }

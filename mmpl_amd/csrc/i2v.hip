@@ -7,9 +7,7 @@
 #include <math.h>
 
 #include "../../include/mmpl_hip.h"
-#include "kernels.h"
-
-#include "mmpl_error.h"
+#include "host_util.h"
 
 namespace {
 
@@ -27,8 +25,19 @@ __global__ void add_kernel(bf16_t* a, const bf16_t* b, size_t n) {
 }
 
 hipError_t linear(const bf16_t* x, int K, const bf16_t* w, const bf16_t* b, bf16_t* y, int M, int N, hipStream_t s) {
-  GemmArgs g = {x, K, w, K, b, y, N, M, N, K, EPI_BIAS, nullptr, 0, nullptr, 0, 1, 1.0f, 0, 0, 0, 0, 0};
+  return mmpl_launch_gemm(gemm_args(x, K, w, K, b, y, N, M, N, K, EPI_BIAS), s);
+}
+// y = x + (A . W^T + b), in place on the residual stream
+hipError_t linear_res(const bf16_t* A, int K, const bf16_t* w, const bf16_t* b, bf16_t* x, int M, int N, hipStream_t s) {
+  GemmArgs g = gemm_args(A, K, w, K, b, x, N, M, N, K, EPI_RES);
+  g.res = x; g.ldres = N;
   return mmpl_launch_gemm(g, s);
+}
+// LayerNorm with an affine (w, b)
+hipError_t layernorm(const bf16_t* x, bf16_t* y, int rows, int d, float eps, const bf16_t* w, const bf16_t* b, hipStream_t s) {
+  LnArgs a = ln_args(x, d, y, d, rows, d, eps);
+  a.w = w; a.b = b;
+  return mmpl_launch_layernorm(a, s);
 }
 hipError_t attend(const bf16_t* q, bf16_t* o, const bf16_t* k, const bf16_t* v, int n_kv, int Lq, int dim, hipStream_t s) {
   AttnArgs a = {};
@@ -38,12 +47,6 @@ hipError_t attend(const bf16_t* q, bf16_t* o, const bf16_t* k, const bf16_t* v, 
   return mmpl_launch_attention(a, s);
 }
 int blocks_for(size_t n) { return (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256); }
-
-#define I2V_TRY(expr, where)                                                  \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess) return mmpl_set_error(where, hipGetErrorString(e_)); \
-  } while (0)
 
 }  // namespace
 
@@ -76,14 +79,12 @@ int mmpl_i2v_img_proj(const void* clip_fea, int n_tok, int clip_dim, int dim, co
   bf16_t* t1 = t0 + (size_t)n_tok * clip_dim;
   bf16_t* t2 = t1 + (size_t)n_tok * clip_dim;
   const bf16_t* const* W = (const bf16_t* const*)w;   // proj.0.{weight,bias}, proj.1.{weight,bias}, proj.3.{weight,bias}, proj.4.{weight,bias}
-  LnArgs l0 = {(const bf16_t*)clip_fea, clip_dim, t0, clip_dim, n_tok, clip_dim, 1e-5f, nullptr, nullptr, 0, 1, W[0], W[1]};
-  I2V_TRY(mmpl_launch_layernorm(l0, s), "mmpl_i2v_img_proj: layernorm 0");
-  I2V_TRY(linear(t0, clip_dim, W[2], W[3], t1, n_tok, clip_dim, s), "mmpl_i2v_img_proj: fc1");
-  I2V_TRY(mmpl_launch_gelu_erf(t1, (size_t)n_tok * clip_dim, s), "mmpl_i2v_img_proj: gelu");
-  I2V_TRY(linear(t1, clip_dim, W[4], W[5], t2, n_tok, dim, s), "mmpl_i2v_img_proj: fc2");
-  LnArgs l1 = {t2, dim, (bf16_t*)out, dim, n_tok, dim, 1e-5f, nullptr, nullptr, 0, 1, W[6], W[7]};
-  I2V_TRY(mmpl_launch_layernorm(l1, s), "mmpl_i2v_img_proj: layernorm 1");
-  I2V_TRY(hipGetLastError(), "mmpl_i2v_img_proj");
+  MMPL_HIP_TRY(layernorm((const bf16_t*)clip_fea, t0, n_tok, clip_dim, 1e-5f, W[0], W[1], s), "mmpl_i2v_img_proj: layernorm 0");
+  MMPL_HIP_TRY(linear(t0, clip_dim, W[2], W[3], t1, n_tok, clip_dim, s), "mmpl_i2v_img_proj: fc1");
+  MMPL_HIP_TRY(mmpl_launch_gelu_erf(t1, (size_t)n_tok * clip_dim, s), "mmpl_i2v_img_proj: gelu");
+  MMPL_HIP_TRY(linear(t1, clip_dim, W[4], W[5], t2, n_tok, dim, s), "mmpl_i2v_img_proj: fc2");
+  MMPL_HIP_TRY(layernorm(t2, (bf16_t*)out, n_tok, dim, 1e-5f, W[6], W[7], s), "mmpl_i2v_img_proj: layernorm 1");
+  MMPL_HIP_TRY(hipGetLastError(), "mmpl_i2v_img_proj");
   return 0;
 }
 
@@ -92,9 +93,9 @@ int mmpl_i2v_img_kv(const void* ctx_img, int n_tok, int dim, const void* wk, con
   if (!ctx_img || !wk || !bk || !wv || !bv || !norm_k_img_w || !k_out || !v_out) return mmpl_set_error("mmpl_i2v_img_kv", "null argument");
   if (n_tok < 1 || dim % 128 || dim > 5120) return mmpl_set_error("mmpl_i2v_img_kv", "unsupported dims");
   hipStream_t s = (hipStream_t)stream;
-  I2V_TRY(linear((const bf16_t*)ctx_img, dim, (const bf16_t*)wk, (const bf16_t*)bk, (bf16_t*)k_out, n_tok, dim, s), "mmpl_i2v_img_kv: k_img");
-  I2V_TRY(mmpl_launch_rmsnorm((bf16_t*)k_out, dim, (const bf16_t*)norm_k_img_w, n_tok, dim, eps, s), "mmpl_i2v_img_kv: norm_k_img");
-  I2V_TRY(linear((const bf16_t*)ctx_img, dim, (const bf16_t*)wv, (const bf16_t*)bv, (bf16_t*)v_out, n_tok, dim, s), "mmpl_i2v_img_kv: v_img");
+  MMPL_HIP_TRY(linear((const bf16_t*)ctx_img, dim, (const bf16_t*)wk, (const bf16_t*)bk, (bf16_t*)k_out, n_tok, dim, s), "mmpl_i2v_img_kv: k_img");
+  MMPL_HIP_TRY(mmpl_launch_rmsnorm((bf16_t*)k_out, dim, (const bf16_t*)norm_k_img_w, n_tok, dim, eps, s), "mmpl_i2v_img_kv: norm_k_img");
+  MMPL_HIP_TRY(linear((const bf16_t*)ctx_img, dim, (const bf16_t*)wv, (const bf16_t*)bv, (bf16_t*)v_out, n_tok, dim, s), "mmpl_i2v_img_kv: v_img");
   return 0;
 }
 
@@ -111,13 +112,13 @@ int mmpl_i2v_cross_attn(const void* x, int Lq, int dim, const void* wq, const vo
   bf16_t* q = (bf16_t*)workspace;
   bf16_t* at = q + (size_t)Lq * dim;
   bf16_t* ai = at + (size_t)Lq * dim;
-  I2V_TRY(linear((const bf16_t*)x, dim, (const bf16_t*)wq, (const bf16_t*)bq, q, Lq, dim, s), "mmpl_i2v_cross_attn: q");
-  I2V_TRY(mmpl_launch_rmsnorm(q, dim, (const bf16_t*)norm_q_w, Lq, dim, eps, s), "mmpl_i2v_cross_attn: norm_q");
-  I2V_TRY(attend(q, ai, (const bf16_t*)k_img, (const bf16_t*)v_img, n_img, Lq, dim, s), "mmpl_i2v_cross_attn: image attention");
-  I2V_TRY(attend(q, at, (const bf16_t*)k_txt, (const bf16_t*)v_txt, n_txt, Lq, dim, s), "mmpl_i2v_cross_attn: text attention");
-  I2V_TRY(mmpl_launch_add(at, ai, (size_t)Lq * dim, s), "mmpl_i2v_cross_attn: x + img_x");
-  I2V_TRY(linear(at, dim, (const bf16_t*)wo, (const bf16_t*)bo, (bf16_t*)out, Lq, dim, s), "mmpl_i2v_cross_attn: o");
-  I2V_TRY(hipGetLastError(), "mmpl_i2v_cross_attn");
+  MMPL_HIP_TRY(linear((const bf16_t*)x, dim, (const bf16_t*)wq, (const bf16_t*)bq, q, Lq, dim, s), "mmpl_i2v_cross_attn: q");
+  MMPL_HIP_TRY(mmpl_launch_rmsnorm(q, dim, (const bf16_t*)norm_q_w, Lq, dim, eps, s), "mmpl_i2v_cross_attn: norm_q");
+  MMPL_HIP_TRY(attend(q, ai, (const bf16_t*)k_img, (const bf16_t*)v_img, n_img, Lq, dim, s), "mmpl_i2v_cross_attn: image attention");
+  MMPL_HIP_TRY(attend(q, at, (const bf16_t*)k_txt, (const bf16_t*)v_txt, n_txt, Lq, dim, s), "mmpl_i2v_cross_attn: text attention");
+  MMPL_HIP_TRY(mmpl_launch_add(at, ai, (size_t)Lq * dim, s), "mmpl_i2v_cross_attn: x + img_x");
+  MMPL_HIP_TRY(linear(at, dim, (const bf16_t*)wo, (const bf16_t*)bo, (bf16_t*)out, Lq, dim, s), "mmpl_i2v_cross_attn: o");
+  MMPL_HIP_TRY(hipGetLastError(), "mmpl_i2v_cross_attn");
   return 0;
 }
 
@@ -158,44 +159,30 @@ int mmpl_clip_visual(const void* patches, int n_patch, int pk, int dim, int mlp_
   bf16_t* big = hbuf + al((size_t)n * dim);       // [n, wide] qkv | mlp hidden
   bf16_t* att = big + al((size_t)n * wide);       // [n, H 128]
   // x = [cls; patches . W^T] + pos
-  I2V_TRY(hipMemcpyAsync(x, G[1], (size_t)dim * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "mmpl_clip_visual: cls");
-  {
-    GemmArgs g = {(const bf16_t*)patches, pk, G[0], pk, nullptr, x + dim, dim, n_patch, dim, pk, EPI_BIAS, nullptr, 0, nullptr, 0, 1, 1.0f, 0, 0, 0, 0, 0};
-    I2V_TRY(mmpl_launch_gemm(g, s), "mmpl_clip_visual: patch embedding");
-  }
-  I2V_TRY(mmpl_launch_add(x, G[2], (size_t)n * dim, s), "mmpl_clip_visual: + pos_embedding");
-  {
-    LnArgs l = {x, dim, hbuf, dim, n, dim, eps, nullptr, nullptr, 0, 1, G[3], G[4]};
-    I2V_TRY(mmpl_launch_layernorm(l, s), "mmpl_clip_visual: pre_norm");
-    I2V_TRY(hipMemcpyAsync(x, hbuf, (size_t)n * dim * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "mmpl_clip_visual: pre_norm copy");
-  }
+  MMPL_HIP_TRY(hipMemcpyAsync(x, G[1], (size_t)dim * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "mmpl_clip_visual: cls");
+  MMPL_HIP_TRY(linear((const bf16_t*)patches, pk, G[0], nullptr, x + dim, n_patch, dim, s), "mmpl_clip_visual: patch embedding");
+  MMPL_HIP_TRY(mmpl_launch_add(x, G[2], (size_t)n * dim, s), "mmpl_clip_visual: + pos_embedding");
+  MMPL_HIP_TRY(layernorm(x, hbuf, n, dim, eps, G[3], G[4], s), "mmpl_clip_visual: pre_norm");
+  MMPL_HIP_TRY(hipMemcpyAsync(x, hbuf, (size_t)n * dim * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "mmpl_clip_visual: pre_norm copy");
   for (int b = 0; b < n_blocks; ++b) {
     const bf16_t* const* W = L + 12 * b;
-    LnArgs l1 = {x, dim, hbuf, dim, n, dim, eps, nullptr, nullptr, 0, 1, W[0], W[1]};
-    I2V_TRY(mmpl_launch_layernorm(l1, s), "mmpl_clip_visual: norm1");
-    I2V_TRY(linear(hbuf, dim, W[2], W[3], big, n, 3 * hw, s), "mmpl_clip_visual: to_qkv");
+    MMPL_HIP_TRY(layernorm(x, hbuf, n, dim, eps, W[0], W[1], s), "mmpl_clip_visual: norm1");
+    MMPL_HIP_TRY(linear(hbuf, dim, W[2], W[3], big, n, 3 * hw, s), "mmpl_clip_visual: to_qkv");
     {
       AttnArgs a = {};
       a.q = big; a.ldq = 3 * hw; a.o = att; a.ldo = hw;
       a.k_pages[0] = big + hw; a.v_pages[0] = big + 2 * hw; a.ldk = 3 * hw; a.ldv = 3 * hw;
       a.n_pages = 1; a.page_rows = n; a.Lq = n; a.H = heads; a.scale = 1.0f / sqrtf((float)head_dim); a.cross = 1;
-      I2V_TRY(mmpl_launch_attention(a, s), "mmpl_clip_visual: attention");
+      MMPL_HIP_TRY(mmpl_launch_attention(a, s), "mmpl_clip_visual: attention");
     }
-    {
-      GemmArgs g = {att, hw, W[4], hw, W[5], x, dim, n, dim, hw, EPI_RES, x, dim, nullptr, 0, 1, 1.0f, 0, 0, 0, 0, 0};
-      I2V_TRY(mmpl_launch_gemm(g, s), "mmpl_clip_visual: proj + residual");
-    }
-    LnArgs l2 = {x, dim, hbuf, dim, n, dim, eps, nullptr, nullptr, 0, 1, W[6], W[7]};
-    I2V_TRY(mmpl_launch_layernorm(l2, s), "mmpl_clip_visual: norm2");
-    I2V_TRY(linear(hbuf, dim, W[8], W[9], big, n, mlp_dim, s), "mmpl_clip_visual: mlp.0");
-    I2V_TRY(mmpl_launch_gelu_erf(big, (size_t)n * mlp_dim, s), "mmpl_clip_visual: gelu");
-    {
-      GemmArgs g = {big, mlp_dim, W[10], mlp_dim, W[11], x, dim, n, dim, mlp_dim, EPI_RES, x, dim, nullptr, 0, 1, 1.0f, 0, 0, 0, 0, 0};
-      I2V_TRY(mmpl_launch_gemm(g, s), "mmpl_clip_visual: mlp.2 + residual");
-    }
+    MMPL_HIP_TRY(linear_res(att, hw, W[4], W[5], x, n, dim, s), "mmpl_clip_visual: proj + residual");
+    MMPL_HIP_TRY(layernorm(x, hbuf, n, dim, eps, W[6], W[7], s), "mmpl_clip_visual: norm2");
+    MMPL_HIP_TRY(linear(hbuf, dim, W[8], W[9], big, n, mlp_dim, s), "mmpl_clip_visual: mlp.0");
+    MMPL_HIP_TRY(mmpl_launch_gelu_erf(big, (size_t)n * mlp_dim, s), "mmpl_clip_visual: gelu");
+    MMPL_HIP_TRY(linear_res(big, mlp_dim, W[10], W[11], x, n, dim, s), "mmpl_clip_visual: mlp.2 + residual");
   }
-  I2V_TRY(hipMemcpyAsync(out, x, (size_t)n * dim * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "mmpl_clip_visual: out");
-  I2V_TRY(hipGetLastError(), "mmpl_clip_visual");
+  MMPL_HIP_TRY(hipMemcpyAsync(out, x, (size_t)n * dim * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "mmpl_clip_visual: out");
+  MMPL_HIP_TRY(hipGetLastError(), "mmpl_clip_visual");
   return 0;
 }
 

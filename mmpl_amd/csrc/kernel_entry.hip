@@ -8,11 +8,9 @@
 #include <stdint.h>
 
 #include "../../include/mmpl_hip.h"
-#include "kernels.h"
+#include "host_util.h"
 #include "taehv_kernels.h"
 #include "vae_kernels.h"
-
-#include "mmpl_error.h"
 
 namespace {
 inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
@@ -201,9 +199,8 @@ int mmpl_gemm_ex(const void* A, int lda, const void* W, int ldw, const void* bia
   REJECT(misaligned(bias, 8), me, "bias not 8-byte aligned");
   REJECT(has_res && misaligned(res, 8), me, "res not 8-byte aligned");
   REJECT(epi == EPI_GATE_RES && misaligned(gate, 8), me, "gate not 8-byte aligned");
-  GemmArgs g = {};
-  g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.bias = (const bf16_t*)bias; g.C = (bf16_t*)C; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K; g.epi = epi; g.res = (const bf16_t*)res; g.ldres = ldres; g.gate = (const bf16_t*)gate;
+  GemmArgs g = gemm_args((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (bf16_t*)C, ldc, M, N, K, epi);
+  g.res = (const bf16_t*)res; g.ldres = ldres; g.gate = (const bf16_t*)gate;
   g.gate_frame_stride = gate_frame_stride; g.rows_per_frame = rows_per_frame > 0 ? rows_per_frame : 1; g.alpha = alpha;
   g.batch = batch; g.sA = (long)sA; g.sW = (long)sW; g.sC = (long)sC;
   if (batch > 1) {
@@ -406,8 +403,9 @@ int mmpl_layernorm_ex(const void* x, int ldx, void* y, int ldy, int rows, int d,
   REJECT(pipeline < -1 || pipeline > 1, me, "pipeline outside -1 .. 1");
   REJECT(pipeline == 1 && (d / 8 + 63) / 64 < 6, me, "the pipelined kernel exists from NIT 6 (d > 2560) only");
   REJECT(groups_per_block < 0, me, "groups_per_block < 0");
-  LnArgs a{(const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, d, eps, (const bf16_t*)scale, (const bf16_t*)shift, mod_frame_stride,
-           rows_per_frame > 0 ? rows_per_frame : 1, (const bf16_t*)w, (const bf16_t*)b};
+  LnArgs a = ln_args((const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, d, eps);
+  a.scale = (const bf16_t*)scale; a.shift = (const bf16_t*)shift; a.mod_frame_stride = mod_frame_stride;
+  a.rows_per_frame = rows_per_frame > 0 ? rows_per_frame : 1; a.w = (const bf16_t*)w; a.b = (const bf16_t*)b;
   // (which kernel runs is the plan's decision, made on the host alone: the last check still precedes the first HIP call)
   REJECT(groups_per_block && !mmpl_ln_pipelined(a, pipeline), me, "groups_per_block with the one-row-per-wave kernel");
   const RowPassPlan p = mmpl_ln_plan(a, pipeline, groups_per_block);

@@ -8,9 +8,7 @@
 #include <vector>
 
 #include "../../include/mmpl_hip.h"
-#include "kernels.h"
-
-#include "mmpl_error.h"
+#include "host_util.h"
 
 namespace {
 
@@ -117,33 +115,24 @@ hipError_t mmpl_launch_t5_zero_pad(bf16_t* out, const int* mask, int L, int dim,
 
 namespace {
 
-struct Carve {
-  char* base;
-  size_t off = 0;
-  void* take(size_t bytes) {
-    void* p = base + off;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  }
-};
 struct Ws {
   bf16_t *x, *xn, *qkv, *p, *vt, *attn, *g, *f;
   float* sc;
   size_t bytes;
 };
 Ws carve(const MmplT5Config& c, void* base) {
-  Carve k{(char*)base};
+  Carver k(base);
   const size_t L = c.text_len;
   Ws w;
-  w.x = (bf16_t*)k.take(L * c.dim * 2);
-  w.xn = (bf16_t*)k.take(L * c.dim * 2);
-  w.qkv = (bf16_t*)k.take(L * 3 * c.dim_attn * 2);
-  w.sc = (float*)k.take((size_t)c.num_heads * L * L * 4);
-  w.p = (bf16_t*)k.take((size_t)c.num_heads * L * L * 2);
-  w.vt = (bf16_t*)k.take((size_t)c.dim_attn * L * 2);
-  w.attn = (bf16_t*)k.take(L * c.dim_attn * 2);
-  w.g = (bf16_t*)k.take(L * c.dim_ffn * 2);
-  w.f = (bf16_t*)k.take(L * c.dim_ffn * 2);
+  w.x = k.take<bf16_t>(L * c.dim);
+  w.xn = k.take<bf16_t>(L * c.dim);
+  w.qkv = k.take<bf16_t>(L * 3 * c.dim_attn);
+  w.sc = k.take<float>((size_t)c.num_heads * L * L);
+  w.p = k.take<bf16_t>((size_t)c.num_heads * L * L);
+  w.vt = k.take<bf16_t>((size_t)c.dim_attn * L);
+  w.attn = k.take<bf16_t>(L * c.dim_attn);
+  w.g = k.take<bf16_t>(L * c.dim_ffn);
+  w.f = k.take<bf16_t>(L * c.dim_ffn);
   w.bytes = k.off;
   return w;
 }
@@ -174,31 +163,28 @@ int mmpl_t5_create(const MmplT5Config* c, MmplT5** out) {
 void mmpl_t5_destroy(MmplT5* h) { delete h; }
 
 int mmpl_t5_bind_weights(MmplT5* h, const void* const* ptrs, int n) {
-  if (!h || !ptrs || n != mmpl_t5_num_weights(&h->cfg)) return mmpl_set_error("mmpl_t5_bind_weights", "wrong pointer count");
-  h->w.resize(n);
-  for (int i = 0; i < n; ++i) {
-    if (!ptrs[i]) return mmpl_set_error("mmpl_t5_bind_weights", "null weight pointer");
-    h->w[i] = (const bf16_t*)ptrs[i];
-  }
-  return 0;
+  if (!h || !ptrs) return mmpl_set_error("mmpl_t5_bind_weights", "wrong pointer count");
+  return bind_weight_ptrs(h->w, ptrs, n, mmpl_t5_num_weights(&h->cfg), "mmpl_t5_bind_weights");
 }
 
 size_t mmpl_t5_workspace_bytes(const MmplT5* h) { return h ? carve(h->cfg, nullptr).bytes : 0; }
 
 int mmpl_t5_encode(MmplT5* h, const int* ids, const int* mask, const int* bucket, void* out, void* workspace, size_t workspace_bytes,
                    mmpl_stream_t stream) {
-  if (!h || h->w.empty()) return mmpl_set_error("mmpl_t5_encode", "weights not bound");
-  if (!ids || !mask || !bucket || !out || !workspace) return mmpl_set_error("mmpl_t5_encode", "null argument");
+  const char* me = "mmpl_t5_encode";
+  if (!h || h->w.empty()) return mmpl_set_error(me, "weights not bound");
+  if (!ids || !mask || !bucket || !out || !workspace) return mmpl_set_error(me, "null argument");
   const MmplT5Config& c = h->cfg;
   Ws w = carve(c, workspace);
-  if (workspace_bytes < w.bytes) return mmpl_set_error("mmpl_t5_encode", "workspace too small");
+  if (workspace_bytes < w.bytes) return mmpl_set_error(me, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int L = c.text_len, d = c.dim, da = c.dim_attn, df = c.dim_ffn, H = c.num_heads, hc = da / H;
-  hipError_t err = hipSuccess;
-  auto chk = [&](hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; };
+  ErrLatch el;
+  auto chk = [&](hipError_t e) { el.chk(e, me); };
   auto gemm = [&](const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, int M, int N, int K, int epi, const bf16_t* res,
                   int ldres, int batch = 0, long sA = 0, long sW = 0, long sC = 0) {
-    GemmArgs g{A, lda, W, ldw, nullptr, (bf16_t*)C, ldc, M, N, K, epi, res, ldres, nullptr, 0, 1, 1.0f, 0, batch, sA, sW, sC};
+    GemmArgs g = gemm_args(A, lda, W, ldw, nullptr, (bf16_t*)C, ldc, M, N, K, epi);
+    g.res = res; g.ldres = ldres; g.batch = batch; g.sA = sA; g.sW = sW; g.sC = sC;
     chk(mmpl_launch_gemm(g, s));
   };
   auto norm = [&](const bf16_t* x, const bf16_t* wt, bf16_t* y) {
@@ -225,8 +211,7 @@ int mmpl_t5_encode(MmplT5* h, const int* ids, const int* mask, const int* bucket
   norm(w.x, h->w[T_NORM], (bf16_t*)out);
   chk(mmpl_launch_t5_zero_pad((bf16_t*)out, mask, L, d, s));
   chk(hipGetLastError());
-  if (err != hipSuccess) return mmpl_set_error("mmpl_t5_encode", hipGetErrorString(err));
-  return 0;
+  return el.report();
 }
 
 }  // extern "C"

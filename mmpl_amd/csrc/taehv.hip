@@ -16,10 +16,7 @@
 #include <vector>
 
 #include "../../include/mmpl_hip.h"
-#include "kernels.h"
-#include "taehv_kernels.h"
-
-#include "mmpl_error.h"
+#include "taehv_host.h"
 
 namespace {
 
@@ -45,47 +42,18 @@ std::vector<std::string> build_names() {
 
 }  // namespace
 
-struct MmplTaehv {
-  int lat_h = 0, lat_w = 0;
-  std::vector<const bf16_t*> w;
-  size_t need = 0;
-  void* ws = nullptr;     // the workspace the current video's memories live in; null = none yet (after create / reset)
-};
+struct MmplTaehv : TaehvHandle {};
 
 namespace {
-
-struct Run {
-  MmplTaehv* v;
-  char* base;
-  size_t off = 0;
-  hipStream_t s;
-  bool dry;
-  int wi = 0;             // next weight slot, in build_names() order
-  hipError_t err = hipSuccess;
-  const char* where = "";
-  bf16_t* frames(int n, int H, int W, int C, size_t* stride = nullptr) {
-    const size_t fr = (size_t)(H + 2) * (W + 2) * C;
-    if (stride) *stride = fr;
-    bf16_t* p = (bf16_t*)(base + off);
-    off += (n * fr * 2 + 255) & ~(size_t)255;
-    return p;
-  }
-  const bf16_t* next_w() { return dry ? nullptr : v->w[wi++]; }
-  void chk(hipError_t e, const char* w) { if (e != hipSuccess && err == hipSuccess) { err = e; where = w; } }
-  void conv(TaehvConvArgs& g) {
-    if (!dry) chk(taehv_launch_conv(g, s), "taehv conv");
-  }
-};
 
 // n <= GROUP consecutive latent frames -> 4 n pixel frames at t_out of out.  The dry pass (r.dry) only lays the workspace out;
 // the layout is that of a full group whatever n is, so every memory keeps its address from call to call.
 // The frames of a group go through each layer in ONE launch (n / n / 2n frames at the first three levels): at 480p a single
 // frame is 128 blocks at the 256-channel level and 210 at the next -- less than one block per CU.  Only the 8x level (4 frames per
 // latent frame, 1560 patches each at 480p) runs one latent frame at a time, so its buffers stay those of one latent frame.
-void decode_group(Run& r, const bf16_t* z, int n, void* out, int fmt, int t_out) {
+void decode_group(TaehvRun& r, const bf16_t* z, int n, void* out, int fmt, int t_out) {
   int H = r.v->lat_h, W = r.v->lat_w, T = n, Ta = GROUP;     // frames at this level: this call's, and the layout's
-  r.off = 0;
-  r.wi = 0;
+  r.rewind();
   size_t fs, fz;
   bf16_t* zin = r.frames(Ta, H, W, 32, &fz);
   // x: where the current level's first MemBlock finds its input frames (slot 0 of each run is the memory)
@@ -102,19 +70,7 @@ void decode_group(Run& r, const bf16_t* z, int n, void* out, int fmt, int t_out)
     const int C = CH[l];
     bf16_t* t1 = r.frames(Ta, H, W, C);
     bf16_t* t2 = r.frames(Ta, H, W, C);
-    for (int b = 0; b < 3; ++b) {
-      // the block's output: the next block's input run, or (last block of the level) a plain run of T frames
-      bf16_t* y = b < 2 ? r.frames(1 + Ta, H, W, C) + fs : r.frames(Ta, H, W, C);
-      TaehvConvArgs g = {};
-      g.ntaps = 9; g.Nw = g.N = g.Nsplit = g.ldd = C; g.T = T; g.Ho = H; g.Wo = W; g.fsd = fs; g.relu = 1;
-      TaehvConvArgs c1 = g, c2 = g, c3 = g;
-      c1.src0 = x + fs; c1.src1 = x; c1.fs0 = c1.fs1 = fs; c1.C0 = c1.C1 = C; c1.Wfrag = r.next_w(); c1.bias = r.next_w(); c1.dst = t1;
-      c2.src0 = t1; c2.fs0 = fs; c2.C0 = C; c2.Wfrag = r.next_w(); c2.bias = r.next_w(); c2.dst = t2;
-      c3.src0 = t2; c3.fs0 = fs; c3.C0 = C; c3.Wfrag = r.next_w(); c3.bias = r.next_w(); c3.dst = y;
-      c3.skip = x + fs; c3.fss = fs; c3.keep = x;
-      r.conv(c1); r.conv(c2); r.conv(c3);
-      x = b < 2 ? y - fs : y;
-    }
+    for (int b = 0; b < 3; ++b) x = memblock(r, x, t1, t2, fs, C, T, Ta, H, W, b == 2);
     // level change: TGrow at this resolution (C -> GROW * C channels = GROW frames), then the up-sampling 3x3 conv
     const int S = GROW[l], Cn = CH[l + 1];
     bf16_t* grown = r.frames(Ta * S, H, W, C);
@@ -155,10 +111,10 @@ void decode_group(Run& r, const bf16_t* z, int n, void* out, int fmt, int t_out)
   }
 }
 
-size_t layout_bytes(MmplTaehv* v) {
-  Run r{v, nullptr, 0, nullptr, true};
+size_t layout_bytes(TaehvHandle* v) {
+  TaehvRun r(v, nullptr, nullptr, "taehv conv");
   decode_group(r, nullptr, GROUP, nullptr, 0, 0);
-  return r.off;
+  return r.k.off;
 }
 
 }  // namespace
@@ -174,32 +130,19 @@ const char* mmpl_taehv_weight_name(int i) {
 
 int mmpl_taehv_create(int lat_h, int lat_w, MmplTaehv** out) {
   if (!out || lat_h < 1 || lat_w < 1) return mmpl_set_error("mmpl_taehv_create", "bad arguments");
-  MmplTaehv* v = new MmplTaehv();
-  v->lat_h = lat_h;
-  v->lat_w = lat_w;
-  v->need = layout_bytes(v);
-  *out = v;
+  *out = taehv_new<MmplTaehv>(lat_h, lat_w, layout_bytes);
   return 0;
 }
 
 void mmpl_taehv_destroy(MmplTaehv* v) { delete v; }
 
 int mmpl_taehv_bind_weights(MmplTaehv* v, const void* const* ptrs, int n) {
-  if (!v || !ptrs || n != mmpl_taehv_num_weights()) return mmpl_set_error("mmpl_taehv_bind_weights", "wrong pointer count");
-  for (int i = 0; i < n; ++i)
-    if (!ptrs[i]) return mmpl_set_error("mmpl_taehv_bind_weights", "null weight pointer");
-  v->w.resize(n);
-  for (int i = 0; i < n; ++i) v->w[i] = (const bf16_t*)ptrs[i];
-  return 0;
+  return taehv_bind(v, ptrs, n, mmpl_taehv_num_weights(), "mmpl_taehv_bind_weights");
 }
 
 size_t mmpl_taehv_workspace_bytes(MmplTaehv* v) { return v ? v->need : 0; }
 
-int mmpl_taehv_reset(MmplTaehv* v) {
-  if (!v) return mmpl_set_error("mmpl_taehv_reset", "null argument");
-  v->ws = nullptr;          // the next decode binds a workspace again and clears it: zero memories
-  return 0;
-}
+int mmpl_taehv_reset(MmplTaehv* v) { return taehv_reset(v, "mmpl_taehv_reset"); }
 
 int mmpl_taehv_decode(MmplTaehv* v, const void* z, int n_frames, void* out, int out_format, int* n_px_frames_out, void* ws,
                       size_t ws_bytes, mmpl_stream_t stream) {
@@ -208,20 +151,13 @@ int mmpl_taehv_decode(MmplTaehv* v, const void* z, int n_frames, void* out, int 
   if (n_frames < 1) return mmpl_set_error("mmpl_taehv_decode", "n_frames < 1");
   if (out_format != 0 && out_format != 1) return mmpl_set_error("mmpl_taehv_decode", "unknown out_format");
   if (!z || !out) return mmpl_set_error("mmpl_taehv_decode", "null argument");
-  if (!ws || ws_bytes < v->need) return mmpl_set_error("mmpl_taehv_decode", "workspace too small");
-  if (v->ws && v->ws != ws)
-    return mmpl_set_error("mmpl_taehv_decode", "workspace differs from the one this video's memories live in (reset first)");
-  Run r{v, (char*)ws, 0, (hipStream_t)stream, false};
-  if (!v->ws) {             // first call of a video: zero memories (and the frames' zero borders)
-    if (hipMemsetAsync(ws, 0, v->need, r.s) != hipSuccess) return mmpl_set_error("mmpl_taehv_decode", "memset failed");
-    v->ws = ws;
-  }
+  if (taehv_bind_workspace(v, ws, ws_bytes, (hipStream_t)stream, "mmpl_taehv_decode")) return 1;
+  TaehvRun r(v, ws, (hipStream_t)stream, "taehv conv");
   const size_t zf = (size_t)16 * v->lat_h * v->lat_w;
   for (int i = 0; i < n_frames; i += GROUP)
     decode_group(r, (const bf16_t*)z + i * zf, n_frames - i < GROUP ? n_frames - i : GROUP, out, out_format, 4 * i);
   if (n_px_frames_out) *n_px_frames_out = 4 * n_frames;
-  if (r.err != hipSuccess) return mmpl_set_error(r.where, hipGetErrorString(r.err));
-  return 0;
+  return r.report();
 }
 
 }  // extern "C"

@@ -16,10 +16,7 @@
 #include <vector>
 
 #include "../../include/mmpl_hip.h"
-#include "kernels.h"
-#include "taehv_kernels.h"
-
-#include "mmpl_error.h"
+#include "taehv_host.h"
 
 namespace {
 
@@ -44,58 +41,30 @@ std::vector<std::string> build_names() {
 
 }  // namespace
 
-struct MmplTaehvEnc {
-  int lat_h = 0, lat_w = 0;
-  std::vector<const bf16_t*> w;
-  size_t need = 0;
-  void* ws = nullptr;     // the workspace the current video's memories live in; null = none yet (after create / reset)
-};
+struct MmplTaehvEnc : TaehvHandle {};
 
 namespace {
 
-struct Run {
-  MmplTaehvEnc* v;
-  char* base;
-  size_t off = 0;
-  hipStream_t s;
-  bool dry;
-  int wi = 0;             // next weight slot, in build_names() order
-  hipError_t err = hipSuccess;
-  const char* where = "";
-  bf16_t* frames(int n, int H, int W, int ch, size_t* stride = nullptr) {
-    const size_t fr = (size_t)(H + 2) * (W + 2) * ch;
-    if (stride) *stride = fr;
-    bf16_t* p = (bf16_t*)(base + off);
-    off += (n * fr * 2 + 255) & ~(size_t)255;
-    return p;
-  }
-  const bf16_t* next_w() { return dry ? nullptr : v->w[wi++]; }
-  void chk(hipError_t e, const char* w) { if (e != hipSuccess && err == hipSuccess) { err = e; where = w; } }
-  void conv(TaehvConvArgs& g) {
-    if (!dry) chk(taehv_launch_conv(g, s), "taehv_enc conv");
-  }
-  // TPool(S) over T output frames: frame t = W . cat[src frame S t, .., S t + S - 1]
-  void tpool(const bf16_t* src, size_t fs, int S, const bf16_t* wf, int T, int H, int W, bf16_t* dst) {
-    TaehvConvArgs g = {};
-    g.src0 = src; g.fs0 = (long)(S * fs); g.C0 = C; g.ntaps = 1; g.Wfrag = wf; g.Nw = g.N = g.Nsplit = g.ldd = C;
-    if (S == 2) { g.src1 = src + fs; g.fs1 = (long)(2 * fs); g.C1 = C; }
-    g.T = T; g.Ho = H; g.Wo = W; g.dst = dst; g.fsd = (long)fs;
-    conv(g);
-  }
-  void s2(const bf16_t* src, size_t fs, const bf16_t* wf, int T, int Ho, int Wo, bf16_t* dst, size_t fsd) {
-    TaehvConvS2Args g = {};
-    g.src = src; g.fs = (long)fs; g.C = C; g.Wfrag = wf; g.Nw = C; g.T = T; g.Ho = Ho; g.Wo = Wo; g.dst = dst; g.fsd = (long)fsd;
-    if (!dry) chk(taehv_launch_conv_s2(g, s), "taehv_enc conv_s2");
-  }
-};
+// TPool(S) over T output frames: frame t = W . cat[src frame S t, .., S t + S - 1]
+void tpool(TaehvRun& r, const bf16_t* src, size_t fs, int S, const bf16_t* wf, int T, int H, int W, bf16_t* dst) {
+  TaehvConvArgs g = {};
+  g.src0 = src; g.fs0 = (long)(S * fs); g.C0 = C; g.ntaps = 1; g.Wfrag = wf; g.Nw = g.N = g.Nsplit = g.ldd = C;
+  if (S == 2) { g.src1 = src + fs; g.fs1 = (long)(2 * fs); g.C1 = C; }
+  g.T = T; g.Ho = H; g.Wo = W; g.dst = dst; g.fsd = (long)fs;
+  r.conv(g);
+}
+void conv_s2(TaehvRun& r, const bf16_t* src, size_t fs, const bf16_t* wf, int T, int Ho, int Wo, bf16_t* dst, size_t fsd) {
+  TaehvConvS2Args g = {};
+  g.src = src; g.fs = (long)fs; g.C = C; g.Wfrag = wf; g.Nw = C; g.T = T; g.Ho = Ho; g.Wo = Wo; g.dst = dst; g.fsd = (long)fsd;
+  if (!r.dry) r.chk(taehv_launch_conv_s2(g, r.s), "taehv_enc conv_s2");
+}
 
 // 4 n pixel frames (n <= GROUP latent frames) -> n latent frames at f_out of z_out.  The dry pass (r.dry) only lays the workspace
 // out; the layout is that of a full group whatever n is, so every memory keeps its address from call to call.
-void encode_group(Run& r, const void* px, int fmt, int n, bf16_t* z_out, int f_out) {
+void encode_group(TaehvRun& r, const void* px, int fmt, int n, bf16_t* z_out, int f_out) {
   const int h = r.v->lat_h, w = r.v->lat_w;
   int H = 8 * h, W = 8 * w;
-  r.off = 0;
-  r.wi = 0;
+  r.rewind();
   // the full-resolution level, one latent frame (4 pixel frames) at a time
   size_t f8, fs;
   bf16_t* full = r.frames(4, H, W, C, &f8);
@@ -113,35 +82,23 @@ void encode_group(Run& r, const void* px, int fmt, int n, bf16_t* z_out, int f_o
     g.px = (const char*)px + (size_t)i * px_stride; g.fmt = fmt; g.Wfrag = w_in; g.bias = b_in; g.T = 4; g.H = H; g.W = W;
     g.dst = full; g.fsd = (long)f8;
     if (!r.dry) r.chk(taehv_launch_conv_in(g, r.s), "taehv_enc conv_in");
-    r.tpool(full, f8, 2, w_pool, 2, H, W, half);
-    r.s2(half, f8, w_s2, 2, H / 2, W / 2, x + fs * (1 + 2 * i), fs);
+    tpool(r, full, f8, 2, w_pool, 2, H, W, half);
+    conv_s2(r, half, f8, w_s2, 2, H / 2, W / 2, x + fs * (1 + 2 * i), fs);
   }
   H /= 2; W /= 2;
   for (int l = 0; l < NLEV; ++l) {
     bf16_t* t1 = r.frames(Ta, H, W, C);
     bf16_t* t2 = r.frames(Ta, H, W, C);
-    for (int b = 0; b < 3; ++b) {
-      // the block's output: the next block's input run, or (last block of the level) a plain run of T frames
-      bf16_t* y = b < 2 ? r.frames(1 + Ta, H, W, C) + fs : r.frames(Ta, H, W, C);
-      TaehvConvArgs g = {};
-      g.ntaps = 9; g.Nw = g.N = g.Nsplit = g.ldd = C; g.T = T; g.Ho = H; g.Wo = W; g.fsd = (long)fs; g.relu = 1;
-      TaehvConvArgs c1 = g, c2 = g, c3 = g;
-      c1.src0 = x + fs; c1.src1 = x; c1.fs0 = c1.fs1 = (long)fs; c1.C0 = c1.C1 = C; c1.Wfrag = r.next_w(); c1.bias = r.next_w(); c1.dst = t1;
-      c2.src0 = t1; c2.fs0 = (long)fs; c2.C0 = C; c2.Wfrag = r.next_w(); c2.bias = r.next_w(); c2.dst = t2;
-      c3.src0 = t2; c3.fs0 = (long)fs; c3.C0 = C; c3.Wfrag = r.next_w(); c3.bias = r.next_w(); c3.dst = y;
-      c3.skip = x + fs; c3.fss = (long)fs; c3.keep = x;
-      r.conv(c1); r.conv(c2); r.conv(c3);
-      x = b < 2 ? y - fs : y;
-    }
+    for (int b = 0; b < 3; ++b) x = memblock(r, x, t1, t2, fs, C, T, Ta, H, W, b == 2);
     if (l == NLEV - 1) break;
     // level change: TPool at this resolution, then the stride-2 conv into the next level's first run
     const int S = POOL[l + 1];
     bf16_t* pooled = r.frames(Ta / S, H, W, C);
-    r.tpool(x, fs, S, r.next_w(), T / S, H, W, pooled);
+    tpool(r, x, fs, S, r.next_w(), T / S, H, W, pooled);
     T /= S; Ta /= S; H /= 2; W /= 2;
     size_t fsn;
     bf16_t* nx = r.frames(1 + Ta, H, W, C, &fsn);
-    r.s2(pooled, fs, r.next_w(), T, H, W, nx + fsn, fsn);
+    conv_s2(r, pooled, fs, r.next_w(), T, H, W, nx + fsn, fsn);
     x = nx;
     fs = fsn;
   }
@@ -155,10 +112,10 @@ void encode_group(Run& r, const void* px, int fmt, int n, bf16_t* z_out, int f_o
   if (!r.dry) r.chk(taehv_launch_z_out(head, z_out, T, H, W, f_out, r.s), "taehv_enc z_out");
 }
 
-size_t layout_bytes(MmplTaehvEnc* v) {
-  Run r{v, nullptr, 0, nullptr, true};
+size_t layout_bytes(TaehvHandle* v) {
+  TaehvRun r(v, nullptr, nullptr, "taehv_enc conv");
   encode_group(r, nullptr, 0, GROUP, nullptr, 0);
-  return r.off;
+  return r.k.off;
 }
 
 }  // namespace
@@ -174,32 +131,19 @@ const char* mmpl_taehv_enc_weight_name(int i) {
 
 int mmpl_taehv_enc_create(int lat_h, int lat_w, MmplTaehvEnc** out) {
   if (!out || lat_h < 1 || lat_w < 1 || lat_h > 4096 || lat_w > 4096) return mmpl_set_error("mmpl_taehv_enc_create", "bad arguments");
-  MmplTaehvEnc* v = new MmplTaehvEnc();
-  v->lat_h = lat_h;
-  v->lat_w = lat_w;
-  v->need = layout_bytes(v);
-  *out = v;
+  *out = taehv_new<MmplTaehvEnc>(lat_h, lat_w, layout_bytes);
   return 0;
 }
 
 void mmpl_taehv_enc_destroy(MmplTaehvEnc* v) { delete v; }
 
 int mmpl_taehv_enc_bind_weights(MmplTaehvEnc* v, const void* const* ptrs, int n) {
-  if (!v || !ptrs || n != mmpl_taehv_enc_num_weights()) return mmpl_set_error("mmpl_taehv_enc_bind_weights", "wrong pointer count");
-  for (int i = 0; i < n; ++i)
-    if (!ptrs[i]) return mmpl_set_error("mmpl_taehv_enc_bind_weights", "null weight pointer");
-  v->w.resize(n);
-  for (int i = 0; i < n; ++i) v->w[i] = (const bf16_t*)ptrs[i];
-  return 0;
+  return taehv_bind(v, ptrs, n, mmpl_taehv_enc_num_weights(), "mmpl_taehv_enc_bind_weights");
 }
 
 size_t mmpl_taehv_enc_workspace_bytes(MmplTaehvEnc* v) { return v ? v->need : 0; }
 
-int mmpl_taehv_enc_reset(MmplTaehvEnc* v) {
-  if (!v) return mmpl_set_error("mmpl_taehv_enc_reset", "null argument");
-  v->ws = nullptr;          // the next encode binds a workspace again and clears it: zero memories
-  return 0;
-}
+int mmpl_taehv_enc_reset(MmplTaehvEnc* v) { return taehv_reset(v, "mmpl_taehv_enc_reset"); }
 
 int mmpl_taehv_encode(MmplTaehvEnc* v, const void* px, int in_format, int n_frames, void* z_out, int* n_latents_out, void* ws,
                       size_t ws_bytes, mmpl_stream_t stream) {
@@ -209,20 +153,14 @@ int mmpl_taehv_encode(MmplTaehvEnc* v, const void* px, int in_format, int n_fram
   if (n_frames < 4 || n_frames % 4) return mmpl_set_error(me, "n_frames must be a multiple of 4, at least 4");
   if (in_format != 0 && in_format != 1) return mmpl_set_error(me, "unknown in_format");
   if (!px || !z_out) return mmpl_set_error(me, "null argument");
-  if (!ws || ws_bytes < v->need) return mmpl_set_error(me, "workspace too small");
-  if (v->ws && v->ws != ws) return mmpl_set_error(me, "workspace differs from the one this video's memories live in (reset first)");
-  Run r{v, (char*)ws, 0, (hipStream_t)stream, false};
-  if (!v->ws) {             // first call of a video: zero memories (and the frames' zero borders)
-    if (hipMemsetAsync(ws, 0, v->need, r.s) != hipSuccess) return mmpl_set_error(me, "memset failed");
-    v->ws = ws;
-  }
+  if (taehv_bind_workspace(v, ws, ws_bytes, (hipStream_t)stream, me)) return 1;
+  TaehvRun r(v, ws, (hipStream_t)stream, "taehv_enc conv");
   const int n_lat = n_frames / 4;
   const size_t pf = (size_t)3 * 64 * v->lat_h * v->lat_w * (in_format == 0 ? sizeof(float) : 1);   // bytes of one pixel frame
   for (int i = 0; i < n_lat; i += GROUP)
     encode_group(r, (const char*)px + (size_t)4 * i * pf, in_format, n_lat - i < GROUP ? n_lat - i : GROUP, (bf16_t*)z_out, i);
   if (n_latents_out) *n_latents_out = n_lat;
-  if (r.err != hipSuccess) return mmpl_set_error(r.where, hipGetErrorString(r.err));
-  return 0;
+  return r.report();
 }
 
 }  // extern "C"

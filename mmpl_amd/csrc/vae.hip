@@ -9,11 +9,9 @@
 #include <vector>
 
 #include "../../include/mmpl_hip.h"
-#include "kernels.h"
+#include "host_util.h"
 #include "mmpl_config.h"
 #include "vae_kernels.h"
-
-#include "mmpl_error.h"
 
 namespace {
 
@@ -74,7 +72,7 @@ struct Arena {
   std::map<std::string, std::pair<size_t, size_t>> named;
   bf16_t* get(const std::string& name, size_t elems, size_t elem_bytes = 2) {
     auto it = named.find(name);
-    const size_t bytes = (elems * elem_bytes + 255) & ~(size_t)255;
+    const size_t bytes = round256(elems * elem_bytes);
     if (it == named.end()) {
       named[name] = {off, bytes};
       it = named.find(name);
@@ -118,19 +116,20 @@ struct MmplVaeStream {
 
 namespace {
 
-struct Ctx {
+struct Ctx : ErrLatch {
   MmplVae* v;
   Arena& ar;
   hipStream_t s;
   bool dry;
   std::map<std::string, int>& ring_base;
   std::map<std::string, bool>& prefilled;
-  hipError_t err = hipSuccess;
-  const char* where = "";
-  size_t plain_elems = 0;
-  Ctx(MmplVae* v_, VaeState& st, hipStream_t s_, bool dry_) : v(v_), ar(st.ar), s(s_), dry(dry_), ring_base(st.ring_base), prefilled(st.prefilled) {}
+  size_t plain_elems;     // of each of the four plain activation buffers: 4 frames of 96 channels at full resolution
+  Ctx(MmplVae* v_, VaeState& st, hipStream_t s_, bool dry_, void* ws = nullptr)
+      : v(v_), ar(st.ar), s(s_), dry(dry_), ring_base(st.ring_base), prefilled(st.prefilled),
+        plain_elems((size_t)4 * (v_->lat_h * 8) * (v_->lat_w * 8) * 96) {
+    ar.base = (char*)ws;
+  }
   bf16_t* plain(int i) { return ar.get("plain" + std::to_string(i), plain_elems); }
-  void chk(hipError_t e, const char* w) { if (e != hipSuccess && err == hipSuccess) { err = e; where = w; } }
 };
 
 void copy_slots(Ctx& c, bf16_t* vol, size_t slot_elems, int from, int to, int n) {
@@ -201,7 +200,8 @@ void conv(Ctx& c, const bf16_t* src, int Cin, int Hp, int Wp, int st, int sy, in
 void gemm(Ctx& c, const bf16_t* A, int lda, const bf16_t* Wt, int ldw, const bf16_t* bias, void* C, int ldc, int M, int N, int K, int epi,
           const bf16_t* res, int ldres, float alpha = 1.f) {
   if (c.dry) return;
-  GemmArgs g{A, lda, Wt, ldw, bias, (bf16_t*)C, ldc, M, N, K, epi, res, ldres, nullptr, 0, 1, alpha, 0, 0, 0, 0, 0};
+  GemmArgs g = gemm_args(A, lda, Wt, ldw, bias, (bf16_t*)C, ldc, M, N, K, epi);
+  g.res = res; g.ldres = ldres; g.alpha = alpha;
   c.chk(mmpl_launch_gemm(g, c.s), "gemm");
 }
 
@@ -442,15 +442,12 @@ void encoder_chunk(Ctx& c, const bf16_t* px, int Ttot, int t0, int T, bool first
   }
 }
 
-size_t plain_elems_for(const MmplVae* v) { return (size_t)4 * (v->lat_h * 8) * (v->lat_w * 8) * 96; }
-
 // The decoder's workspace layout: a dry pass over the video's first frame and one later frame, in the order a decode meets them
 // (the first frame skips the time_conv volumes; a one-shot decode lays its arena out in the same order as it goes).  A stream
 // keeps this layout for its lifetime, so a call that begins in the middle of a video finds every volume where the calls before
 // it left it.
 void decoder_layout(MmplVae* v, VaeState& st) {
   Ctx c(v, st, nullptr, true);
-  c.plain_elems = plain_elems_for(v);
   float dummy[16] = {0};
   decoder_frame(c, nullptr, 0, true, dummy, dummy, nullptr, 0, 0);
   decoder_frame(c, nullptr, 1, false, dummy, dummy, nullptr, 0, 1);
@@ -481,13 +478,8 @@ int mmpl_vae_create(int lat_h, int lat_w, MmplVae** out) {
 void mmpl_vae_destroy(MmplVae* v) { delete v; }
 
 int mmpl_vae_bind_weights(MmplVae* v, const void* const* ptrs, int n) {
-  if (!v || !ptrs || n != (int)v->names.size()) return mmpl_set_error("mmpl_vae_bind_weights", "wrong pointer count");
-  v->w.resize(n);
-  for (int i = 0; i < n; ++i) {
-    if (!ptrs[i]) return mmpl_set_error("mmpl_vae_bind_weights", "null weight pointer");
-    v->w[i] = (const bf16_t*)ptrs[i];
-  }
-  return 0;
+  if (!v || !ptrs) return mmpl_set_error("mmpl_vae_bind_weights", "wrong pointer count");
+  return bind_weight_ptrs(v->w, ptrs, n, (int)v->names.size(), "mmpl_vae_bind_weights");
 }
 
 size_t mmpl_vae_workspace_bytes(MmplVae* v, int mode) {
@@ -497,7 +489,6 @@ size_t mmpl_vae_workspace_bytes(MmplVae* v, int mode) {
     decoder_layout(v, st);
   } else {
     Ctx c(v, st, nullptr, true);
-    c.plain_elems = plain_elems_for(v);
     float dummy[16] = {0};
     encoder_chunk(c, nullptr, 5, 0, 1, true, dummy, dummy, nullptr, 0);
     encoder_chunk(c, nullptr, 5, 1, 4, false, dummy, dummy, nullptr, 1);
@@ -512,14 +503,11 @@ int mmpl_vae_decode(MmplVae* v, const void* z, int n_frames, const float* mean, 
   const size_t need = mmpl_vae_workspace_bytes(v, 0);
   if (ws_bytes < need) return mmpl_set_error("mmpl_vae_decode", "workspace too small");
   VaeState st;
-  Ctx c(v, st, (hipStream_t)stream, false);
-  c.ar.base = (char*)ws;
-  c.plain_elems = plain_elems_for(v);
+  Ctx c(v, st, (hipStream_t)stream, false, ws);
   if (hipMemsetAsync(ws, 0, need, c.s) != hipSuccess) return mmpl_set_error("mmpl_vae_decode", "memset failed");  // clear_cache()
   int t_out = 0;
   for (int i = 0; i < n_frames; ++i) t_out += decoder_frame(c, (const bf16_t*)z, i, i == 0, mean, inv_std, out, 0, t_out);
-  if (c.err != hipSuccess) return mmpl_set_error(c.where, hipGetErrorString(c.err));
-  return 0;
+  return c.report();
 }
 
 int mmpl_vae_encode(MmplVae* v, const void* px, int n_px_frames, const float* mean, const float* inv_std, void* out, void* ws,
@@ -529,15 +517,12 @@ int mmpl_vae_encode(MmplVae* v, const void* px, int n_px_frames, const float* me
   const size_t need = mmpl_vae_workspace_bytes(v, 1);
   if (ws_bytes < need) return mmpl_set_error("mmpl_vae_encode", "workspace too small");
   VaeState st;
-  Ctx c(v, st, (hipStream_t)stream, false);
-  c.ar.base = (char*)ws;
-  c.plain_elems = plain_elems_for(v);
+  Ctx c(v, st, (hipStream_t)stream, false, ws);
   if (hipMemsetAsync(ws, 0, need, c.s) != hipSuccess) return mmpl_set_error("mmpl_vae_encode", "memset failed");
   const int iters = 1 + (n_px_frames - 1) / 4;
   for (int i = 0; i < iters; ++i)
     encoder_chunk(c, (const bf16_t*)px, n_px_frames, i == 0 ? 0 : 1 + 4 * (i - 1), i == 0 ? 1 : 4, i == 0, mean, inv_std, (float*)out, i);
-  if (c.err != hipSuccess) return mmpl_set_error(c.where, hipGetErrorString(c.err));
-  return 0;
+  return c.report();
 }
 
 int mmpl_vae_stream_create(MmplVae* v, MmplVaeStream** out) {
@@ -573,9 +558,7 @@ int mmpl_vae_stream_decode(MmplVaeStream* s, const void* z, int n_frames, const 
   if (!ws || ws_bytes < s->need) return mmpl_set_error("mmpl_vae_stream_decode", "workspace too small");
   if (s->ws && s->ws != ws)
     return mmpl_set_error("mmpl_vae_stream_decode", "workspace differs from the one this video's cache lives in (reset first)");
-  Ctx c(v, s->st, (hipStream_t)stream, false);
-  c.ar.base = (char*)ws;
-  c.plain_elems = plain_elems_for(v);
+  Ctx c(v, s->st, (hipStream_t)stream, false, ws);
   if (!s->ws) {             // first call of a video: clear_cache()
     if (hipMemsetAsync(ws, 0, s->need, c.s) != hipSuccess) return mmpl_set_error("mmpl_vae_stream_decode", "memset failed");
     s->ws = ws;
@@ -586,8 +569,7 @@ int mmpl_vae_stream_decode(MmplVaeStream* s, const void* z, int n_frames, const 
     ++s->st.frames_done;
   }
   if (n_px_frames_out) *n_px_frames_out = t_out;
-  if (c.err != hipSuccess) return mmpl_set_error(c.where, hipGetErrorString(c.err));
-  return 0;
+  return c.report();
 }
 
 }  // extern "C"

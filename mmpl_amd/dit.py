@@ -124,8 +124,7 @@ class DitEngine:
         w = slot_tensors(self._lib, g, self.L, self.dim, self.in_dim)
         n = self._lib.mmpl_dit_num_weights(C.byref(self._c))
         assert len(w) == n, (len(w), n)
-        arr = (C.c_void_p * n)(*[t.data_ptr() for t in w])
-        _lib.check(self._lib.mmpl_dit_bind_weights(self._h, arr, n), "mmpl_dit_bind_weights")
+        _lib.bind_weights(self._lib.mmpl_dit_bind_weights, self._h, w, "mmpl_dit_bind_weights")
         self._weights = w      # keep alive: the library borrows the pointers
         if self.model_type == "i2v":
             self._i2v_w = dict(

@@ -67,8 +67,7 @@ class T5Engine:
                                  f"[{self.cfg['num_buckets']}, {self.cfg['num_heads']}]")
         n = self._lib.mmpl_t5_num_weights(C.byref(self._c))
         assert len(w) == n
-        arr = (C.c_void_p * n)(*[t.data_ptr() for t in w])
-        _lib.check(self._lib.mmpl_t5_bind_weights(self._h, arr, n), "mmpl_t5_bind_weights")
+        _lib.bind_weights(self._lib.mmpl_t5_bind_weights, self._h, w, "mmpl_t5_bind_weights")
         self._weights = w
 
     def encode(self, ids: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:

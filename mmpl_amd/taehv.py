@@ -30,30 +30,63 @@ def patch_tgrow_layers(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-class TaehvEngine:
+class _TaehvHalf:
+    """What the two engines share: the library handle behind the symbol prefix ``_SYM`` (<_SYM>_create / _destroy /
+    _num_weights / _weight_name / _bind_weights / _reset / _workspace_bytes), the repacked weights and the lazy workspace."""
+    _SYM = ""
+
     def __init__(self, lat_h: int, lat_w: int, device="cuda:0"):
         self.lat_h, self.lat_w = lat_h, lat_w
         self.device = torch.device(device)
         self._lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self._lib.mmpl_taehv_create(lat_h, lat_w, C.byref(h)), "mmpl_taehv_create")
+        _lib.check(self._fn("create")(lat_h, lat_w, C.byref(h)), f"{self._SYM}_create")
         self._h = h
         self._weights: List[torch.Tensor] = []
         self._ws: Optional[torch.Tensor] = None
-        self.latents_done = 0                                        # latent frames decoded since clear_cache()
+
+    def _fn(self, name: str):
+        return getattr(self._lib, f"{self._SYM}_{name}")
 
     def __del__(self):
         try:
             if getattr(self, "_h", None):
-                self._lib.mmpl_taehv_destroy(self._h)
+                self._fn("destroy")(self._h)
                 self._h = None
         except Exception:
             pass
 
-    @staticmethod
-    def weight_names() -> List[str]:
+    @classmethod
+    def weight_names(cls) -> List[str]:
         lib = _lib.load()
-        return [lib.mmpl_taehv_weight_name(i).decode() for i in range(lib.mmpl_taehv_num_weights())]
+        name = getattr(lib, f"{cls._SYM}_weight_name")
+        return [name(i).decode() for i in range(getattr(lib, f"{cls._SYM}_num_weights")())]
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        names = self.weight_names()
+        missing = [n for n in names if n not in sd]
+        if missing:
+            raise KeyError(f"TAEHV state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}")
+        ws = [self._repack(n, sd[n]).contiguous().to(self.device) for n in names]
+        _lib.bind_weights(self._fn("bind_weights"), self._h, ws, f"{self._SYM}_bind_weights")
+        self._weights = ws
+
+    def clear_cache(self) -> None:
+        """Ends the streamed video: the next streamed call starts from zero memories."""
+        _lib.check(self._fn("reset")(self._h), f"{self._SYM}_reset")
+
+    def _workspace(self) -> torch.Tensor:
+        if self._ws is None:
+            self._ws = torch.empty(self._fn("workspace_bytes")(self._h), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+
+class TaehvEngine(_TaehvHalf):
+    _SYM = "mmpl_taehv"
+
+    def __init__(self, lat_h: int, lat_w: int, device="cuda:0"):
+        super().__init__(lat_h, lat_w, device)
+        self.latents_done = 0                                        # latent frames decoded since clear_cache()
 
     @staticmethod
     def _repack(name: str, t: torch.Tensor) -> torch.Tensor:
@@ -69,19 +102,11 @@ class TaehvEngine:
         return VaeEngine._frag_pack(t.reshape(cout, -1), cin_pad)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        sd = patch_tgrow_layers(sd)
-        names = self.weight_names()
-        missing = [n for n in names if n not in sd]
-        if missing:
-            raise KeyError(f"TAEHV state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}")
-        ws = [self._repack(n, sd[n]).contiguous().to(self.device) for n in names]
-        arr = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-        _lib.check(self._lib.mmpl_taehv_bind_weights(self._h, arr, len(ws)), "mmpl_taehv_bind_weights")
-        self._weights = ws
+        super().load_state_dict(patch_tgrow_layers(sd))
 
     def clear_cache(self) -> None:
         """Ends the streamed video: the next ``decode_stream`` call starts from zero memories."""
-        _lib.check(self._lib.mmpl_taehv_reset(self._h), "mmpl_taehv_reset")
+        super().clear_cache()
         self.latents_done = 0
 
     def decode_stream(self, latent: torch.Tensor, mean=None, std=None, out_format: str = "float") -> torch.Tensor:
@@ -94,9 +119,7 @@ class TaehvEngine:
         z = latent.to(device=self.device, dtype=torch.bfloat16).contiguous()
         F = z.shape[0]
         assert F >= 1 and z.shape[1:] == (16, self.lat_h, self.lat_w)
-        if self._ws is None:
-            self._ws = torch.empty(self._lib.mmpl_taehv_workspace_bytes(self._h), dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._workspace()
         H, W = 8 * self.lat_h, 8 * self.lat_w
         if out_format == "uint8":
             out = torch.empty(4 * F, H, W, 3, dtype=torch.uint8, device=self.device)
@@ -117,34 +140,15 @@ class TaehvEngine:
         return self.decode_stream(latent, out_format=out_format)
 
 
-class TaehvEncoderEngine:
+class TaehvEncoderEngine(_TaehvHalf):
     """The ENCODER half (``TAEHV.encode_video``; libmmpl_hip.so: mmpl_taehv_enc_* / mmpl_taehv_encode): pixels in [0, 1] -> the
     pipeline's normalised latents, 4 pixel frames per latent frame, causal in time with one frame of memory per MemBlock.  Takes
     the reference's state dict as it is (``encoder.N...`` keys; decoder keys are ignored)."""
+    _SYM = "mmpl_taehv_enc"
 
     def __init__(self, lat_h: int, lat_w: int, device="cuda:0"):
-        self.lat_h, self.lat_w = lat_h, lat_w
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._lib.mmpl_taehv_enc_create(lat_h, lat_w, C.byref(h)), "mmpl_taehv_enc_create")
-        self._h = h
-        self._weights: List[torch.Tensor] = []
-        self._ws: Optional[torch.Tensor] = None
+        super().__init__(lat_h, lat_w, device)
         self.frames_done = 0                                         # pixel frames encoded since clear_cache()
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.mmpl_taehv_enc_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    @staticmethod
-    def weight_names() -> List[str]:
-        lib = _lib.load()
-        return [lib.mmpl_taehv_enc_weight_name(i).decode() for i in range(lib.mmpl_taehv_enc_num_weights())]
 
     @staticmethod
     def _repack(name: str, t: torch.Tensor) -> torch.Tensor:
@@ -154,19 +158,9 @@ class TaehvEncoderEngine:
             return VaeEngine._frag_pack(torch.cat([t, t.new_zeros(t.shape[0], 5)], dim=1), 32)
         return TaehvEngine._repack(name, t)
 
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        names = self.weight_names()
-        missing = [n for n in names if n not in sd]
-        if missing:
-            raise KeyError(f"TAEHV state dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}")
-        ws = [self._repack(n, sd[n]).contiguous().to(self.device) for n in names]
-        arr = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-        _lib.check(self._lib.mmpl_taehv_enc_bind_weights(self._h, arr, len(ws)), "mmpl_taehv_enc_bind_weights")
-        self._weights = ws
-
     def clear_cache(self) -> None:
         """Ends the streamed video: the next ``encode_stream`` call starts from zero memories."""
-        _lib.check(self._lib.mmpl_taehv_enc_reset(self._h), "mmpl_taehv_enc_reset")
+        super().clear_cache()
         self.frames_done = 0
 
     def _check_px(self, px: torch.Tensor) -> bool:
@@ -186,9 +180,7 @@ class TaehvEncoderEngine:
         u8 = self._check_px(px)
         px = px.to(device=self.device, dtype=torch.uint8 if u8 else torch.float32).contiguous()
         T = px.shape[0]
-        if self._ws is None:
-            self._ws = torch.empty(self._lib.mmpl_taehv_enc_workspace_bytes(self._h), dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._workspace()
         z = torch.empty(T // 4, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=self.device)
         n_out = C.c_int(0)
         with torch.cuda.device(self.device):

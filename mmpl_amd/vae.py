@@ -124,8 +124,7 @@ class VaeEngine:
                 ws.append(self._frag_pack(w2d, (cin + 31) // 32 * 32).to(self.device))
                 continue
             ws.append(self._repack(name, sd[name]).contiguous().to(self.device))
-        arr = (C.c_void_p * n)(*[t.data_ptr() for t in ws])
-        _lib.check(self._lib.mmpl_vae_bind_weights(self._h, arr, n), "mmpl_vae_bind_weights")
+        _lib.bind_weights(self._lib.mmpl_vae_bind_weights, self._h, ws, "mmpl_vae_bind_weights")
         self._weights = ws
 
     def _workspace(self, mode: int) -> torch.Tensor:

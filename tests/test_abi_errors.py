@@ -75,6 +75,38 @@ def test_t5_encode_rejects_null_arguments_before_any_launch():
         lib.mmpl_t5_destroy(h)
 
 
+def test_failed_bind_leaves_t5_and_vae_handles_unbound():
+    """A refused mmpl_*_bind_weights touches nothing: the handle had no weights, so the encode / decode after it still says so (the
+    sequence tests/test_taehv_host.py runs for TAEHV).  The calls after the bind carry arguments the NEXT check refuses too, so a
+    handle that did count as bound launches nothing either."""
+    lib = _lib.load()
+    P = C.c_void_p(0x10000)
+    cfg = _lib.MmplT5Config(vocab=1000, dim=256, dim_attn=256, dim_ffn=512, num_heads=4, num_layers=2, num_buckets=32, text_len=64, eps=1e-6)
+    h = C.c_void_p()
+    assert lib.mmpl_t5_create(C.byref(cfg), C.byref(h)) == 0
+    try:
+        nw = lib.mmpl_t5_num_weights(C.byref(cfg))
+        assert "weights not bound" in _err(lib.mmpl_t5_encode(h, None, None, None, None, None, 0, None))
+        assert "wrong pointer count" in _err(lib.mmpl_t5_bind_weights(h, (C.c_void_p * 3)(1, 2, 3), 3))
+        assert "null weight pointer" in _err(lib.mmpl_t5_bind_weights(h, (C.c_void_p * nw)(*([0x1000] * (nw - 1) + [0])), nw))
+        assert "weights not bound" in _err(lib.mmpl_t5_encode(h, None, None, None, None, None, 0, None))
+        assert "wrong pointer count" in _err(lib.mmpl_t5_bind_weights(h, None, nw))
+    finally:
+        lib.mmpl_t5_destroy(h)
+    v = C.c_void_p()
+    assert lib.mmpl_vae_create(2, 2, C.byref(v)) == 0
+    try:
+        nw = lib.mmpl_vae_num_weights()
+        assert "weights not bound" in _err(lib.mmpl_vae_decode(v, P, 0, None, None, P, P, 0, None))
+        assert "wrong pointer count" in _err(lib.mmpl_vae_bind_weights(v, (C.c_void_p * 3)(1, 2, 3), 3))
+        assert "null weight pointer" in _err(lib.mmpl_vae_bind_weights(v, (C.c_void_p * nw)(*([0x1000] * (nw - 1) + [0])), nw))
+        assert "weights not bound" in _err(lib.mmpl_vae_decode(v, P, 0, None, None, P, P, 0, None))
+        assert "weights not bound" in _err(lib.mmpl_vae_encode(v, P, 0, None, None, P, P, 0, None))
+        assert "wrong pointer count" in _err(lib.mmpl_vae_bind_weights(v, None, nw))
+    finally:
+        lib.mmpl_vae_destroy(v)
+
+
 def test_kernel_entry_points_reject_bad_shapes():
     lib = _lib.load()
     # K must be a multiple of 64, leading dimensions of 8 elements: rejected before any launch

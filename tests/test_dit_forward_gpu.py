@@ -156,6 +156,32 @@ def test_forward_runtime_errors_raise():
     assert torch.isfinite(y.float()).all()
 
 
+def test_failed_bind_leaves_the_handle_unbound():
+    """A refused mmpl_dit_bind_weights touches nothing: the handle had no weights, so the forward after it still says so (the
+    sequence tests/test_taehv_host.py runs for TAEHV).  n_frames 0 here, so a forward that did get past that check is refused by
+    the next one and launches nothing."""
+    import ctypes as C
+    from mmpl_amd.dit import DitEngine
+    from mmpl_amd.synthetic import WAN_CONFIGS
+    eng = DitEngine(WAN_CONFIGS["tiny"], 16, 24, "cuda:0")
+    lib, h = eng._lib, eng._h
+    nw = lib.mmpl_dit_num_weights(C.byref(eng._c))
+
+    def err(rc):
+        assert rc != 0
+        return lib.mmpl_last_error().decode()
+
+    def forward():
+        return lib.mmpl_dit_forward(h, None, None, 0, None, None, None, 0, None, None, 15, None, None, 512, None, None, None, None, None, 0, None)
+
+    assert "weights not bound" in err(forward())
+    assert "wrong pointer count" in err(lib.mmpl_dit_bind_weights(h, (C.c_void_p * 3)(1, 2, 3), 3))
+    assert "null weight pointer" in err(lib.mmpl_dit_bind_weights(h, (C.c_void_p * nw)(*([0x1000] * (nw - 1) + [0])), nw))
+    assert "weights not bound" in err(forward())
+    assert "null argument" in err(lib.mmpl_dit_bind_weights(h, None, nw))
+    assert "null argument" in err(lib.mmpl_dit_bind_weights(None, (C.c_void_p * nw)(*([0x1000] * nw)), nw))
+
+
 def test_build_then_smoke_in_one_process():
     """__graft_entry__.build() followed by smoke() in ONE fresh process (the library is dlopen'ed before anything touched
     the device): regression test for the HIP-runtime load order (mmpl_amd/_lib.py imports torch before dlopen)."""
