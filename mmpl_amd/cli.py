@@ -199,6 +199,86 @@ def extend_refusal(args, fewstep: bool):
     return None
 
 
+def first_refusal(args, world: int, fewstep: bool):
+    """The first reason this command line cannot run, asked in ``main``'s order (None = it can).  ``main`` has put fewstep,
+    num_frame_per_block, kv_window and pixel_hw on ``args``."""
+    checks = (lambda: bidirectional_refusal(args, world), lambda: stream_refusal(args, fewstep), lambda: preview_refusal(args),
+              lambda: rolling_refusal(args, fewstep), lambda: solver_refusal(args, fewstep),
+              lambda: fewstep_refusal(args, world) if fewstep and not args.bidirectional else None,
+              lambda: extend_refusal(args, fewstep))
+    return next((why for why in (check() for check in checks) if why is not None), None)
+
+
+def _prompts(args):
+    if args.data_path:
+        from .utils.dataset import TextDataset
+        ds = TextDataset(args.data_path)
+        return [ds[i]["prompts"] for i in range(len(ds))]
+    return ["a cat running on the grass"]
+
+
+def _to_u8(video: torch.Tensor) -> torch.Tensor:
+    """[1, T, 3, H, W] in [0, 1] -> uint8 frames (Wan_fps_inference_1gpu.py:209-225 scales by 255 before write_video)"""
+    return (video * 255.0).clamp(0, 255).to(torch.uint8)
+
+
+def _save_clip(frames: torch.Tensor, args, idx: int, what: str = "") -> None:
+    """uint8 frames, [1, T, 3, H, W] or already the written layout [T, H, W, 3] on the host -> ``idx``-0.pt (torch.save) and the
+    video file next to it (Wan_fps_inference_1gpu.py:225)."""
+    out = frames[0].permute(0, 2, 3, 1).contiguous().cpu() if frames.dim() == 5 else frames
+    path = os.path.join(args.output_folder, f"{idx}-0.pt")
+    torch.save(out, path)
+    from .utils.video_io import write_video
+    vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)
+    print(f"[mmpl_amd.cli] {what}prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
+
+
+def _load_image(path: str, geo, dev) -> torch.Tensor:
+    """The image at the clip's pixel size, [3, H, W] bf16 in [-1, 1] on the device: Resize -> ToTensor -> Normalize(0.5, 0.5)
+    (I2V/Wan_fps_inference_1gpu.py:74-79, image2video.py:186-246)."""
+    import numpy as np
+    from PIL import Image
+    H, W = geo.pixel_hw
+    img = Image.open(path).convert("RGB").resize((W, H), Image.BILINEAR)
+    px = torch.from_numpy(np.asarray(img).copy()).permute(2, 0, 1).float() / 255.0
+    return ((px - 0.5) / 0.5).to(device=dev, dtype=torch.bfloat16)
+
+
+def _build_models(args, dev, geo, mcfg, make_generator, i2v_dir=None):
+    """(generator, text encoder, VAE, CLIP tower) of a run.  ``make_generator(model_config)`` builds the wrapper (model_config None:
+    from the checkpoint directory).  --synthetic: seeded weights, text embeddings and VAE; otherwise the encoder and the VAE are
+    None, i.e. the pipeline's own defaults: the reference checkpoints under ../wan_models (wan_wrapper.local_wan_path).
+    ``i2v_dir``: the Wan-I2V model type, whose CLIP ViT-H weights lie in that directory.  --checkpoint_path is loaded last."""
+    from .wan_wrapper import SyntheticTextEncoder, WanVAEWrapper
+    i2v, clip = i2v_dir is not None, None
+    if i2v:
+        from .i2v_clip import CLIPVisionTower
+        mcfg = dict(mcfg, model_type="i2v")
+        tiny_clip = args.synthetic and args.model in ("tiny", "small")      # tests: 3 blocks instead of ViT-H's 32
+        clip = CLIPVisionTower(num_layers=3 if tiny_clip else 32, device=dev)
+    gen = make_generator(mcfg if args.synthetic else None)
+    if i2v and gen.model_type != "i2v":
+        raise SystemExit("--i2v_model: the checkpoint directory does not hold a model_type 'i2v' config")
+    enc, vae = None, None
+    if args.synthetic:
+        if i2v:
+            from .synthetic import clip_visual_state_dict, dit_i2v_state_dict
+            gen.load_state_dict(dit_i2v_state_dict(mcfg, seed=1, device=dev))
+            clip.load_state_dict(clip_visual_state_dict(1280, 16, clip.num_layers, seed=3, device=dev))
+        else:
+            gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
+        enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
+        vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
+    elif i2v:
+        from .checkpoints import read_clip_visual
+        from .wan_wrapper import local_wan_path
+        clip.load_state_dict(read_clip_visual(f"{local_wan_path}/{i2v_dir}/models_clip_open-clip-xlm-roberta-large-vit-huge-14.pth"))
+    if args.checkpoint_path:
+        from .checkpoints import read_mmpl_checkpoint
+        gen.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
+    return gen, enc, vae, clip
+
+
 def build_preview_vae(args, dev, geo):
     """TAEHVWrapper for --preview_vae [PATH]: the checkpoint at PATH (default ../wan_models/taew2_1.pth), or seeded weights with
     --synthetic (both halves: the decoder, and the encoder --extend needs)."""
@@ -219,24 +299,17 @@ def build_fewstep_pipeline(config, args, dev, geo, mcfg):
     """WanDiffusionWrapper + CausalInferencePipeline (Wan_fps_inference_1gpu.py:61), then `independent_first_frame = False`
     as the entry script sets it (:73)."""
     from .pipeline import CausalInferencePipeline
-    from .wan_wrapper import SyntheticTextEncoder, WanDiffusionWrapper, WanVAEWrapper
+    from .wan_wrapper import WanDiffusionWrapper
     kw = dict(getattr(config, "model_kwargs", {}) or {})
     for name in ("local_attn_size", "sink_size"):                        # --local_attn_size / --sink_size override the config's
         if getattr(args, name, None) is not None:
             kw[name] = getattr(args, name)
     config.rolling_kv = bool(getattr(args, "rolling", False))
-    gen = WanDiffusionWrapper("Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B", **kw, is_causal=True,
-                              model_config=mcfg if args.synthetic else None, geometry=geo, device=dev)
-    enc, vae = None, None
-    if args.synthetic:
-        gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
-        enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
-        vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
+    gen, enc, vae, _ = _build_models(args, dev, geo, mcfg, lambda model_config: WanDiffusionWrapper(
+        "Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B", **kw, is_causal=True, model_config=model_config, geometry=geo,
+        device=dev))
     preview = build_preview_vae(args, dev, geo) if getattr(args, "preview_vae", None) is not None else None
     pipe = CausalInferencePipeline(config, dev, generator=gen, text_encoder=enc, vae=vae, preview_vae=preview)
-    if args.checkpoint_path:
-        from .checkpoints import read_mmpl_checkpoint
-        pipe.generator.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
     pipe.independent_first_frame = False
     return pipe
 
@@ -314,31 +387,12 @@ def main(argv=None):
     config = load_config(args.config_path)
     fewstep = is_fewstep(config)
     args.fewstep = fewstep
-    why = bidirectional_refusal(args, world)
-    if why is not None:
-        ap.error(why)
-    why = stream_refusal(args, fewstep)
-    if why is not None:
-        ap.error(why)
-    why = preview_refusal(args)
-    if why is not None:
-        ap.error(why)
-    why = rolling_refusal(args, fewstep)
-    if why is not None:
-        ap.error(why)
-    why = solver_refusal(args, fewstep)
-    if why is not None:
-        ap.error(why)
-    if fewstep and not args.bidirectional:
-        why = fewstep_refusal(args, world)
-        if why is not None:
-            ap.error(why)
     geo = Geometry(*args.latent_hw) if args.latent_hw else Geometry.named(args.resolution)
     las = args.local_attn_size if args.local_attn_size is not None else (getattr(config, "model_kwargs", None) or {}).get("local_attn_size", -1)
     args.num_frame_per_block = int(getattr(config, "num_frame_per_block", 1))
     args.kv_window = geo.frames_per_chunk if int(las) == -1 else int(las)
     args.pixel_hw = tuple(geo.pixel_hw)
-    why = extend_refusal(args, fewstep)
+    why = first_refusal(args, world, fewstep)
     if why is not None:
         ap.error(why)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -355,7 +409,7 @@ def main(argv=None):
     torch.set_grad_enabled(False)
 
     from .pipeline import CausalFPSInferencePipeline
-    from .wan_wrapper import SyntheticTextEncoder, WanFPSWrapper, WanVAEWrapper
+    from .wan_wrapper import WanFPSWrapper
     mcfg = WAN_CONFIGS[args.model]
     if args.bidirectional:
         return _main_bidirectional(config, args, dev, geo, mcfg)
@@ -363,47 +417,18 @@ def main(argv=None):
         return _main_fewstep(config, args, dev, geo, mcfg)
     config.sampling_steps = args.sampling_steps
     config.sample_solver = args.sample_solver
-    clip = None
-    if args.i2v_model:
-        if not (args.i2v and args.image):
-            ap.error("--i2v_model needs --i2v --image")
-        from .i2v_clip import CLIPVisionTower
-        mcfg = dict(mcfg, model_type="i2v")
-        tiny_clip = args.synthetic and args.model in ("tiny", "small")      # tests: 2 blocks instead of ViT-H's 32
-        clip = CLIPVisionTower(num_layers=3 if tiny_clip else 32, device=dev)
-    gen = WanFPSWrapper("Wan2.1-I2V-14B-720P" if args.i2v_model else "Wan2.1-T2V-14B", **config.model_kwargs, is_causal=True,
-                        model_config=mcfg if args.synthetic else None, geometry=geo, device=dev)
-    if args.i2v_model and gen.model_type != "i2v":
-        raise SystemExit("--i2v_model: the checkpoint directory does not hold a model_type 'i2v' config")
-    if args.synthetic:
-        if args.i2v_model:
-            from .synthetic import clip_visual_state_dict, dit_i2v_state_dict
-            gen.load_state_dict(dit_i2v_state_dict(mcfg, seed=1, device=dev))
-            clip.load_state_dict(clip_visual_state_dict(1280, 16, clip.num_layers, seed=3, device=dev))
-        else:
-            gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
-        enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
-        vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
-    else:
-        enc, vae = None, None       # reference checkpoints under ../wan_models (wan_wrapper.local_wan_path)
-        if args.i2v_model:
-            from .checkpoints import read_clip_visual
-            from .wan_wrapper import local_wan_path
-            clip.load_state_dict(read_clip_visual(f"{local_wan_path}/Wan2.1-I2V-14B-720P/models_clip_open-clip-xlm-roberta-large-vit-huge-14.pth"))
+    if args.i2v_model and not (args.i2v and args.image):
+        ap.error("--i2v_model needs --i2v --image")
+    i2v_dir = "Wan2.1-I2V-14B-720P" if args.i2v_model else None
+    gen, enc, vae, clip = _build_models(args, dev, geo, mcfg, lambda model_config: WanFPSWrapper(
+        i2v_dir or "Wan2.1-T2V-14B", **config.model_kwargs, is_causal=True, model_config=model_config, geometry=geo, device=dev), i2v_dir)
     mode = "i2v" if args.i2v else "t2v"
     pipe = CausalFPSInferencePipeline(config, dev, generator=gen, text_encoder=enc, vae=vae, device_cond=dev, device_uncond=dev, save=None,
                                       mode=mode, geometry=geo)
     image_latent, first_px = None, None
-    if args.i2v:
-        # I2V/Wan_fps_inference_1gpu.py:74-79,100-104: Resize -> ToTensor -> Normalize(0.5, 0.5) -> vae.encode_to_latent
-        import numpy as np
-        from PIL import Image
-        H, W = geo.pixel_hw
-        img = Image.open(args.image).convert("RGB").resize((W, H), Image.BILINEAR)
-        px = torch.from_numpy(np.asarray(img).copy()).permute(2, 0, 1).float() / 255.0
-        px = ((px - 0.5) / 0.5).unsqueeze(0).unsqueeze(2).to(device=dev, dtype=torch.bfloat16)      # [1, 3, 1, H, W]
-        image_latent = pipe.vae.encode_to_latent(px).to(torch.bfloat16)                                # [1, 1, 16, h, w]
-        first_px = px[0, :, 0]
+    if args.i2v:                                 # I2V/Wan_fps_inference_1gpu.py:100-104: the image -> vae.encode_to_latent
+        first_px = _load_image(args.image, geo, dev)
+        image_latent = pipe.vae.encode_to_latent(first_px[None, :, None]).to(torch.bfloat16)         # [1, 3, 1, H, W] -> [1, 1, 16, h, w]
 
     def image_cond(frame):
         """the Wan-I2V model type's conditioning for a chunk whose first pixel frame is `frame` ([3, H, W] in [-1, 1])"""
@@ -416,24 +441,10 @@ def main(argv=None):
                     "y": torch.empty(20, args.num_output_frames, geo.lat_h, geo.lat_w, device=dev, dtype=torch.bfloat16)}
         from .i2v_condition import build_image_condition
         return build_image_condition(pipe.vae, clip, frame, args.num_output_frames)
-    if args.checkpoint_path:
-        from .checkpoints import read_mmpl_checkpoint
-        pipe.generator_cond.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
 
-    if args.data_path:
-        from .utils.dataset import TextDataset
-        ds = TextDataset(args.data_path)
-        prompts = [ds[i]["prompts"] for i in range(len(ds))]
-    else:
-        prompts = ["a cat running on the grass"]
     os.makedirs(args.output_folder, exist_ok=True)
-
-    def to_u8(video):
-        """[1, T, 3, H, W] in [0, 1] -> uint8 frames (Wan_fps_inference_1gpu.py:209-225 scales by 255 before write_video)"""
-        return (video * 255.0).clamp(0, 255).to(torch.uint8)
-
     shape = [1, args.num_output_frames, 16, geo.lat_h, geo.lat_w]
-    for idx, prompt in enumerate(prompts):
+    for idx, prompt in enumerate(_prompts(args)):
         # noise for every chunk is drawn in order from one seeded generator on every rank (the reference draws it on the
         # main thread in chunk order, ..._parallel_4gpu_20s.py:170,232-251)
         g = torch.Generator(device="cpu").manual_seed(args.seed)
@@ -445,7 +456,7 @@ def main(argv=None):
                                           image_condition=image_cond(frame0))
                 initial = rolling_initial_latent(pipe.vae, video)
                 frame0 = video[0, -5].to(torch.bfloat16) * 2.0 - 1.0       # the next chunk starts at this chunk's 5th-last frame
-                videos.append(to_u8(video))
+                videos.append(_to_u8(video))
         else:
             pair, heads, lay = (CfgPair.build(world, dev, True) if args.cfg_split else (None, None, None))
             pipe.cfg_pair = pair
@@ -467,30 +478,16 @@ def main(argv=None):
                     initial = image_latent
                 video, _ = pipe.inference(noises[c].to(dev), [prompt], initial_latent=initial, return_latents=True,
                                           image_condition=image_cond(frame_of[0] if c == 0 else frame_of.get("next")))
-                return to_u8(video)         # quantised on the owner: the device all-gather moves 224 MB per 720p chunk, not 896
+                return _to_u8(video)        # quantised on the owner: the device all-gather moves 224 MB per 720p chunk, not 896
 
             videos = run_chunk_wavefront(make_chunk, args.duration, ho, to_initial,
                                          pair=pair, lane=lay["lane_of"][rank] if lay else rank, n_lanes=world // 2 if lay else world,
                                          initial_like=torch.empty([1, 2, 16, geo.lat_h, geo.lat_w], device=dev, dtype=torch.bfloat16))
         if videos is not None:
-            full = stitch_chunks(videos)                                     # [1, T, 3, H, W] uint8
-            out = full[0].permute(0, 2, 3, 1).contiguous().cpu()
-            path = os.path.join(args.output_folder, f"{idx}-0.pt")
-            torch.save(out, path)
-            from .utils.video_io import write_video
-            vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)    # Wan_fps_inference_1gpu.py:225
-            print(f"[mmpl_amd.cli] prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
+            _save_clip(stitch_chunks(videos), args, idx)                     # [1, T, 3, H, W] uint8
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-
-
-def _prompts(args):
-    if args.data_path:
-        from .utils.dataset import TextDataset
-        ds = TextDataset(args.data_path)
-        return [ds[i]["prompts"] for i in range(len(ds))]
-    return ["a cat running on the grass"]
 
 
 def _main_fewstep(config, args, dev, geo, mcfg):
@@ -527,13 +524,8 @@ def _main_fewstep(config, args, dev, geo, mcfg):
                 parts.append(frames)
             out = torch.cat(parts)                                                                             # [T, H, W, 3]
         else:
-            video = pipe.inference(noise.to(dev), [prompt], return_latents=False)
-            out = (video * 255.0).clamp(0, 255).to(torch.uint8)[0].permute(0, 2, 3, 1).contiguous().cpu()     # [T, H, W, 3]
-        path = os.path.join(args.output_folder, f"{idx}-0.pt")
-        torch.save(out, path)
-        from .utils.video_io import write_video
-        vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)
-        print(f"[mmpl_amd.cli] few-step prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
+            out = _to_u8(pipe.inference(noise.to(dev), [prompt], return_latents=False))
+        _save_clip(out, args, idx, "few-step ")
 
 
 def i2v_model_name(args) -> str:
@@ -544,34 +536,14 @@ def i2v_model_name(args) -> str:
 def build_bidirectional_pipeline(config, args, dev, geo, mcfg):
     """WanDiffusionWrapper(is_causal=False) + the bidirectional pipeline `pipeline_class` picks for `config`; with --i2v_model the
     generator is the Wan-I2V model type and the pipeline gets `clip`, the CLIP ViT-H tower its image conditioning needs."""
-    from .wan_wrapper import SyntheticTextEncoder, WanDiffusionWrapper, WanVAEWrapper
-    i2v = bool(getattr(args, "i2v_model", False))
+    from .wan_wrapper import WanDiffusionWrapper
+    i2v_dir = i2v_model_name(args) if getattr(args, "i2v_model", False) else None
     kw = {k: v for k, v in dict(getattr(config, "model_kwargs", {}) or {}).items() if k in ("model_name", "timestep_shift")}
-    if i2v:
-        kw["model_name"] = i2v_model_name(args)
-        mcfg = dict(mcfg, model_type="i2v")
+    if i2v_dir is not None:
+        kw["model_name"] = i2v_dir
     kw.setdefault("model_name", "Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B")
-    gen = WanDiffusionWrapper(**kw, is_causal=False, model_config=mcfg if args.synthetic else None, geometry=geo, device=dev)
-    if i2v and gen.model_type != "i2v":
-        raise SystemExit("--i2v_model: the checkpoint directory does not hold a model_type 'i2v' config")
-    enc, vae, clip = None, None, None
-    if i2v:
-        from .i2v_clip import CLIPVisionTower
-        tiny_clip = args.synthetic and args.model in ("tiny", "small")      # tests: 3 blocks instead of ViT-H's 32
-        clip = CLIPVisionTower(num_layers=3 if tiny_clip else 32, device=dev)
-    if args.synthetic:
-        if i2v:
-            from .synthetic import clip_visual_state_dict, dit_i2v_state_dict
-            gen.load_state_dict(dit_i2v_state_dict(mcfg, seed=1, device=dev))
-            clip.load_state_dict(clip_visual_state_dict(1280, 16, clip.num_layers, seed=3, device=dev))
-        else:
-            gen.load_state_dict(dit_state_dict(mcfg, seed=1, device=dev))
-        enc = SyntheticTextEncoder(mcfg.get("text_dim", 4096), dev)
-        vae = WanVAEWrapper(geometry=geo, device=dev, state_dict=vae_state_dict(seed=2))
-    elif i2v:
-        from .checkpoints import read_clip_visual
-        from .wan_wrapper import local_wan_path
-        clip.load_state_dict(read_clip_visual(f"{local_wan_path}/{kw['model_name']}/models_clip_open-clip-xlm-roberta-large-vit-huge-14.pth"))
+    gen, enc, vae, clip = _build_models(args, dev, geo, mcfg, lambda model_config: WanDiffusionWrapper(
+        **kw, is_causal=False, model_config=model_config, geometry=geo, device=dev), i2v_dir)
     pipe = pipeline_class(config, bidirectional=True)(config, dev, generator=gen, text_encoder=enc, vae=vae)
     pipe.clip = clip
     if not is_fewstep(config):
@@ -579,9 +551,6 @@ def build_bidirectional_pipeline(config, args, dev, geo, mcfg):
         pipe.sample_solver = args.sample_solver
         if getattr(args, "sample_shift", None) is not None:
             pipe.shift = float(args.sample_shift)
-    if args.checkpoint_path:
-        from .checkpoints import read_mmpl_checkpoint
-        pipe.generator.load_state_dict(read_mmpl_checkpoint(args.checkpoint_path, use_ema=args.use_ema))
     return pipe
 
 
@@ -593,25 +562,13 @@ def _main_bidirectional(config, args, dev, geo, mcfg):
     extra = {}
     if args.i2v_model:
         # image2video.py:186-246: the image at the clip's pixel size in [-1, 1] -> CLIP tokens + the conditioning video y
-        import numpy as np
-        from PIL import Image
         from .i2v_condition import build_image_condition
-        H, W = geo.pixel_hw
-        img = Image.open(args.image).convert("RGB").resize((W, H), Image.BILINEAR)
-        px = torch.from_numpy(np.asarray(img).copy()).permute(2, 0, 1).float() / 255.0
-        px = ((px - 0.5) / 0.5).to(device=dev, dtype=torch.bfloat16)                                   # [3, H, W]
-        extra["image_condition"] = build_image_condition(pipe.vae, pipe.clip, px, args.num_output_frames)
+        extra["image_condition"] = build_image_condition(pipe.vae, pipe.clip, _load_image(args.image, geo, dev), args.num_output_frames)
     for idx, prompt in enumerate(_prompts(args)):
         g = torch.Generator(device="cpu").manual_seed(args.seed)
         noise = torch.randn(shape, generator=g).to(torch.bfloat16)
         torch.manual_seed(args.seed)                         # the few-step re-noise draws: the device generator
-        video = pipe.inference(noise.to(dev), [prompt], **extra)
-        out = (video * 255.0).clamp(0, 255).to(torch.uint8)[0].permute(0, 2, 3, 1).contiguous().cpu()         # [T, H, W, 3]
-        path = os.path.join(args.output_folder, f"{idx}-0.pt")
-        torch.save(out, path)
-        from .utils.video_io import write_video
-        vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)
-        print(f"[mmpl_amd.cli] bidirectional prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
+        _save_clip(_to_u8(pipe.inference(noise.to(dev), [prompt], **extra)), args, idx, "bidirectional ")
 
 
 if __name__ == "__main__":

@@ -300,15 +300,9 @@ class DitEngine:
         assert t.dtype == torch.float32 and t.numel() == nF and t.is_cuda
         if self.model_type == "i2v" and self._img_kv is None:
             raise RuntimeError("DitEngine: an i2v model needs set_image_kv(*precompute_image_context(clip_fea)) before forward")
-        for sh in (share_out, share_in):
-            assert sh is None or (sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() >= nF * self.S * self.dim and sh.device == x.device)
-        if attn_history is not None:
-            need = self._lib.mmpl_dit_attn_history_bytes(self._h, nF)
-            assert attn_history.dtype == torch.uint8 and attn_history.is_contiguous() and attn_history.numel() >= need and attn_history.device == x.device
         if frame_base is not None:
             assert frame_base.dtype == torch.int32 and frame_base.numel() == 1 and frame_base.device == x.device, (frame_base.dtype, tuple(frame_base.shape))
-        if out is None:
-            out = torch.empty(nF, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=x.device)
+        out = self._checked_out(x, share_out, share_in, attn_history, out)
         ws = self.workspace(nF) if workspace is None else workspace
         n_slots = k_cache.shape[1] // self.S
         ia = lambda v: (C.c_int * len(v))(*[int(i) for i in v])
@@ -316,10 +310,21 @@ class DitEngine:
             _lib.check(self._lib.mmpl_dit_forward_at(
                 self._h, _lib.ptr(x), _lib.ptr(t), nF, ia(frame_ids), ia(write_slots), ia(visible_slots), len(visible_slots),
                 _lib.ptr(k_cache), _lib.ptr(v_cache), n_slots, _lib.ptr(cross_k), _lib.ptr(cross_v),
-                self.text_len if cross_rows is None else int(cross_rows),
-                None if share_out is None else _lib.ptr(share_out), None if share_in is None else _lib.ptr(share_in),
-                None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base),
-                _lib.stream_ptr()), "mmpl_dit_forward")
+                self.text_len if cross_rows is None else int(cross_rows), _lib.ptr(share_out), _lib.ptr(share_in),
+                _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base), _lib.stream_ptr()), "mmpl_dit_forward")
+        return out
+
+    def _checked_out(self, x: torch.Tensor, share_out, share_in, attn_history, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Both forwards' checks of the optional tensors (share buffers, attention history) against x's frame count and device;
+        returns `out`, allocated when None."""
+        nF = x.shape[0]
+        for sh in (share_out, share_in):
+            assert sh is None or (sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() >= nF * self.S * self.dim and sh.device == x.device)
+        if attn_history is not None:
+            need = self._lib.mmpl_dit_attn_history_bytes(self._h, nF)
+            assert attn_history.dtype == torch.uint8 and attn_history.is_contiguous() and attn_history.numel() >= need and attn_history.device == x.device
+        if out is None:
+            out = torch.empty(nF, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=x.device)
         return out
 
     # ------------------------------------------------------------------ whole-clip (bidirectional) forward
@@ -358,18 +363,11 @@ class DitEngine:
         if i2v:
             assert y.is_contiguous() and y.dtype == torch.bfloat16 and y.shape == (nF, self.in_dim - 16, self.lat_h, self.lat_w) and y.device == x.device
         assert t.dtype == torch.float32 and t.numel() == 1 and t.device == x.device
-        for sh in (share_out, share_in):
-            assert sh is None or (sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() >= nF * self.S * self.dim and sh.device == x.device)
-        if attn_history is not None:
-            need = self._lib.mmpl_dit_attn_history_bytes(self._h, nF)
-            assert attn_history.dtype == torch.uint8 and attn_history.is_contiguous() and attn_history.numel() >= need and attn_history.device == x.device
         ws = self.full_workspace(nF) if workspace is None else workspace
-        if out is None:
-            out = torch.empty(nF, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=x.device)
+        out = self._checked_out(x, share_out, share_in, attn_history, out)
         assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.shape == (nF, 16, self.lat_h, self.lat_w)
-        tail = (nF, _lib.ptr(cross_k), _lib.ptr(cross_v), self.text_len if cross_rows is None else int(cross_rows),
-                None if share_out is None else _lib.ptr(share_out), None if share_in is None else _lib.ptr(share_in),
-                None if attn_history is None else _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel())
+        tail = (nF, _lib.ptr(cross_k), _lib.ptr(cross_v), self.text_len if cross_rows is None else int(cross_rows), _lib.ptr(share_out),
+                _lib.ptr(share_in), _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel())
         with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
             if i2v:
                 _lib.check(self._lib.mmpl_dit_forward_full_i2v(self._h, _lib.ptr(x), _lib.ptr(y), _lib.ptr(t), *tail, _lib.stream_ptr()),
@@ -388,7 +386,11 @@ class DitEngine:
         layer.  `x`, `t`, `out` and the caches are captured BY ADDRESS: update their contents in place between replays
         (that is what the denoise loop does: latents and the timestep change, the shapes never do).
         `pre`: launches recorded in front of the forward (the i2v model type refreshes the latent channels of its 36-channel
-        input buffer there)."""
+        input buffer there).
+        The first capture of a stage shape on this engine runs the forward once eagerly, ahead of the capture (see below), on the
+        caller's own buffers: it writes `out` and the caches' write slots, and it runs with the caller's `attn_history`, so it
+        ADVANCES that history by one forward before any replay does.  A caller whose bits must not depend on whether the shape was
+        warm zeroes the history after capture() (the pipeline does, at every stage boundary)."""
         self.workspace(x.shape[0])                      # allocate outside the capture
         if x.shape[0] not in self._warm:                # one eager call per (engine, stage shape): the kernels a shape selects (pipelined
             # LayerNorm from 16 384 rows, the v8 GEMM variants, attn_cross_kernel<NT>, the split-KV tail) set their dynamic-LDS

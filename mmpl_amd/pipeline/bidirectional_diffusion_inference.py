@@ -32,22 +32,18 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..scheduler import (FlowDPMSolverMultistepScheduler, FlowUniPCMultistepScheduler, get_sampling_sigmas, retrieve_timesteps)
-from ..wan_wrapper import WanDiffusionWrapper, WanTextEncoder, WanVAEWrapper
+from ._common import (GeneratorPipeline, cfg_concurrent, cfg_step, cfg_step_buffers, decode_video, eager_then_capture,
+                      make_sample_scheduler)
 
 
-class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
+class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
     def __init__(self, args, device, generator=None, text_encoder=None, vae=None):
         super().__init__()
-        self.device = torch.device(device)
-        self.generator = WanDiffusionWrapper(**getattr(args, "model_kwargs", {}), is_causal=False,
-                                             device=device) if generator is None else generator
+        self._set_generator(args, device, generator, is_causal=False)
         if getattr(self.generator, "is_causal", False):
             raise ValueError("BidirectionalDiffusionInferencePipeline needs WanDiffusionWrapper(is_causal=False)")
         self.i2v = getattr(self.generator, "model_type", "t2v") == "i2v"
-        self.geometry = self.generator.geometry
-        self.text_encoder = WanTextEncoder(device=device) if text_encoder is None else text_encoder
-        self.vae = WanVAEWrapper(geometry=self.geometry, device=device) if vae is None else vae
+        self._set_codecs(text_encoder, vae, device)
 
         self.num_train_timesteps = args.num_train_timestep
         self.sampling_steps = 50
@@ -61,42 +57,24 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
         self.share_block0 = True          # sequential branches: the uncond forward takes block 0's self-attention from the cond one
         self.graph_captures = 0           # hipGraphs constructed so far (tests: none after the first call)
         self._steps: Dict[tuple, dict] = {}     # (frames, solver, steps, guidance, concurrent, share) -> static buffers, scheduler, graph
+        self._stores = (self._steps,)
         self._side_stream = None
         self.crossattn_cache_pos = None
         self.crossattn_cache_neg = None
 
-    def to(self, *args, **kwargs):
-        return self
-
-    def release_graphs(self) -> None:
-        """Drop the captured step graphs (and the static buffers they read)."""
-        torch.cuda.synchronize(self.device)
-        self._steps.clear()
-
     # ------------------------------------------------------------------------------------------------------------
     def _initialize_sample_scheduler(self, noise):
-        """bidirectional_diffusion_inference.py:89-110 on the device-facing schedulers (mmpl_amd/scheduler.py)."""
-        if self.sample_solver == 'unipc':
-            s = FlowUniPCMultistepScheduler(num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
-            s.set_timesteps(self.sampling_steps, device=noise.device, shift=self.shift)
-            self.timesteps = s.timesteps
-        elif self.sample_solver == 'dpm++':
-            s = FlowDPMSolverMultistepScheduler(num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
-            self.timesteps, _ = retrieve_timesteps(s, device=noise.device, sigmas=get_sampling_sigmas(self.sampling_steps, self.shift))
-        else:
-            raise NotImplementedError("Unsupported solver.")
+        """bidirectional_diffusion_inference.py:89-110: the solver `sample_solver` names, `self.timesteps` set to its schedule."""
+        s, self.timesteps = make_sample_scheduler(self.sample_solver, self.num_train_timesteps, self.sampling_steps, self.shift, noise.device)
         return s
 
     def _step_state(self, noise: torch.Tensor) -> dict:
         """Static buffers, the scheduler with its device step table and (later) the graph of one step shape."""
         F = noise.shape[1]
         engine, dev = self.generator.engine, self.device
-        concurrent = self.concurrent_cfg
-        if concurrent is None:
-            from ..stage_plan import concurrent_cfg_pays
-            concurrent = concurrent_cfg_pays(F * engine.S, engine.dim)
-        share = bool(self.share_block0 and not concurrent)
-        key = (F, self.sample_solver, int(self.sampling_steps), float(self.args.guidance_scale), bool(concurrent), share)
+        concurrent = cfg_concurrent(self, engine, F)
+        key = (F, self.sample_solver, int(self.sampling_steps), float(self.args.guidance_scale), concurrent,
+               bool(self.share_block0 and not concurrent))
         st = self._steps.get(key)
         if st is None:
             g = self.geometry
@@ -107,35 +85,21 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
             sched._ensure_state(latents)
             st = dict(latents=latents, flow=torch.empty((2,) + shape, dtype=torch.bfloat16, device=dev),
                       t=torch.empty(1, dtype=torch.float32, device=dev), sched=sched, n=len(sched.timesteps), graph=None,
-                      timesteps=self.timesteps,
-                      concurrent=bool(concurrent), share=engine.shared_block0_buffer(F) if share else None, ws2=None,
+                      timesteps=self.timesteps, concurrent=concurrent,
                       # i2v: the conditioning video, frame-major, read by both forwards of every step and never written by them
                       y=torch.empty((F, engine.in_dim - 16, g.lat_h, g.lat_w), dtype=torch.bfloat16, device=dev) if self.i2v else None)
             engine.full_workspace(F)                                      # allocations and the stream: outside any capture
-            if concurrent:
-                st["ws2"] = engine.full_workspace(F, second=True)
-                if self._side_stream is None:
-                    self._side_stream = torch.cuda.Stream(device=dev)
+            st["share"], st["ws2"] = cfg_step_buffers(self, engine, F, concurrent, lambda n: engine.full_workspace(n, second=True), dev)
             self._steps[key] = st
         return st
 
     def _step(self, st: dict) -> None:
         """One denoise step's launches (bidirectional_diffusion_inference.py:62-76): eager, or recorded into the step graph."""
-        gen, pos, neg = self.generator, self.crossattn_cache_pos, self.crossattn_cache_neg
-        x, t, flow = st["latents"], st["t"], st["flow"]
+        caches = (self.crossattn_cache_pos, self.crossattn_cache_neg)
         kw = {} if st["y"] is None else {"y": st["y"]}                    # i2v: both branches see the image (image2video.py arg_null)
-        if st["concurrent"]:
-            main, side = torch.cuda.current_stream(self.device), self._side_stream
-            side.wait_stream(main)                                        # fork
-            gen.flow_full(x, t, pos, out=flow[0], **kw)
-            with torch.cuda.stream(side):
-                gen.flow_full(x, t, neg, out=flow[1], workspace=st["ws2"], **kw)
-            main.wait_stream(side)                                        # join: the CFG / solver update needs both
-        else:
-            gen.flow_full(x, t, pos, out=flow[0], share_out=st["share"], **kw)
-            gen.flow_full(x, t, neg, out=flow[1], share_in=st["share"], **kw)
-        # flow = uncond + g (cond - uncond); latents = scheduler.step(flow): one fused kernel, scalars and next t from device tables
-        st["sched"].step_cfg_table(flow[0], flow[1], x, t)
+        cfg_step(lambda bi, out, **k: self.generator.flow_full(st["latents"], st["t"], caches[bi], out=out, **k, **kw),
+                 st["sched"], st["flow"], st["latents"], st["t"], self.device, self._side_stream if st["concurrent"] else None,
+                 st["share"], st["ws2"])
 
     def inference(self, noise: torch.Tensor, text_prompts: List[str], return_latents=False,
                   image_condition: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
@@ -157,9 +121,8 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
             if self.crossattn_cache_pos is None:
                 self.crossattn_cache_pos = self.generator.new_crossattn_cache()
                 self.crossattn_cache_neg = self.generator.new_crossattn_cache()
-            for cache, d in ((self.crossattn_cache_pos, conditional_dict), (self.crossattn_cache_neg, unconditional_dict)):
-                pe = d["prompt_embeds"]
-                cache.fill(pe[0] if pe.dim() == 3 else pe)
+            self.crossattn_cache_pos.fill(conditional_dict["prompt_embeds"])
+            self.crossattn_cache_neg.fill(unconditional_dict["prompt_embeds"])
 
             st = self._step_state(noise)
             self.timesteps = st["timesteps"]
@@ -175,24 +138,16 @@ class BidirectionalDiffusionInferencePipeline(torch.nn.Module):
             if st["graph"] is not None:
                 for _ in range(n):
                     st["graph"].replay()
-            else:
-                self._step(st)                                            # first use: step 1 eagerly (the real work) ...
-                if self.use_graphs:                                       # ... then the same launches into the step's graph
-                    torch.cuda.synchronize(dev)
-                    g = torch.cuda.CUDAGraph()
-                    self.graph_captures += 1
-                    with torch.cuda.graph(g):
-                        self._step(st)
-                    st["graph"] = g
-                    for _ in range(n - 1):
+            else:                                                         # first use: step 1 eagerly, then into the step's graph
+                g = st["graph"] = eager_then_capture(self, lambda: self._step(st))
+                for _ in range(n - 1):
+                    if g is not None:
                         g.replay()
-                else:
-                    for _ in range(n - 1):
+                    else:
                         self._step(st)
 
             latents = st["latents"].unsqueeze(0).clone()
-            video = self.vae.decode_to_pixel(latents)
-            video = (video * 0.5 + 0.5).clamp(0, 1)
+            video = decode_video(self.vae, latents)
         if return_latents:
             return video, latents.to(noise.dtype)
         return video

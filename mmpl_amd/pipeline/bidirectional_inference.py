@@ -18,23 +18,19 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..wan_wrapper import WanDiffusionWrapper, WanTextEncoder, WanVAEWrapper
+from ._common import GeneratorPipeline, decode_video, eager_then_capture, fewstep_scalars, fill_bank
 
 
-class BidirectionalInferencePipeline(torch.nn.Module):
+class BidirectionalInferencePipeline(GeneratorPipeline):
     def __init__(self, args, device, generator=None, text_encoder=None, vae=None):
         super().__init__()
-        self.device = torch.device(device)
-        self.generator = WanDiffusionWrapper(**getattr(args, "model_kwargs", {}), is_causal=False,
-                                             device=device) if generator is None else generator
+        self._set_generator(args, device, generator, is_causal=False)
         if getattr(self.generator, "is_causal", False):
             raise ValueError("BidirectionalInferencePipeline needs WanDiffusionWrapper(is_causal=False)")
         if getattr(self.generator, "model_type", "t2v") != "t2v":
             raise ValueError("BidirectionalInferencePipeline is text-to-video only (no few-step i2v checkpoint exists); sample a "
                              "model_type 'i2v' generator with BidirectionalDiffusionInferencePipeline(image_condition=...)")
-        self.geometry = self.generator.geometry
-        self.text_encoder = WanTextEncoder(device=device) if text_encoder is None else text_encoder
-        self.vae = WanVAEWrapper(geometry=self.geometry, device=device) if vae is None else vae
+        self._set_codecs(text_encoder, vae, device)
 
         self.scheduler = self.generator.get_scheduler()
         self.denoising_step_list = torch.tensor(args.denoising_step_list, dtype=torch.long)
@@ -50,24 +46,13 @@ class BidirectionalInferencePipeline(torch.nn.Module):
         self.noise_generator: Optional[torch.Generator] = None       # None = the device's default generator (torch.randn_like)
         self.graph_captures = 0           # hipGraphs constructed so far (tests: none after the first call)
         self._calls: Dict[tuple, dict] = {}     # (frames, step list) -> static buffers and the graph
+        self._stores = (self._calls,)
         self.crossattn_cache = None
 
-    def to(self, *args, **kwargs):
-        return self
-
-    def release_graphs(self) -> None:
-        """Drop the captured graphs (and the static buffers they read)."""
-        torch.cuda.synchronize(self.device)
-        self._calls.clear()
-
     def _step_scalars(self):
-        """(engine timestep, sigma of the x0 conversion, sigma of add_noise to the NEXT listed step) per forward, from the step
-        list's own dtype the way the reference's tensors carry it (float32 when warped, int64 otherwise)."""
-        steps = list(self.denoising_step_list)
-        t_eng = [float(t) for t in steps[:-1]]
-        sig_x0 = [self.generator.sigma_x0(t) for t in steps[:-1]]
-        sig_next = [self.generator.sigma_add_noise(t) for t in steps[1:]]
-        return t_eng, sig_x0, sig_next
+        """(engine timestep, sigma of the x0 conversion, sigma of add_noise to the NEXT listed step) per forward: one at every
+        listed step but the last."""
+        return fewstep_scalars(self.generator, self.denoising_step_list, len(self.denoising_step_list) - 1)
 
     def _run(self, st: dict, scalars) -> None:
         """The call's launches (bidirectional_inference.py:52-67): eager, or recorded into the call's hipGraph."""
@@ -90,8 +75,7 @@ class BidirectionalInferencePipeline(torch.nn.Module):
             conditional_dict = self.text_encoder(text_prompts=text_prompts)
             if self.crossattn_cache is None:
                 self.crossattn_cache = self.generator.new_crossattn_cache()
-            pe = conditional_dict["prompt_embeds"]
-            self.crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
+            self.crossattn_cache.fill(conditional_dict["prompt_embeds"])
 
             scalars = self._step_scalars()
             n_fwd = len(scalars[0])
@@ -106,27 +90,14 @@ class BidirectionalInferencePipeline(torch.nn.Module):
                                              t=torch.empty(1, dtype=torch.float32, device=dev), graph=None)
                 self.generator.engine.full_workspace(num_frames)          # allocated outside the capture
             st["x"].copy_(noise[0].to(device=dev, dtype=torch.bfloat16))
-            draws = iter(self.renoise_override) if self.renoise_override is not None else None
-            for i in range(n_fwd):                                        # the reference's torch.randn_like draws, in order
-                if draws is not None:
-                    st["bank"][i].copy_(next(draws).reshape(st["bank"][i].shape))
-                else:
-                    st["bank"][i].normal_(0.0, 1.0, generator=self.noise_generator)
+            fill_bank(st["bank"], n_fwd, iter(self.renoise_override) if self.renoise_override is not None else None, self.noise_generator)
             if st["graph"] is not None:
                 st["graph"].replay()
-            else:
-                self._run(st, scalars)                                    # first use: the real work, eagerly ...
-                if self.use_graphs:                                       # ... then the same launches into the call's graph
-                    torch.cuda.synchronize(dev)
-                    g = torch.cuda.CUDAGraph()
-                    self.graph_captures += 1
-                    with torch.cuda.graph(g):
-                        self._run(st, scalars)
-                    st["graph"] = g
+            else:                                                         # first use: eagerly, then into the call's graph
+                st["graph"] = eager_then_capture(self, lambda: self._run(st, scalars))
 
             latents = st["x0"].unsqueeze(0).clone()
-            video = self.vae.decode_to_pixel(latents)
-            video = (video * 0.5 + 0.5).clamp(0, 1)
+            video = decode_video(self.vae, latents)
         if return_latents:
             return video, latents.to(noise.dtype)
         return video

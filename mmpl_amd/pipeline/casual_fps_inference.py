@@ -25,13 +25,12 @@ from typing import Callable, List, Optional
 import torch
 
 from ..geometry import Geometry
-from ..scheduler import (FlowDPMSolverMultistepScheduler, FlowUniPCMultistepScheduler, get_sampling_sigmas,
-                         retrieve_timesteps)
 from ..stage_plan import StagePlan
-from ..wan_wrapper import WanFPSWrapper, WanTextEncoder, WanVAEWrapper
+from ..wan_wrapper import WanFPSWrapper
+from ._common import PipelineBase, cfg_concurrent, cfg_step, cfg_step_buffers, decode_video, make_sample_scheduler
 
 
-class CausalFPSInferencePipeline(torch.nn.Module):
+class CausalFPSInferencePipeline(PipelineBase):
     def __init__(self, args, device, generator=None, text_encoder=None, vae=None, device_cond="cuda:0",
                  device_uncond="cuda:0", save="latents_chunk1.pt", mode: str = "t2v", geometry: Optional[Geometry] = None):
         super().__init__()
@@ -46,8 +45,7 @@ class CausalFPSInferencePipeline(torch.nn.Module):
         self.generator_cond = WanFPSWrapper(**getattr(args, "model_kwargs", {}), is_causal=True, geometry=self.geometry,
                                             device=device_cond) if generator is None else generator
         self.generator_cond.model.num_frame_per_block = 1
-        self.text_encoder = WanTextEncoder(device=device_cond) if text_encoder is None else text_encoder
-        self.vae = WanVAEWrapper(geometry=self.geometry, device=device_cond) if vae is None else vae
+        self._set_codecs(text_encoder, vae, device_cond)
 
         self.num_train_timesteps = args.num_train_timestep
         self.sampling_steps = getattr(args, "sampling_steps", 50)
@@ -95,9 +93,6 @@ class CausalFPSInferencePipeline(torch.nn.Module):
         self.image_or_video_shape = [1, 1, 16, self.geometry.lat_h, self.geometry.lat_w]
         self.ddpm_index = torch.randint(980, self.num_train_timesteps, [1, 1], device=self.device_cond, dtype=torch.long)
         self.ddmp_timestep = self.ddpm_scheduler.timesteps.to(self.ddpm_index.device)[self.ddpm_index] + 1000
-
-    def to(self, *args, **kwargs):
-        return self
 
     # ------------------------------------------------------------------------------------------------------------
     def _forward(self, latents, cond, timestep, kv, cross, frames, out=None, workspace=None, share_out=None, share_in=None):
@@ -234,32 +229,20 @@ class CausalFPSInferencePipeline(torch.nn.Module):
                         sample_scheduler._ensure_state(latents)
                         torch.cuda.synchronize(dev)
                         engine = self.generator_cond.engine
-                        concurrent = self.concurrent_cfg
-                        if concurrent is None:
-                            from ..stage_plan import concurrent_cfg_pays
-                            concurrent = concurrent_cfg_pays(len(frames) * S, engine.dim)
-                        ws2 = None
-                        share = engine.shared_block0_buffer(len(frames)) if (self.share_block0 and not concurrent) else None
-                        if concurrent:                                      # (allocations and the stream: outside the capture)
-                            ws2 = engine.second_workspace(len(frames))
-                            if self._side_stream is None:
-                                self._side_stream = torch.cuda.Stream(device=dev)
+                        concurrent = cfg_concurrent(self, engine, len(frames))
+                        # (allocations and the stream: outside the capture)
+                        share, ws2 = cfg_step_buffers(self, engine, len(frames), concurrent, engine.second_workspace, dev)
+                        if concurrent:
                             torch.cuda.synchronize(dev)
-                        step_graph = torch.cuda.CUDAGraph()
+
+                        def forward(bi, out, **kw):
+                            d, kv, cross, _ = branches[bi]
+                            self._forward(latents, d, timestep, kv, cross, frames, out, **kw)
+
+                        step_graph = torch.cuda.CUDAGraph()                   # (no eager run of its own: the forward graphs above had theirs)
                         with torch.cuda.graph(step_graph):
-                            if concurrent:
-                                main, side = torch.cuda.current_stream(dev), self._side_stream
-                                (d0, kv0, cr0, _), (d1, kv1, cr1, _) = branches
-                                side.wait_stream(main)                          # fork
-                                self._forward(latents, d0, timestep, kv0, cr0, frames, outs[0])
-                                with torch.cuda.stream(side):
-                                    self._forward(latents, d1, timestep, kv1, cr1, frames, outs[1], workspace=ws2)
-                                main.wait_stream(side)                          # join: the CFG / UniPC update needs both
-                            else:
-                                for bi, ((d, kv, cross, _), o) in enumerate(zip(branches, outs)):
-                                    self._forward(latents, d, timestep, kv, cross, frames, o, share_out=share if bi == 0 else None,
-                                                  share_in=share if bi == 1 else None)
-                            sample_scheduler.step_cfg_table(flow[0], flow[1], latents, timestep)
+                            cfg_step(forward, sample_scheduler, flow, latents, timestep, dev, self._side_stream if concurrent else None,
+                                     share, ws2)
                 for kv in live_kv:                                            # a new stage: other shapes, other blocks
                     kv.reset_attn_history()
                 if step_graph is not None:
@@ -307,21 +290,12 @@ class CausalFPSInferencePipeline(torch.nn.Module):
 
             video = None
             if decode and (pair is None or pair.role == 0):
-                video = self.vae.decode_to_pixel(output)
-                video = (video * 0.5 + 0.5).clamp(0, 1)
+                video = decode_video(self.vae, output)
         if return_latents:
             return video, output
         return video
 
     def _initialize_sample_scheduler(self, noise):
-        """casual_fps_inference.py:503-524.  Both classes offer the same device-facing interface (mmpl_amd/scheduler.py)."""
-        if self.sample_solver == "unipc":
-            s = FlowUniPCMultistepScheduler(num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
-            s.set_timesteps(self.sampling_steps, device=noise.device, shift=self.shift)
-            self.timesteps = s.timesteps
-        elif self.sample_solver == "dpm++":
-            s = FlowDPMSolverMultistepScheduler(num_train_timesteps=self.num_train_timesteps, shift=1, use_dynamic_shifting=False)
-            self.timesteps, _ = retrieve_timesteps(s, device=noise.device, sigmas=get_sampling_sigmas(self.sampling_steps, self.shift))
-        else:
-            raise NotImplementedError("Unsupported solver.")
+        """casual_fps_inference.py:503-524: the solver `sample_solver` names, `self.timesteps` set to its schedule."""
+        s, self.timesteps = make_sample_scheduler(self.sample_solver, self.num_train_timesteps, self.sampling_steps, self.shift, noise.device)
         return s

@@ -29,18 +29,14 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..wan_wrapper import WanDiffusionWrapper, WanTextEncoder, WanVAEWrapper
+from ._common import GeneratorPipeline, decode_video, eager_then_capture, fewstep_scalars, fill_bank
 
 
-class CausalInferencePipeline(torch.nn.Module):
+class CausalInferencePipeline(GeneratorPipeline):
     def __init__(self, args, device, generator=None, text_encoder=None, vae=None, preview_vae=None):
         super().__init__()
-        self.device = torch.device(device)
-        self.generator = WanDiffusionWrapper(**getattr(args, "model_kwargs", {}), is_causal=True,
-                                             device=device) if generator is None else generator
-        self.geometry = self.generator.geometry
-        self.text_encoder = WanTextEncoder(device=device) if text_encoder is None else text_encoder
-        self.vae = WanVAEWrapper(geometry=self.geometry, device=device) if vae is None else vae
+        self._set_generator(args, device, generator, is_causal=True)
+        self._set_codecs(text_encoder, vae, device)
         self.preview_vae = preview_vae    # optional TAEHVWrapper: inference_stream(decoder="preview")
 
         self.scheduler = self.generator.get_scheduler()
@@ -75,19 +71,13 @@ class CausalInferencePipeline(torch.nn.Module):
         self._out: Dict[int, torch.Tensor] = {}                     # static output latents, by frame count
         self._roll_bufs: Dict[tuple, torch.Tensor] = {}             # rolling blocks past the window: static x0, by graph key
         self._frame_base: Optional[torch.Tensor] = None             # ... and the int32 device scalar their RoPE positions start from
+        self._stores = (self._graphs, self._bufs, self._out, self._roll_bufs)
         self._side: Optional[torch.cuda.Stream] = None              # inference_stream: the decode stream
         self._stage: Optional[torch.Tensor] = None                  # inference_stream: pinned uint8 staging, [2, frames, H, W, 3]
 
-    def to(self, *args, **kwargs):
-        return self
-
     def release_graphs(self) -> None:
         """Drop every captured block graph (and the static buffers they read)."""
-        torch.cuda.synchronize(self.device)                           # the decode stream of inference_stream included
-        self._graphs.clear()
-        self._bufs.clear()
-        self._out.clear()
-        self._roll_bufs.clear()
+        super().release_graphs()                                      # synchronises: the decode stream of inference_stream included
         self._frame_base = None
 
     # ------------------------------------------------------------------------------------------------------------
@@ -106,13 +96,8 @@ class CausalInferencePipeline(torch.nn.Module):
         return sched
 
     def _step_scalars(self):
-        """(engine timestep, sigma of the x0 conversion, sigma of the next step's add_noise) per step, from the step list's
-        own dtype the way the reference's tensors carry it (float32 when warped, int64 otherwise)."""
-        steps = list(self.denoising_step_list)
-        t_eng = [float(t) for t in steps]
-        sig_x0 = [self.generator.sigma_x0(t) for t in steps]
-        sig_next = [self.generator.sigma_add_noise(t) for t in steps[1:]]
-        return t_eng, sig_x0, sig_next
+        """(engine timestep, sigma of the x0 conversion, sigma of the next step's add_noise) per step: a forward at every one."""
+        return fewstep_scalars(self.generator, self.denoising_step_list, len(self.denoising_step_list))
 
     def _block_buffers(self, F: int) -> dict:
         b = self._bufs.get(F)
@@ -187,8 +172,7 @@ class CausalInferencePipeline(torch.nn.Module):
             for blk in self.crossattn_cache:
                 blk["is_init"] = False
             self.generator.set_cache_ends(self.kv_cache1, 0, 0)
-        pe = conditional_dict["prompt_embeds"]
-        self.crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
+        self.crossattn_cache.fill(conditional_dict["prompt_embeds"])
 
         noise_bf = noise.to(device=dev, dtype=torch.bfloat16).contiguous()
         output = self._output(num_output_frames)
@@ -221,11 +205,7 @@ class CausalInferencePipeline(torch.nn.Module):
             b = self._block_buffers(F)
             write, vis, le = self.generator.slots(self.kv_cache1, s, F, rolling=self.rolling_kv)   # (rolling: checks the RoPE range)
             b["x"].copy_(noise_bf[0, s - num_input_frames:s - num_input_frames + F])
-            for i in range(n - 1):                                        # the reference's torch.randn_like draws, in order
-                if draws is not None:
-                    b["bank"][i].copy_(next(draws).reshape(b["bank"][i].shape))
-                else:
-                    b["bank"][i].normal_(0.0, 1.0, generator=self.noise_generator)
+            fill_bank(b["bank"], n - 1, draws, self.noise_generator)
             rolled = self.rolling_kv and s + F > W                        # a frame at or past the window: position-free launches
             if not rolled:
                 out_blk, rel, base = output[0, s:s + F], s, None
@@ -245,14 +225,9 @@ class CausalInferencePipeline(torch.nn.Module):
             g = self._graphs.get(key)
             if g is not None:
                 g.replay()
-            else:
-                self._run_block(b, out_blk, rel, write, vis, scalars, base)   # first use: the real work, eagerly ...
-                if self.use_graphs:                                       # ... then the same launches into the block's graph
-                    torch.cuda.synchronize(dev)
-                    g = torch.cuda.CUDAGraph()
-                    self.graph_captures += 1
-                    with torch.cuda.graph(g):
-                        self._run_block(b, out_blk, rel, write, vis, scalars, base)
+            else:                                                         # first use: eagerly, then into the block's graph
+                g = eager_then_capture(self, lambda: self._run_block(b, out_blk, rel, write, vis, scalars, base))
+                if g is not None:
                     self._graphs[key] = g
             if rolled:
                 output[0, s:s + F].copy_(out_blk)                         # on the compute stream: complete before the yield's consumers
@@ -299,8 +274,7 @@ class CausalInferencePipeline(torch.nn.Module):
                 vae_start.record()
 
             latents = output.clone().to(noise.dtype)
-            video = self.vae.decode_to_pixel(output.clone(), use_cache=False)
-            video = (video * 0.5 + 0.5).clamp(0, 1)
+            video = decode_video(self.vae, output.clone(), use_cache=False)
 
             if profile:
                 vae_end.record()

@@ -31,6 +31,39 @@ from .synthetic import WAN_CONFIGS
 local_wan_path = "../wan_models"
 
 
+def _state_dict_or_disk(state_dict: Optional[dict], path: str) -> Optional[dict]:
+    """`state_dict`, or, without one, the checkpoint at `path` (None where there is no such file)."""
+    if state_dict is None and os.path.exists(path):
+        from .checkpoints import read_state_dict
+        state_dict = read_state_dict(path)
+    return state_dict
+
+
+def _unbatched(pe: torch.Tensor) -> torch.Tensor:
+    """Rows of embeddings ([T, D]: prompt_embeds, clip_fea), or the reference's batch of one of them ([1, T, D]) -> [T, D]."""
+    return pe[0] if pe.dim() == 3 else pe
+
+
+def _source(t: torch.Tensor) -> tuple:
+    """What to remember of a tensor something is built from: the object and its version counter."""
+    return t, t._version
+
+
+def _built_from(src: Optional[tuple], t: torch.Tensor) -> bool:
+    """Is `src` (a `_source`, or None) this very tensor object, not written in place since?  What was built from it is then still its."""
+    return src is not None and src[0] is t and src[1] == t._version
+
+
+def _conditioning_video(y, engine: DitEngine, who: str) -> torch.Tensor:
+    """The i2v model type's `y` as the reference passes it ([20, F, h, w], a list of one such, or [1, 20, F, h, w]) -> the validated
+    [20, F, h, w]; ValueError (in the name of the wrapper `who`) for any other shape."""
+    yy = y[0] if isinstance(y, (list, tuple)) or y.dim() == 5 else y
+    e = engine
+    if yy.dim() != 4 or yy.shape[0] != e.in_dim - 16 or tuple(yy.shape[2:]) != (e.lat_h, e.lat_w):
+        raise ValueError(f"{who}: y is {tuple(yy.shape)}, expected [{e.in_dim - 16}, F, {e.lat_h}, {e.lat_w}]")
+    return yy
+
+
 class KVCache(list):
     """list of per-layer dicts like the reference's kv_cache; `k_all` / `v_all`: [L, n_slots*S, dim]."""
 
@@ -82,7 +115,8 @@ class CrossAttnCache(list):
         return all(b["is_init"] for b in self)
 
     def fill(self, prompt_embeds: torch.Tensor):
-        self.rows = self.engine.precompute_context(prompt_embeds, out=(self.k_all, self.v_all)).rows
+        """prompt_embeds: [T, D], or a text encoder's [1, T, D]."""
+        self.rows = self.engine.precompute_context(_unbatched(prompt_embeds), out=(self.k_all, self.v_all)).rows
         for b in self:
             b["is_init"] = True
 
@@ -109,33 +143,30 @@ class _ModelHandle:
         return iter(self.engine._weights)
 
 
-class WanFPSWrapper(torch.nn.Module):
-    def __init__(self, model_name="Wan2.1-T2V-14B", timestep_shift=8.0, is_causal=False, local_attn_size=-1, sink_size=0,
-                 *, model_config: Optional[dict] = None, geometry: Optional[Geometry] = None, device="cuda:0"):
+class _GeneratorBase(torch.nn.Module):
+    """What the two generator wrappers share: the model config (``model_config``, else the diffusers directory under
+    ``local_wan_path``, else ``WAN_CONFIGS`` by name), the ``DitEngine`` with the directory's weights, the training-time
+    ``FlowMatchScheduler`` and the nn.Module-compatible entry points the entry scripts use."""
+
+    def __init__(self, model_name, timestep_shift, is_causal, model_config, geometry, device, max_frames: int = 7):
         super().__init__()
-        assert is_causal, "only the causal FPS generator is on the hot path"
         self.geometry = geometry or Geometry.named("480p")
         from .checkpoints import read_diffusers_dir
-        cfg = model_config
-        wdir = f"{local_wan_path}/{model_name}/"
-        disk_cfg, disk_sd = read_diffusers_dir(wdir)          # CausalFPSWanModel.from_pretrained(...) (wan_wrapper.py:328-330)
+        # <Model>.from_pretrained(...) (wan_wrapper.py:127-133, 328-330); local_wan_path is read now, not at import
+        disk_cfg, disk_sd = read_diffusers_dir(f"{local_wan_path}/{model_name}/")
+        cfg = disk_cfg if model_config is None else model_config
         if cfg is None:
-            cfg = disk_cfg
-        if cfg is None:
-            key = "14B" if "14B" in model_name else "1.3B"
-            cfg = WAN_CONFIGS[key]
-        self.engine = DitEngine(cfg, self.geometry.lat_h, self.geometry.lat_w, device)
-        self.model = _ModelHandle(self.engine)
+            cfg = WAN_CONFIGS["14B" if "14B" in model_name else "1.3B"]
+        self.engine = DitEngine(cfg, self.geometry.lat_h, self.geometry.lat_w, device, max_frames=max_frames)
         if disk_sd is not None:
             self.engine.load_state_dict(disk_sd)
         self.model_type = self.engine.model_type
-        self._clip_src = None                 # (clip_fea tensor, its version counter) the engine's image K/V were built from
+        self._clip_src = None                 # i2v: the `_source` of the clip_fea the image K / V were built from
         self.uniform_timestep = not is_causal
         self.scheduler = FlowMatchScheduler(shift=timestep_shift, sigma_min=0.0, extra_one_step=True)
         self.scheduler.set_timesteps(1000, training=True)
-        self.seq_len = self.geometry.frame_seqlen * self.geometry.frames_per_chunk
+        self.seq_len = self.geometry.frame_seqlen * self.geometry.frames_per_chunk      # the reference's 32760
 
-    # nn.Module-compatible entry points the entry scripts use
     def load_state_dict(self, state_dict, strict: bool = True):
         """MMPL .pt checkpoints hold {'generator': {'model.<key>': tensor}} (Wan_fps_inference_1gpu.py:66-68)."""
         from .checkpoints import strip_generator_prefix
@@ -145,14 +176,22 @@ class WanFPSWrapper(torch.nn.Module):
     def to(self, *args, **kwargs):
         return self                       # weights already live on the GPU in bf16
 
-    def get_scheduler(self):
+    def get_scheduler(self) -> FlowMatchScheduler:
         return self.scheduler
-
-    def new_kv_cache(self, n_slots: int = 15) -> KVCache:
-        return KVCache(self.engine, n_slots)
 
     def new_crossattn_cache(self) -> CrossAttnCache:
         return CrossAttnCache(self.engine)
+
+
+class WanFPSWrapper(_GeneratorBase):
+    def __init__(self, model_name="Wan2.1-T2V-14B", timestep_shift=8.0, is_causal=False, local_attn_size=-1, sink_size=0,
+                 *, model_config: Optional[dict] = None, geometry: Optional[Geometry] = None, device="cuda:0"):
+        assert is_causal, "only the causal FPS generator is on the hot path"
+        super().__init__(model_name, timestep_shift, is_causal, model_config, geometry, device)
+        self.model = _ModelHandle(self.engine)
+
+    def new_kv_cache(self, n_slots: int = 15) -> KVCache:
+        return KVCache(self.engine, n_slots)
 
     def _image_stream(self, frames, conditional_dict, clip_fea, y):
         """Wan-I2V model type: make sure the engine's image K/V belong to this `clip_fea` (MLPProj + per-block k_img / v_img,
@@ -163,26 +202,20 @@ class WanFPSWrapper(torch.nn.Module):
         y = conditional_dict.get("y") if y is None else y
         if clip_fea is None or y is None:
             raise ValueError("WanFPSWrapper: an i2v model needs clip_fea and y (model.py:672-673)")
-        key = (clip_fea, clip_fea._version)       # same tensor object AND not written in place since: the K/V are still its
-        if self._clip_src is None or self._clip_src[0] is not key[0] or self._clip_src[1] != key[1]:
-            fea = clip_fea[0] if clip_fea.dim() == 3 else clip_fea
-            self.engine.set_image_kv(*self.engine.precompute_image_context(fea))
-            self._clip_src = key
-        yy = y[0] if isinstance(y, (list, tuple)) or y.dim() == 5 else y              # [20, F, h, w]
-        assert yy.shape[0] == self.engine.in_dim - 16 and yy.shape[2:] == (self.engine.lat_h, self.engine.lat_w), tuple(yy.shape)
+        if not _built_from(self._clip_src, clip_fea):
+            self.engine.set_image_kv(*self.engine.precompute_image_context(_unbatched(clip_fea)))
+            self._clip_src = _source(clip_fea)
+        yy = _conditioning_video(y, self.engine, "WanFPSWrapper")
         # (a stack of views: no host-built index tensor, so this also runs inside a hipGraph capture)
         return torch.stack([yy[:, f] for f in frames], dim=0).to(device=self.engine.device, dtype=torch.bfloat16)
 
-    def capture(self, noisy_image_or_video, conditional_dict, timestep, kv_cache, crossattn_cache, current_start, out,
-                clip_fea=None, y=None):
-        """hipGraph of this exact forward (fixed buffers / stage shape); returns the graph, replay() re-runs it on the
-        current contents of `noisy_image_or_video`, `timestep` and the caches."""
-        assert noisy_image_or_video.is_contiguous() and noisy_image_or_video.dtype == torch.bfloat16
-        assert timestep.dtype == torch.float32 and timestep.is_contiguous() and out.is_contiguous()
+    def _stage(self, x, conditional_dict, kv_cache, crossattn_cache, current_start, clip_fea, y):
+        """What `forward` and `capture` do before the engine call: fill the cross-attention cache on first use (model.py:175-180),
+        make the stage's frames visible (causal_fps_model.py:209,219 / 255), bring `x` ([nF, 16, h, w]) to contiguous bf16 and
+        build the i2v model type's image stream.  -> (x, frames, visible slots, ys)"""
         S = self.engine.S
         if not crossattn_cache.is_init:
-            pe = conditional_dict["prompt_embeds"]
-            crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
+            crossattn_cache.fill(conditional_dict["prompt_embeds"])
         starts = [int(s) for s in current_start]
         frames = [s // S for s in starts]
         vis = kv_cache.vis
@@ -190,14 +223,24 @@ class WanFPSWrapper(torch.nn.Module):
             for s in starts:
                 if s not in vis:
                     vis.append(s)
-        x, pre = noisy_image_or_video[0], None
-        ys = self._image_stream(frames, conditional_dict, clip_fea, y)
+        if x.dtype != torch.bfloat16 or not x.is_contiguous():
+            x = x.to(torch.bfloat16).contiguous()
+        return x, frames, [slot_of(o // S) for o in vis], self._image_stream(frames, conditional_dict, clip_fea, y)
+
+    def capture(self, noisy_image_or_video, conditional_dict, timestep, kv_cache, crossattn_cache, current_start, out,
+                clip_fea=None, y=None):
+        """hipGraph of this exact forward (fixed buffers / stage shape); returns the graph, replay() re-runs it on the
+        current contents of `noisy_image_or_video`, `timestep` and the caches."""
+        assert noisy_image_or_video.is_contiguous() and noisy_image_or_video.dtype == torch.bfloat16
+        assert timestep.dtype == torch.float32 and timestep.is_contiguous() and out.is_contiguous()
+        x, frames, visible, ys = self._stage(noisy_image_or_video[0], conditional_dict, kv_cache, crossattn_cache, current_start,
+                                             clip_fea, y)
+        pre = None
         if ys is not None:                    # static 36-channel input; the graph refreshes its latent channels before the forward
             lat, x = x, torch.cat([x, ys], dim=1).contiguous()
             pre = lambda: x[:, :16].copy_(lat)
-        g = self.engine.capture(x, timestep.view(-1), frames, StagePlan.write_slots(frames),
-                                [slot_of(o // S) for o in vis], kv_cache.k_all, kv_cache.v_all, crossattn_cache.k_all,
-                                crossattn_cache.v_all, out[0], pre=pre, cross_rows=crossattn_cache.rows,
+        g = self.engine.capture(x, timestep.view(-1), frames, StagePlan.write_slots(frames), visible, kv_cache.k_all, kv_cache.v_all,
+                                crossattn_cache.k_all, crossattn_cache.v_all, out[0], pre=pre, cross_rows=crossattn_cache.rows,
                                 attn_history=kv_cache.attn_history)
         return g if ys is None else _HeldGraph(g, x)
 
@@ -209,26 +252,11 @@ class WanFPSWrapper(torch.nn.Module):
                 share_in: Optional[torch.Tensor] = None):
         assert kv_cache is not None and crossattn_cache is not None, "the FPS path always runs with caches"
         assert noisy_image_or_video.shape[0] == 1, "batch size 1 (as every reference entry point)"
-        S = self.engine.S
-        if not crossattn_cache.is_init:                                   # model.py:175-180
-            pe = conditional_dict["prompt_embeds"]
-            crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
-        starts = [int(s) for s in current_start]
-        frames = [s // S for s in starts]
-        vis = kv_cache.vis
-        if 15 * S not in starts:                                          # causal_fps_model.py:209,219 / 255
-            for s in starts:
-                if s not in vis:
-                    vis.append(s)
-        x = noisy_image_or_video[0]
-        if x.dtype != torch.bfloat16 or not x.is_contiguous():
-            x = x.to(torch.bfloat16).contiguous()
-        lat = x
-        ys = self._image_stream(frames, conditional_dict, clip_fea, y)
-        if ys is not None:
-            x = torch.cat([x, ys], dim=1).contiguous()                     # model.py:680-681
+        lat, frames, visible, ys = self._stage(noisy_image_or_video[0], conditional_dict, kv_cache, crossattn_cache, current_start,
+                                               clip_fea, y)
+        x = lat if ys is None else torch.cat([lat, ys], dim=1).contiguous()       # model.py:680-681
         t = timestep.reshape(-1).to(device=x.device, dtype=torch.float32)
-        flow = self.engine.forward(x, t, frames, StagePlan.write_slots(frames), [slot_of(o // S) for o in vis],
+        flow = self.engine.forward(x, t, frames, StagePlan.write_slots(frames), visible,
                                    kv_cache.k_all, kv_cache.v_all, crossattn_cache.k_all, crossattn_cache.v_all,
                                    out=None if out is None else out[0], cross_rows=crossattn_cache.rows, workspace=workspace,
                                    share_out=share_out, share_in=share_in, attn_history=kv_cache.attn_history)
@@ -262,10 +290,7 @@ class WanTextEncoder(torch.nn.Module):
         self.model = None
         if encode_fn is not None:
             return
-        path = pretrained_path or f"{local_wan_path}/Wan2.1-T2V-14B/models_t5_umt5-xxl-enc-bf16.pth"
-        if state_dict is None and os.path.exists(path):
-            from .checkpoints import read_state_dict
-            state_dict = read_state_dict(path)
+        state_dict = _state_dict_or_disk(state_dict, pretrained_path or f"{local_wan_path}/Wan2.1-T2V-14B/models_t5_umt5-xxl-enc-bf16.pth")
         if state_dict is not None:
             from .checkpoints import infer_t5_config
             from .t5 import T5Engine
@@ -338,10 +363,7 @@ class WanVAEWrapper(torch.nn.Module):
         from .vae import VaeEngine
         self.geometry = geometry or Geometry.named("480p")
         self.model = VaeEngine(self.geometry.lat_h, self.geometry.lat_w, device)
-        path = pretrained_path or f"{local_wan_path}/Wan2.1-T2V-14B/Wan2.1_VAE.pth"
-        if state_dict is None and os.path.exists(path):
-            from .checkpoints import read_state_dict
-            state_dict = read_state_dict(path)
+        state_dict = _state_dict_or_disk(state_dict, pretrained_path or f"{local_wan_path}/Wan2.1-T2V-14B/Wan2.1_VAE.pth")
         if state_dict is not None:
             self.model.load_state_dict(state_dict)
 
@@ -387,10 +409,7 @@ class TAEHVWrapper(torch.nn.Module):
         self.model = TaehvEngine(self.geometry.lat_h, self.geometry.lat_w, device)
         self.encoder = None                                          # TaehvEncoderEngine once encoder weights are loaded
         self.mean, self.std = None, None                             # both halves work in the normalised latent space
-        path = pretrained_path or f"{local_wan_path}/taew2_1.pth"
-        if state_dict is None and os.path.exists(path):
-            from .checkpoints import read_state_dict
-            state_dict = read_state_dict(path)
+        state_dict = _state_dict_or_disk(state_dict, pretrained_path or f"{local_wan_path}/taew2_1.pth")
         if state_dict is not None:
             self.model.load_state_dict(state_dict)
             if any(k.startswith("encoder.") for k in state_dict):
@@ -516,7 +535,7 @@ class _CausalModelHandle(_ModelHandle):
         self.sink_size = sink_size
 
 
-class WanDiffusionWrapper(torch.nn.Module):
+class WanDiffusionWrapper(_GeneratorBase):
     """utils/wan_wrapper.py:116-300 with ``is_causal=True`` (CausalWanModel, the Self-Forcing / CausVid generator) on the HIP DiT.
 
     For inference CausalWanModel differs from CausalFPSWanModel in two places only, both host-side here:
@@ -537,48 +556,18 @@ class WanDiffusionWrapper(torch.nn.Module):
 
     def __init__(self, model_name="Wan2.1-T2V-14B", timestep_shift=8.0, is_causal=False, local_attn_size=-1, sink_size=0,
                  *, model_config: Optional[dict] = None, geometry: Optional[Geometry] = None, device="cuda:0", max_frames: int = 7):
-        super().__init__()
+        super().__init__(model_name, timestep_shift, is_causal, model_config, geometry, device, max_frames)
         self.is_causal = bool(is_causal)
-        self.geometry = geometry or Geometry.named("480p")
-        from .checkpoints import read_diffusers_dir
-        cfg = model_config
-        # CausalWanModel.from_pretrained / WanModel.from_pretrained (:127-133)
-        disk_cfg, disk_sd = read_diffusers_dir(f"{local_wan_path}/{model_name}/")
-        if cfg is None:
-            cfg = disk_cfg
-        if cfg is None:
-            cfg = WAN_CONFIGS["14B" if "14B" in model_name else "1.3B"]
-        self.engine = DitEngine(cfg, self.geometry.lat_h, self.geometry.lat_w, device, max_frames=max_frames)
-        if self.engine.model_type != "t2v" and self.is_causal:
+        if self.model_type != "t2v" and self.is_causal:
             raise ValueError("WanDiffusionWrapper: the few-step causal generator is a t2v model (the i2v model type is bidirectional: "
                              "is_causal=False)")
         self.local_attn_size = int(local_attn_size)
         # is_causal=False: WanModel, the whole clip in one forward (DitEngine.forward_full); nothing of the causal cache applies
         self.model = _CausalModelHandle(self.engine, self.local_attn_size, sink_size) if self.is_causal else _ModelHandle(self.engine)
-        self._ctx: List[tuple] = []               # is_causal=False: (prompt_embeds, its version, CrossKV) of the last two prompts
-        if disk_sd is not None:
-            self.engine.load_state_dict(disk_sd)
-        self.model_type = self.engine.model_type
-        self._clip_src = None                 # i2v: (clip_fea tensor, its version counter) the image K / V were built from
+        self._ctx: List[tuple] = []               # is_causal=False: (`_source` of prompt_embeds, CrossKV) of the last two prompts
         self._img_kv = None                   # i2v: the wrapper's one (img_k, img_v) pair, refreshed in place by set_image
-        self.uniform_timestep = not is_causal
-        self.scheduler = FlowMatchScheduler(shift=timestep_shift, sigma_min=0.0, extra_one_step=True)
-        self.scheduler.set_timesteps(1000, training=True)
-        self.seq_len = self.geometry.frame_seqlen * self.geometry.frames_per_chunk      # the reference's 32760
         self._sig64 = self.scheduler.sigmas.double()
         self._ts64 = self.scheduler.timesteps.double()
-
-    # nn.Module-compatible entry points
-    def load_state_dict(self, state_dict, strict: bool = True):
-        from .checkpoints import strip_generator_prefix
-        self.engine.load_state_dict(strip_generator_prefix(state_dict))
-        return torch.nn.modules.module._IncompatibleKeys([], [])
-
-    def to(self, *args, **kwargs):
-        return self
-
-    def get_scheduler(self) -> FlowMatchScheduler:
-        return self.scheduler
 
     @property
     def window_frames(self) -> int:
@@ -588,9 +577,6 @@ class WanDiffusionWrapper(torch.nn.Module):
     def new_kv_cache(self, n_slots: Optional[int] = None) -> KVCache:
         """The reference's kv_cache1 (causal_inference.py:278-297): local_attn_size frames, or 32760 tokens = 21 frames."""
         return KVCache(self.engine, self.window_frames if n_slots is None else n_slots)
-
-    def new_crossattn_cache(self) -> CrossAttnCache:
-        return CrossAttnCache(self.engine)
 
     # -- host scalars of the reference's timestep -> sigma lookups ------------------------------------------------------------
     def sigma_x0(self, timestep) -> float:
@@ -664,34 +650,31 @@ class WanDiffusionWrapper(torch.nn.Module):
         this very tensor and it was not written since."""
         if self.model_type != "i2v":
             raise ValueError("WanDiffusionWrapper.set_image: the generator is a t2v model")
-        if self._clip_src is not None and self._clip_src[0] is clip_fea and self._clip_src[1] == clip_fea._version:
+        if _built_from(self._clip_src, clip_fea):
             return
-        fea = clip_fea[0] if clip_fea.dim() == 3 else clip_fea
+        fea = _unbatched(clip_fea)
         if self._img_kv is not None and self._img_kv[0].shape[1] != fea.shape[0]:
             raise ValueError(f"WanDiffusionWrapper.set_image: {fea.shape[0]} image tokens, the attached K / V hold {self._img_kv[0].shape[1]}")
         first = self._img_kv is None
         self._img_kv = self.engine.precompute_image_context(fea, out=self._img_kv)
         if first:
             self.engine.set_image_kv(*self._img_kv)
-        self._clip_src = (clip_fea, clip_fea._version)
+        self._clip_src = _source(clip_fea)
 
     def frame_major_y(self, y) -> torch.Tensor:
         """The conditioning video as the reference passes it ([20, F, h, w], a list of one such, or [1, 20, F, h, w]) -> [F, 20, h, w]
         bf16 on the engine's device, the layout `flow_full` reads."""
-        yy = y[0] if isinstance(y, (list, tuple)) or y.dim() == 5 else y
-        e = self.engine
-        if yy.dim() != 4 or yy.shape[0] != e.in_dim - 16 or tuple(yy.shape[2:]) != (e.lat_h, e.lat_w):
-            raise ValueError(f"WanDiffusionWrapper: y is {tuple(yy.shape)}, expected [{e.in_dim - 16}, F, {e.lat_h}, {e.lat_w}]")
-        return yy.to(device=e.device, dtype=torch.bfloat16).permute(1, 0, 2, 3).contiguous()
+        yy = _conditioning_video(y, self.engine, "WanDiffusionWrapper")
+        return yy.to(device=self.engine.device, dtype=torch.bfloat16).permute(1, 0, 2, 3).contiguous()
 
     def _context_kv(self, prompt_embeds: torch.Tensor):
         """Per-layer text K / V of `prompt_embeds`, kept for the last two prompts (the cond and the uncond one of a CFG loop) as
         long as the tensor is the same object and was not written since."""
-        for src, ver, kv in self._ctx:
-            if src is prompt_embeds and ver == prompt_embeds._version:
+        for src, kv in self._ctx:
+            if _built_from(src, prompt_embeds):
                 return kv
-        kv = self.engine.precompute_context(prompt_embeds[0] if prompt_embeds.dim() == 3 else prompt_embeds)
-        self._ctx = self._ctx[-1:] + [(prompt_embeds, prompt_embeds._version, kv)]
+        kv = self.engine.precompute_context(_unbatched(prompt_embeds))
+        self._ctx = self._ctx[-1:] + [(_source(prompt_embeds), kv)]
         return kv
 
     def _forward_full(self, noisy_image_or_video: torch.Tensor, conditional_dict: dict, timestep: torch.Tensor):
@@ -741,8 +724,7 @@ class WanDiffusionWrapper(torch.nn.Module):
         if cs % S:
             raise ValueError(f"current_start {cs} is not a multiple of the frame length {S}")
         if not crossattn_cache.is_init:                                   # model.py:175-180
-            pe = conditional_dict["prompt_embeds"]
-            crossattn_cache.fill(pe[0] if pe.dim() == 3 else pe)
+            crossattn_cache.fill(conditional_dict["prompt_embeds"])
         x = noisy_image_or_video[0].to(torch.bfloat16).contiguous()
         nF = x.shape[0]
         ts = timestep.reshape(-1)
