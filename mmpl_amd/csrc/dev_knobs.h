@@ -8,9 +8,8 @@
 
 #ifndef MMPL_DEV_ABLATIONS
 #if defined(W64_ABL) || defined(W64_LMIN_EXP) || defined(W64_LMAX_EXP) || defined(W64_REF_OFFSET) || defined(W64_REF_TILES) ||           \
-    defined(GEMM_POLICY_A) || defined(GEMM_POLICY_W) || defined(GEMM6_ABL) || defined(GEMM6_STORE) || defined(GEMM6_RESLD) ||            \
-    defined(GEMM6_TIMING) || defined(GEMM8_ABL) || defined(GEMM8_BAR1) || defined(GEMM8_DMAS) || defined(GEMM8_BAR2) || defined(GEMM8_RD) || \
-    defined(GEMM8_FINEWAIT) || defined(GEMM8_PF)
+    defined(GEMM6_ABL) || defined(GEMM6_TIMING) || defined(GEMM8_ABL) || defined(GEMM8_BAR1) || defined(GEMM8_DMAS) ||                  \
+    defined(GEMM8_BAR2) || defined(GEMM8_RD) || defined(GEMM8_FINEWAIT) || defined(GEMM8_PF)
 #error "development knob on the command line without -DMMPL_DEV_ABLATIONS (mmpl_amd/csrc/dev_knobs.h)"
 #endif
 #endif
@@ -35,26 +34,12 @@
 #endif
 
 // ---- gemm.hip
-// GEMM_POLICY_A / _W: cache-policy modifier of the LDS-DMA loads of the activation / weight operand in the large-problem kernels:
-// 0 none, 1 nt, 2 sc1, 3 sc0 sc1 (profiles/r05*_gemm_policy*.log: rejected).
-#ifndef GEMM_POLICY_A
-#define GEMM_POLICY_A 0
-#endif
-#ifndef GEMM_POLICY_W
-#define GEMM_POLICY_W 0
-#endif
 // GEMM6_ABL (results are garbage): 1 = every block's LDS-DMA reads operand tile (0, 0): same instruction stream and LDS traffic, every
 // fetch an L2 hit -> what the loop costs without fabric / HBM latency; 2 = no epilogue at all (what a perfectly overlapped epilogue
 // would leave); 4 = no LDS-DMA in the k loop; 8 = the whole staged epilogue except its global stores; 16 = no residual loads in the
 // staged epilogue (a constant instead: the upper bound of what issuing them under the last k-tile could hide)
 #ifndef GEMM6_ABL
 #define GEMM6_ABL 0
-#endif
-#ifndef GEMM6_STORE
-#define GEMM6_STORE 1       // cache policy of the staged epilogue's C stores: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1 (write-through, no L2 allocate)
-#endif
-#ifndef GEMM6_RESLD
-#define GEMM6_RESLD 0       // residual loads of the staged epilogue: 0 plain, 1 nt
 #endif
 #ifndef GEMM6_TIMING
 #define GEMM6_TIMING 0      // 1 = every wave leaves { prologue, k loop, epilogue } shader cycles over the output (tools/bench_kernels.py gemmphases)

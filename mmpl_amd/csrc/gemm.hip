@@ -1,13 +1,28 @@
 // bf16 GEMM with fused epilogues for the Wan DiT linears:  C[M,N] = epi( A[M,K] . W[N,K]^T + bias[N] ).
 //
-// A is token-major activations, W is an nn.Linear weight ([out, in], K contiguous) -- both operands are
-// K-contiguous, which is exactly the MFMA A/B fragment shape, so no transposes anywhere.
-// Tile 128x128x64, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 fragments of
-// v_mfma_f32_16x16x32_bf16.  Operands are staged global -> registers -> XOR-swizzled LDS (conflict-free
-// ds_read_b128), double-buffered with the next tile's global loads in flight under the
-// current tile's MFMAs; one barrier per K tile.  The MFMA is issued "swapped" (W fragment as the A
-// operand) so each lane ends up with 4 consecutive output columns -> 8-byte epilogue loads/stores.
-// Rounding points of the epilogues follow the reference's bf16 module boundaries (DESIGN.md "numerics").
+// A is token-major activations, W is an nn.Linear weight ([out, in], K contiguous) -- both operands are K-contiguous, which is exactly
+// the MFMA A/B fragment shape, so no transposes anywhere.  Every kernel multiplies 64-wide k-tiles with v_mfma_f32_16x16x32_bf16 out of
+// XOR-swizzled LDS (swz64: conflict-free ds_read_b128) and issues the MFMA "swapped" (W fragment as the A operand), so each
+// lane ends up with 4 consecutive output columns of one token row.  Rounding points of the epilogues follow the reference's bf16 module
+// boundaries (DESIGN.md "numerics").  mmpl_gemm_plan picks the kernel; the launchers decide nothing.
+//
+//   kernel                block tile   waves      operand path                              picked for (mmpl_gemm_plan)
+//   gemm_bf16_kernel      128 x 128    4 (2 x 2)  global -> registers -> LDS, 2 stages      everything else: small, batched (GEMM_KERNEL_SMALL)
+//   gemm_bf16_v2_kernel   256 x 128    8 (4 x 2)  LDS-DMA, 3-stage ring, 64-bit addresses   M >= 1024, N >= 128, K >= 128 that v6 cannot take
+//                                                                                           (N < 256, or an operand of 4 GiB) (GEMM_KERNEL_V2)
+//   gemm_bf16_v6_kernel   256 x 256    8 (2 x 4)  LDS-DMA, 2-stage ring, two wave groups    M >= 1024, N >= 256, K >= 128, one matrix
+//                                                 half a k-tile apart ("ping-pong")         (GEMM_KERNEL_V6, plan_v6)
+//   gemm_bf16_v8_kernel   256 x 256    4 (2 x 2)  the same ring; a wave owns 128 x 128 in   the same, N >= 8192 (GEMM_KERNEL_V8, plan_v6)
+//                                                 the accumulator file, k-tile in registers
+//   gemm_tail128_kernel   128 x 128    4 (2 x 2)  a quadrant of a 256 x 256 tile            tails of v6 / v8 (below)
+//
+// v6 and v8 walk one tile order (XcdTileList): every XCD owns a list of tiles, and with tile tickets (draw_ticket) a launch of one block
+// per CU works through it.  When the tile count leaves a partial last round of one tile per CU, plan_v6 stops the main launch at the
+// full rounds and gives the leftover tiles of every list to a tail launch:
+//   GEMM_TAIL_SPLITK   K >= 4096: gemm_bf16_v6_kernel<EPI, true>, s blocks per tile over 1/s of the k-tiles each, fp32 partials summed
+//                      in part order by whoever finishes last
+//   GEMM_TAIL_128_8    K < 4096, the leftovers fit one round at one block per CU: quadrants on gemm128_ring_tile (4-stage LDS-DMA ring)
+//   GEMM_TAIL_128_4    K < 4096, ... at two blocks per CU: quadrants on gemm128_tile (the small kernel's register-staged body)
 #include <stdlib.h>
 
 #include "common.h"
@@ -18,29 +33,156 @@
 
 // per-phase shader-cycle counters of the large-problem kernels: development builds with -DGEMM6_TIMING=1 only (dev_knobs.h)
 #ifdef MMPL_DEV_ABLATIONS
-#define GEMM_DEV_TICKS [[maybe_unused]] unsigned long long tk0 = 0, tk1 = 0, tk2 = 0, tk3 = 0
+#define GEMM_DEV_TICKS [[maybe_unused]] unsigned long long tk0 = 0, tk1 = 0, tk2 = 0
 #define GEMM_DEV_TICK(x) do { if constexpr (GEMM6_TIMING) x = __builtin_readcyclecounter(); } while (0)
+#define GEMM_DEV_DUMP(writer, slot, nt) do { if constexpr (GEMM6_TIMING) gemm_dev_dump(g, writer, slot, tk0, tk1, tk2, nt); } while (0)
 #else
 #define GEMM_DEV_TICKS do { } while (0)
 #define GEMM_DEV_TICK(x) do { } while (0)
+#define GEMM_DEV_DUMP(writer, slot, nt) do { } while (0)
 #endif
+#define MMPL_HD __host__ __device__ __forceinline__
 
 namespace {
 using w64::sfor;
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB per operand tile
+// The 256 x 256 x 64 block tile of v6, v8 and (as four quadrants) the 128 x 128 tails: one stage of the LDS ring = the activation
+// rows [0, 32 KiB) + the weight rows [32 KiB, 64 KiB), both swizzled like every other tile (swz64)
+constexpr int BM256 = 256, BN256 = 256;
+constexpr int OPER256_BYTES = BM256 * BK * 2, STAGE256 = 2 * OPER256_BYTES;
+
+// ---------------------------------------------------------------------------------------------------------------
+// Pieces every kernel shares.
+// Byte offset of 16-byte chunk c of row r in a swizzled tile of 64-wide (128-byte) bf16 rows
+MMPL_DEV int swz64(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
+
+MMPL_DEV void zero_acc(f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// One 32-wide k-step of a wave's 64 x 64 tile: 4 + 4 fragment reads and 16 MFMAs, weights as the A operand.  a_off / w_off:
+// swz64(row of fragment i, lane >> 4); the chunk of k-step ks is 4 ks + (lane >> 4), and XOR with (row & 7) commutes with adding
+// 4 ks (bit 2).  (The loop over the two k-steps of a k-tile stays with the caller: inside this function hipcc schedules v2's loop differently.)
+MMPL_DEV void kstep4x4(f32x4 (&acc)[4][4], const char* As, const int (&a_off)[4], const char* Ws, const int (&w_off)[4], int ks) {
+  bf16x8 af[4], wf[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    af[i] = *reinterpret_cast<const bf16x8*>(As + (a_off[i] ^ (ks << 6)));
+    wf[i] = *reinterpret_cast<const bf16x8*>(Ws + (w_off[i] ^ (ks << 6)));
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
+}
+
+// 4 / 8 bf16 of 2 / 4 words -> fp32
+MMPL_DEV void unpack4(const uint2& w, float (&f)[4]) {
+  f[0] = __uint_as_float(w.x << 16); f[1] = __uint_as_float(w.x & 0xffff0000u);
+  f[2] = __uint_as_float(w.y << 16); f[3] = __uint_as_float(w.y & 0xffff0000u);
+}
+MMPL_DEV void unpack8(const uint4& w, float (&f)[8]) {
+  const uint32_t x[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = __uint_as_float((e & 1) ? (x[e >> 1] & 0xffff0000u) : (x[e >> 1] << 16));
+}
+
+// Grouped-M order: position `bid` of a tile list -> tile (tm, tn).  A group is `group` row panels x all column panels, walked
+// down the rows first, so the tiles in flight together span few row panels; gsz = row panels of the (ragged last) group.
+struct TileAt { int tm, tn, gsz, bid; };
+MMPL_HD TileAt grouped_m(int bid, int tiles_m, int per_group, int group) {
+  const int first_m = (bid / per_group) * group;
+  const int gsz = tiles_m - first_m < group ? tiles_m - first_m : group;
+  return {first_m + (bid % per_group) % gsz, (bid % per_group) / gsz, gsz, bid};
+}
+// The tile of block blockIdx.x of a one-block-per-tile launch of TM x TN tiles: XCD-aware (blocks b, b + 8, ... share an L2 and get a
+// contiguous eighth of the list) + grouped along M
+template <int GROUP, int TM, int TN> MMPL_DEV TileAt grouped_tile(int M, int N) {
+  const int tiles_m = (M + TM - 1) / TM, tiles_n = (N + TN - 1) / TN;
+  const int nwg = tiles_m * tiles_n;
+  const int q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+  const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective for any nwg
+  return grouped_m(bid, tiles_m, GROUP * tiles_n, GROUP);
+}
+
+// The tile order of the 256 x 256 kernels (v6, v8, their 128 x 128 tails) and of plan_v6: every XCD owns a list of tiles in
+// grouped-M order, so that the blocks sharing one L2 work on neighbouring tiles.  Without tile tickets block b is entry b >> 3 of
+// XCD b & 7's list (the hardware deals blocks round-robin to the XCDs); with them see draw_ticket.
+// Sweep-synchronous order (sync_sweeps): the M-groups (`group` row panels x all column panels) are dealt to the XCDs like cards
+// -- XCD x works through groups x, x + 8, x + 16, ... -- so all eight XCDs walk the column panels of W at the same time, a W
+// panel comes out of HBM once per sweep and the other seven XCDs find it in the Infinity Cache.  With contiguous chunks of
+// the tile list (the previous order) the XCDs sat at eight different column positions and W was streamed from HBM eight
+// times over: 8.5 GB of fabric reads per qkv GEMM, 2.7 TB/s, every L2 miss an HBM miss.  What the deal leaves over (fewer than
+// 8 full groups, a ragged last group) is split into eight contiguous chunks as before.
+struct XcdTileList {
+  int tiles_m, tiles_n, per_group;   // per_group: tiles of an M-group
+  int dealt;                         // tiles of this list that come from dealt groups (its first entries)
+  int lq, lr;                        // the remainder: lq tiles per XCD, one more on the first lr XCDs
+  int chunk_all;                     // length of this XCD's list
+  int group, xcd;
+  MMPL_HD XcdTileList(int M, int N, int group_, int sync_sweeps, int xcd_) : group(group_), xcd(xcd_) {
+    tiles_m = (M + BM256 - 1) / BM256;
+    tiles_n = (N + BN256 - 1) / BN256;
+    per_group = group * tiles_n;
+    const int rounds = sync_sweeps ? (tiles_m / group) >> 3 : 0;
+    dealt = rounds * per_group;
+    const int left = tiles_m * tiles_n - 8 * dealt;
+    lq = left >> 3;
+    lr = left & 7;
+    chunk_all = dealt + lq + (xcd < lr ? 1 : 0);
+  }
+  // Entries the main launch computes: all, or (splitk_s > 1: a tail launch takes the rest) the full rounds of `per` CUs
+  MMPL_HD int main_chunk(int splitk_s, int per) const { return splitk_s > 1 ? chunk_all - chunk_all % per : chunk_all; }
+  MMPL_HD TileAt tile(int idx) const {
+    const int bid = idx < dealt ? ((idx / per_group) * 8 + xcd) * per_group + idx % per_group
+                                : 8 * dealt + (xcd < lr ? xcd * (lq + 1) : lr * (lq + 1) + (xcd - lr) * lq) + (idx - dealt);
+    return grouped_m(bid, tiles_m, per_group, group);
+  }
+};
+
+// Tile tickets (GemmArgs.tile_counter): the kernel is launched once per CU and a block takes the next tile of ITS XCD's list when
+// it is done with the previous one: equal tiles do not take equal time (blocks that are first to touch an operand panel wait on
+// HBM, 33-42 cycles per MFMA across blocks), and a lock-step round lasts as long as its slowest block.  Exactly chunk + (blocks of
+// the XCD) tickets are drawn per launch; whoever draws the last one knows every other block of the XCD is leaving and zeroes the
+// counter for the next launch.  Returns the drawn list index, or -1: leave.  Block-uniform; s_ticket is the block's exchange word,
+// blocks_x the blocks of this launch on the XCD ((gridDim.x >> 3) + (xcd < (gridDim.x & 7)), computed once outside the caller's loop).
+MMPL_DEV int draw_ticket(int* counter, int& s_ticket, int chunk, int xcd, int blocks_x) {
+  if (threadIdx.x == 0) s_ticket = atomicAdd(counter + xcd, 1);
+  __syncthreads();
+  const int ticket = s_ticket;
+  if (ticket < chunk) return ticket;
+  if (ticket == chunk + blocks_x - 1 && threadIdx.x == 0) counter[xcd] = 0;
+  return -1;
+}
+
+#ifdef MMPL_DEV_ABLATIONS
+// -DGEMM6_TIMING=1: { prologue, k loop, epilogue } shader cycles of a wave, over the output: slot = 4 floats, the layout
+// tools/bench_kernels.py gemmphases reads
+MMPL_DEV void gemm_dev_dump(const GemmArgs& g, bool writer, int slot, unsigned long long tk0, unsigned long long tk1, unsigned long long tk2, int nt) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned long long tk3 = __builtin_readcyclecounter();
+  __syncthreads();
+  if (!writer) return;
+  float* tp = reinterpret_cast<float*>(g.C) + slot * 4;
+  tp[0] = (float)(tk1 - tk0);
+  tp[1] = (float)(tk2 - tk1);
+  tp[2] = (float)(tk3 - tk2);
+  tp[3] = (float)(2 * nt);                                  // in 32-wide k stages
+}
+#endif
 
 // Shared epilogue: wave tile 64x64 at (mw, nw); lane holds, per fragment (i,j), column m = ..+(lane&15) and rows
 // n = ..+4*(lane>>4)+{0..3} (the MFMA is issued with the W fragment as the A operand).
+// Pass 1 issues every load of the tile (bias, residual, gate) before pass 2 stores anything: the residual usually IS the
+// output buffer (x += ...), so with loads and stores interleaved per fragment hipcc must keep each load behind the previous
+// store and the tile's epilogue becomes 16 dependent HBM round trips; like this they are all in flight at once.
 template <int EPI>
 MMPL_DEV void gemm_epilogue(const GemmArgs& g, const f32x4 (&acc)[4][4], int mw, int nw, int frow, int fchunk) {
-  const int m0 = 0, n0 = 0, wm = 0, wn = 0;
-  (void)m0; (void)n0; (void)wm; (void)wn;
-  // ---- epilogue: lane holds, per fragment (i,j), column m = ..+(lane&15) and rows n = ..+4*(lane>>4)+{0..3}.
-  // Pass 1 issues every load of the tile (bias, residual, gate) before pass 2 stores anything: the residual usually IS the
-  // output buffer (x += ...), so with loads and stores interleaved per fragment hipcc must keep each load behind the previous
-  // store and the tile's epilogue becomes 16 dependent HBM round trips; like this they are all in flight at once.
   uint2 bias4[4], res4[4][4], gate4[4][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -77,13 +219,10 @@ MMPL_DEV void gemm_epilogue(const GemmArgs& g, const f32x4 (&acc)[4][4], int mw,
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(g.C) + (size_t)m * g.ldc + n) = o4;
         continue;
       }
-      float v[4];
-      {
-        const uint2 bb = bias4[j];
-        const float b[4] = {bf2f(bb.x & 0xffff), bf2f(bb.x >> 16), bf2f(bb.y & 0xffff), bf2f(bb.y >> 16)};
+      float v[4], b[4];
+      unpack4(bias4[j], b);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = rbf(acc[i][j][r] + b[r]);  // Linear output rounds to bf16
-      }
+      for (int r = 0; r < 4; ++r) v[r] = rbf(acc[i][j][r] + b[r]);  // Linear output rounds to bf16
       if (EPI == EPI_BIAS_GELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
@@ -91,11 +230,11 @@ MMPL_DEV void gemm_epilogue(const GemmArgs& g, const f32x4 (&acc)[4][4], int mw,
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = silu(v[r]);
       } else if (EPI == EPI_GATE_RES || EPI == EPI_RES) {
-        const uint2 xx = res4[i][j];
-        float x[4] = {bf2f(xx.x & 0xffff), bf2f(xx.x >> 16), bf2f(xx.y & 0xffff), bf2f(xx.y >> 16)};
+        float x[4];
+        unpack4(res4[i][j], x);
         if (EPI == EPI_GATE_RES) {
-          const uint2 ee = gate4[i][j];
-          float e[4] = {bf2f(ee.x & 0xffff), bf2f(ee.x >> 16), bf2f(ee.y & 0xffff), bf2f(ee.y >> 16)};
+          float e[4];
+          unpack4(gate4[i][j], e);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = rbf(v[r] * e[r]);  // y * e rounds, then x + (.) rounds
         }
@@ -133,7 +272,7 @@ MMPL_DEV void gemm128_tile(const GemmArgs& g, char* smem, int m0, int n0) {
     const int row = srow + 32 * j;
     a_ptr[j] = g.A + (size_t)min(m0 + row, g.M - 1) * g.lda + schunk * 8;
     w_ptr[j] = g.W + (size_t)min(n0 + row, g.N - 1) * g.ldw + schunk * 8;
-    lds_off[j] = row * 128 + ((schunk ^ (row & 7)) << 4);
+    lds_off[j] = swz64(row, schunk);
   }
   u32x4 ra[4], rw[4];
   const int nt = g.K / BK;
@@ -150,19 +289,15 @@ MMPL_DEV void gemm128_tile(const GemmArgs& g, char* smem, int m0, int n0) {
   __syncthreads();
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   // fragment read offsets (bytes within a tile): row = base + 16*i + (lane&15), 16-B chunk = 4*ks + (lane>>4)
   const int frow = lane & 15, fchunk = lane >> 4;
   int a_off[4], w_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int ar = 64 * wm + 16 * i + frow, wr = 64 * wn + 16 * i + frow;
-    a_off[i] = ar * 128 + ((fchunk ^ (ar & 7)) << 4);
-    w_off[i] = wr * 128 + ((fchunk ^ (wr & 7)) << 4);
+    a_off[i] = swz64(64 * wm + 16 * i + frow, fchunk);
+    w_off[i] = swz64(64 * wn + 16 * i + frow, fchunk);
   }
 
   for (int t = 0; t < nt; ++t) {
@@ -175,23 +310,8 @@ MMPL_DEV void gemm128_tile(const GemmArgs& g, char* smem, int m0, int n0) {
         rw[j] = *reinterpret_cast<const u32x4*>(w_ptr[j] + koff);
       }
     }
-    const char* Ac = As + cur * TILE_BYTES;
-    const char* Wc = Ws + cur * TILE_BYTES;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[4], wf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        // chunk index for k-step ks is (4*ks + fchunk); XOR with (row&7) commutes with adding 4*ks (bit 2)
-        af[i] = *reinterpret_cast<const bf16x8*>(Ac + (a_off[i] ^ (ks << 6)));
-        wf[i] = *reinterpret_cast<const bf16x8*>(Wc + (w_off[i] ^ (ks << 6)));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-    }
+    for (int ks = 0; ks < 2; ++ks) kstep4x4(acc, As + cur * TILE_BYTES, a_off, Ws + cur * TILE_BYTES, w_off, ks);
     if (t + 1 < nt) {
       char* An = As + (cur ^ 1) * TILE_BYTES;
       char* Wn = Ws + (cur ^ 1) * TILE_BYTES;
@@ -215,22 +335,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     g.C = (bf16_t*)((char*)g.C + (size_t)blockIdx.y * g.sC * (g.epi == EPI_F32_SCALE ? 4 : 2));
   }
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // ---- block -> tile mapping: XCD-aware (blocks b, b+8, ... share an L2) + grouped along M
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-  const int nwg = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective for any nwg
-  }
-  constexpr int GROUP = 8;
-  const int per_group = GROUP * tiles_n;
-  const int gid = bid / per_group;
-  const int first_m = gid * GROUP;
-  const int gsz = min(tiles_m - first_m, GROUP);
-  const int tm = first_m + (bid % per_group) % gsz;
-  const int tn = (bid % per_group) / gsz;
-  gemm128_tile<EPI>(g, smem, tm * BM, tn * BN);
+  const TileAt t = grouped_tile<8, BM, BN>(g.M, g.N);
+  gemm128_tile<EPI>(g, smem, t.tm * BM, t.tn * BN);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -250,21 +356,8 @@ MMPL_DEV void glds16(const void* g, char* lds) {
 template <int EPI>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_bf16_v2_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tiles_m = (g.M + BM2 - 1) / BM2, tiles_n = (g.N + BN2 - 1) / BN2;
-  const int nwg = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  constexpr int GROUP = 4;
-  const int per_group = GROUP * tiles_n;
-  const int gid = bid / per_group;
-  const int first_m = gid * GROUP;
-  const int gsz = min(tiles_m - first_m, GROUP);
-  const int tm = first_m + (bid % per_group) % gsz;
-  const int tn = (bid % per_group) / gsz;
-  const int m0 = tm * BM2, n0 = tn * BN2;
+  const TileAt tile = grouped_tile<4, BM2, BN2>(g.M, g.N);
+  const int m0 = tile.tm * BM2, n0 = tile.tn * BN2;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -293,17 +386,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int frow = lane & 15, fchunk = lane >> 4;
   int a_off[4], w_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int ar = 64 * wm + 16 * i + frow, wr = 64 * wn + 16 * i + frow;
-    a_off[i] = ar * 128 + ((fchunk ^ (ar & 7)) << 4);
-    w_off[i] = A2_BYTES + wr * 128 + ((fchunk ^ (wr & 7)) << 4);
+    a_off[i] = swz64(64 * wm + 16 * i + frow, fchunk);
+    w_off[i] = A2_BYTES + swz64(64 * wn + 16 * i + frow, fchunk);
   }
 
   const int nt = g.K / BK;
@@ -320,19 +409,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (t + 2 < nt) issue(t + 2);
     const char* st = smem + (t % NSTAGE2) * STAGE2;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[4], wf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[i] = *reinterpret_cast<const bf16x8*>(st + (a_off[i] ^ (ks << 6)));
-        wf[i] = *reinterpret_cast<const bf16x8*>(st + (w_off[i] ^ (ks << 6)));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-    }
+    for (int ks = 0; ks < 2; ++ks) kstep4x4(acc, st, a_off, st, w_off, ks);
     // tile t+1 must have landed (everything but the 6 newest DMA ops of this wave), then everyone syncs
     if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -341,67 +418,35 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   gemm_epilogue<EPI>(g, acc, m0 + 64 * wm, n0 + 64 * wn, frow, fchunk);
 }
 
-// (v3 -- 256x256x32 tile, 3-stage DMA ring, 990 TFLOP/s -- was removed once v4 / v6 superseded it; the tile constants stay)
-constexpr int BM3 = 256, BN3 = 256;
-
 // ---------------------------------------------------------------------------------------------------------------
-// (v4 -- the lock-step predecessor of v6: same tile and 2-stage ring, both wave groups reading then multiplying together,
-// 1070-1200 TFLOP/s -- was removed in round 2: unreachable in normal operation; its geometry constants stay)
-constexpr int BK4 = 64, A4_BYTES = BM3 * BK4 * 2, STAGE4 = 2 * A4_BYTES;
-MMPL_DEV int swz64(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
-
-// ---------------------------------------------------------------------------------------------------------------
-// v6 "ping-pong" (default for large problems): v4's tile (256x256x64, 8 waves 2x4, 2-stage LDS-DMA ring) with the two wave groups (waves 0-3 / 4-7:
-// waves w and w+4 share a SIMD) running half a k-tile apart.  Per k-tile a wave runs
+// v6 "ping-pong" (default for large problems): 256x256x64 tile, 8 waves 2x4, 2-stage LDS-DMA ring, with the two wave groups (waves 0-3 /
+// 4-7: waves w and w+4 share a SIMD) running half a k-tile apart.  Per k-tile a wave runs
 //   R_t = { request its 24 LDS fragments of tile t (+ group A: issue ALL 64 LDS-DMA ops of tile t+1) }
 //   M_t = { 64 MFMAs }
 // and while one group is in M the other is in R, so each SIMD's matrix pipe is fed by one wave while its partner's
-// LDS reads / DMA issue stalls happen in the shadow, instead of both waves reading, then both multiplying (the removed v4).
+// LDS reads / DMA issue stalls happen in the shadow, instead of both waves reading, then both multiplying (the lock-step form this
+// replaced: 1070-1200 TFLOP/s on the 14B/720p shapes against 1220-1290 here, measured in one process; 1310 vs 1415 at 8192^3).
 // A DMA op is global_load_lds_dwordx4 voff, s[base] with voff = (clamped row * ld + swizzled chunk) * 2: needs
-// M * lda * 2 and N * ldw * 2 < 4 GiB (checked by the launcher, else the 64-bit-addressed v2).  Same MFMA order as v4 was;
-// measured in one process on the 14B/720p shapes: +4 ... +14 % over v4 (1220-1290 vs 1070-1200 TFLOP/s, 1415 vs 1310
-// at 8192^3).  With the DMA ops removed the same kernel runs at 1450-1470: the LDS-DMA issue stalls (~100 cycles per
+// M * lda * 2 and N * ldw * 2 < 4 GiB (checked by the launcher, else the 64-bit-addressed v2).
+// With the DMA ops removed the same kernel runs at 1450-1470: the LDS-DMA issue stalls (~100 cycles per
 // op) are the remaining cost.  A BK = 32 / 4-deep-ring variant in which both groups issue their own DMA ops inside
 // their R segments was slower (twice the barriers: 1040-1150).
-// cache-policy modifier of the operand streams' LDS-DMA loads (dev_knobs.h GEMM_POLICY_A / _W; "" in every shipped build)
-#define GEMM_POL_STR_0 ""
-#define GEMM_POL_STR_1 " nt"
-#define GEMM_POL_STR_2 " sc1"
-#define GEMM_POL_STR_3 " sc0 sc1"
-#define GEMM_POL_CAT(n) GEMM_POL_STR_##n
-#define GEMM_POL_STR(n) GEMM_POL_CAT(n)
-#define GEMM_POL_A GEMM_POL_STR(GEMM_POLICY_A)
-#define GEMM_POL_W GEMM_POL_STR(GEMM_POLICY_W)
-MMPL_DEV void glds16s(const void* base, uint32_t voff, char* lds) {
-  const uint32_t dst = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)lds);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
-}
-MMPL_DEV void glds16s_a(const void* base, uint32_t voff, char* lds) {
-  const uint32_t dst = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)lds);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" GEMM_POL_A ::"v"(voff), "s"(base), "s"(dst) : "memory");
-}
-MMPL_DEV void glds16s_w(const void* base, uint32_t voff, char* lds) {
-  const uint32_t dst = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)lds);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" GEMM_POL_W ::"v"(voff), "s"(base), "s"(dst) : "memory");
+
+// LDS-DMA: every lane's BYTES (16 or 4) at base + voff go straight to LDS, lane-linear from LDS address `dst` (no destination VGPR;
+// counted by vmcnt).  The 4-byte form is the L2 prefetch of v6 / v8: one 64-byte half line per lane into a dump area nobody reads
+// (nothing to wait for in the loop; the issuing wave drains vmcnt before it leaves the kernel).
+MMPL_DEV uint32_t lds_addr(const char* lds) { return (uint32_t)(size_t)((__attribute__((address_space(3))) char*)lds); }
+template <int BYTES> MMPL_DEV void lds_dma(const void* base, uint32_t voff, uint32_t dst) {
+  static_assert(BYTES == 16 || BYTES == 4, "LDS-DMA width");
+  if constexpr (BYTES == 16) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
+  else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
 }
 
+// C store of the staged epilogue: non-temporal (against plain, sc1 and sc0 sc1: profiles/r03c_gemm6_store_policy_sweep.log,
+// r05c_gemm_store_policy_1p3B.log)
 MMPL_DEV void store16_c(void* p, const uint4& v) {
   const u32x4 w = {v.x, v.y, v.z, v.w};
-#if GEMM6_STORE == 1
   asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(p), "v"(w) : "memory");
-#elif GEMM6_STORE == 2
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(w) : "memory");
-#elif GEMM6_STORE == 3
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(w) : "memory");
-#else
-  *reinterpret_cast<u32x4*>(p) = w;
-#endif
-}
-// L2 prefetch of one 64-byte half line per lane: an LDS-DMA dword into a dump area nobody reads (no destination VGPR, nothing to
-// wait for in the loop; the issuing wave drains vmcnt before it leaves the kernel)
-MMPL_DEV void glds4s(const void* base, uint32_t voff, char* lds) {
-  const uint32_t dst = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)lds);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
 }
 
 // v6 epilogue, LDS-staged.  The MFMA leaves each lane with one token row and 4 consecutive output columns per fragment: stored
@@ -443,8 +488,7 @@ MMPL_DEV void epi_load_res(const GemmArgs& g, EpiIn& in, int mw, int nw, int lan
       if ((GEMM6_ABL & 16) && g.M >= 0) {                              // dev mock (results are garbage): no residual loads at all -- the upper
         in.res8[u] = uint4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};      // bound of what hiding them under the k loop can buy
       } else if (n_ok && m < g.M) {
-        const u32x4* rp = reinterpret_cast<const u32x4*>(g.res + (size_t)m * g.ldres + n);
-        const u32x4 rv = GEMM6_RESLD ? __builtin_nontemporal_load(rp) : *rp;
+        const u32x4 rv = *reinterpret_cast<const u32x4*>(g.res + (size_t)m * g.ldres + n);
         in.res8[u] = uint4{rv[0], rv[1], rv[2], rv[3]};
       } else {
         in.res8[u] = uint4{0u, 0u, 0u, 0u};
@@ -475,9 +519,8 @@ MMPL_DEV void epi_stage(const f32x4 (&acc)[2][4][4], const EpiIn& in, char* stg,
       const int row = 64 * h + 16 * i + frow;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float b[4] = {__uint_as_float(in.bias4[j].x << 16), __uint_as_float(in.bias4[j].x & 0xffff0000u),
-                            __uint_as_float(in.bias4[j].y << 16), __uint_as_float(in.bias4[j].y & 0xffff0000u)};
-        float v[4];
+        float b[4], v[4];
+        unpack4(in.bias4[j], b);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           v[r] = rbf(acc[h][i][j][r] + b[r]);                       // Linear output rounds to bf16
@@ -507,14 +550,14 @@ MMPL_DEV void epi_finish(const GemmArgs& g, const EpiIn& in, const char* stg, in
     if (HAS_RES) {
       uint4 ev = uint4{0u, 0u, 0u, 0u};
       if (EPI == EPI_GATE_RES) ev = (m < in.m_split) ? in.gate_lo : in.gate_hi;
-      const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w}, xw[4] = {in.res8[u].x, in.res8[u].y, in.res8[u].z, in.res8[u].w}, ew[4] = {ev.x, ev.y, ev.z, ev.w};
-      float v[8];
+      float y[8], x[8], gt[8], v[8];
+      unpack8(yv, y);
+      unpack8(in.res8[u], x);
+      unpack8(ev, gt);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float y = __uint_as_float((e & 1) ? (yw[e >> 1] & 0xffff0000u) : (yw[e >> 1] << 16));
-        const float x = __uint_as_float((e & 1) ? (xw[e >> 1] & 0xffff0000u) : (xw[e >> 1] << 16));
-        if (EPI == EPI_GATE_RES) y = rbf(y * __uint_as_float((e & 1) ? (ew[e >> 1] & 0xffff0000u) : (ew[e >> 1] << 16)));   // y * e rounds
-        v[e] = x + y;                                               // x + (.) rounds at the pack
+        if (EPI == EPI_GATE_RES) y[e] = rbf(y[e] * gt[e]);          // y * e rounds
+        v[e] = x[e] + y[e];                                         // x + (.) rounds at the pack
       }
       ov.x = pack2bf(v[0], v[1]); ov.y = pack2bf(v[2], v[3]); ov.z = pack2bf(v[4], v[5]); ov.w = pack2bf(v[6], v[7]);
     }
@@ -567,38 +610,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   extern __shared__ __attribute__((aligned(16))) char smem[];
   GEMM_DEV_TICKS;
   GEMM_DEV_TICK(tk0);
-  const int tiles_m = (g.M + BM3 - 1) / BM3, tiles_n = (g.N + BN3 - 1) / BN3;
-  const int nwg = tiles_m * tiles_n;
-  // Tile order: every XCD owns a list of tiles in grouped-M order (below), so that the blocks sharing one L2 work on neighbouring
-  // tiles.  Without a tile counter block b is entry b >> 3 of XCD b & 7's list (the hardware deals blocks round-robin to the
-  // XCDs).  With one (g.tile_counter) the kernel is launched once per CU and a block takes the next tile of ITS XCD's list when
-  // it is done with the previous one: equal tiles do not take equal time (blocks that are first to touch an
-  // operand panel wait on HBM, 33-42 cycles per MFMA across blocks), and a lock-step round lasts as long as its slowest block.
-  // Ticket protocol: exactly chunk + (blocks of the XCD) tickets are drawn per launch; whoever draws the last one knows every
-  // other block of the XCD is leaving and zeroes the counter for the next launch.
   __shared__ int s_ticket;
   const bool persistent = !SPLITK && g.tile_counter != nullptr;
   const int my_xcd = blockIdx.x & 7;
-  const int GROUP = g.group;
-  const int per_group = GROUP * tiles_n;
-  // Sweep-synchronous order (g.sync_sweeps): the M-groups (GROUP row panels x all column panels) are dealt to the XCDs like cards
-  // -- XCD x works through groups x, x + 8, x + 16, ... -- so all eight XCDs walk the column panels of W at the same time, a W
-  // panel comes out of HBM once per sweep and the other seven XCDs find it in the Infinity Cache.  With contiguous chunks of
-  // the tile list (the previous order) the XCDs sat at eight different column positions and W was streamed from HBM eight
-  // times over: 8.5 GB of fabric reads per qkv GEMM, 2.7 TB/s, every L2 miss an HBM miss.  What the deal leaves over (fewer than
-  // 8 full groups, a ragged last group) is split into eight contiguous chunks as before.
-  const int full_groups = tiles_m / GROUP;
-  const int rounds = g.sync_sweeps ? full_groups >> 3 : 0;
-  const int dealt = rounds * per_group;                              // tiles per XCD that come from dealt groups
-  const int left = nwg - 8 * dealt;                                  // tiles of the remainder list
-  const int lq = left >> 3, lr = left & 7;
-  const int chunk_all = dealt + lq + (my_xcd < lr ? 1 : 0);
-  const int chunk_main = g.splitk_s > 1 ? chunk_all - chunk_all % g.splitk_per : chunk_all;   // the tail belongs to the split-K launch
-  const int chunk = SPLITK ? chunk_all : chunk_main;
+  const XcdTileList list(g.M, g.N, g.group, g.sync_sweeps, my_xcd);
+  const int chunk_main = list.main_chunk(g.splitk_s, g.splitk_per);          // the rest belongs to the tail launch
+  const int chunk = SPLITK ? list.chunk_all : chunk_main;
   [[maybe_unused]] int part = 0, slot = 0;
   const int blocks_x = (int)(gridDim.x >> 3) + (my_xcd < (int)(gridDim.x & 7) ? 1 : 0);
   for (;;) {
-  int idx = blockIdx.x >> 3;                                         // index into THIS XCD's tile list (block b of a one-block-per-tile
+  int idx = blockIdx.x >> 3;                                         // index into THIS XCD's tile list
   if constexpr (SPLITK) {
     const int t_local = idx / g.splitk_s;
     part = idx - t_local * g.splitk_s;
@@ -606,40 +627,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     idx = chunk_main + t_local;
     if (idx >= chunk) return;
   }
-  if (persistent) {                                                  // launch runs on XCD b & 7: the hardware deals blocks round-robin)
-    if (threadIdx.x == 0) s_ticket = atomicAdd(g.tile_counter + my_xcd, 1);
-    __syncthreads();
-    const int ticket = s_ticket;
-    if (ticket >= chunk) {
-      if (ticket == chunk + blocks_x - 1 && threadIdx.x == 0) g.tile_counter[my_xcd] = 0;
-      return;
-    }
-    idx = ticket;
+  if (persistent) {
+    idx = draw_ticket(g.tile_counter, s_ticket, chunk, my_xcd, blocks_x);
+    if (idx < 0) return;
   }
-  int bid;                                                           // position in the grouped-M tile list
-  if (idx < dealt) {
-    bid = ((idx / per_group) * 8 + my_xcd) * per_group + idx % per_group;
-  } else {
-    bid = 8 * dealt + (my_xcd < lr ? my_xcd * (lq + 1) : lr * (lq + 1) + (my_xcd - lr) * lq) + (idx - dealt);
-  }
-  const int gid = bid / per_group;
-  const int first_m = gid * GROUP;
-  const int gsz = min(tiles_m - first_m, GROUP);
-  const int tm = first_m + (bid % per_group) % gsz;
-  const int tn = (bid % per_group) / gsz;
-  const int m0 = tm * BM3, n0 = tn * BN3;
+  const TileAt tile = list.tile(idx);
+  const int gsz = tile.gsz, tn = tile.tn;
+  const int m0 = tile.tm * BM256, n0 = tn * BN256;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3, grp = wave >> 2;
 
   // ---- DMA (group A only): wave w issues pieces 4q + w, q = 0..15 (q < 8: A rows 8*(4q+w).., q >= 8: W rows)
   const int prow = lane >> 3, lc = ((lane & 7) ^ (prow & 7)) << 3;   // row within the piece, swizzled source chunk (elements)
-  const int nt_all = g.K / BK4;
+  const int nt_all = g.K / BK;
   const int kt0 = SPLITK ? part * nt_all / g.splitk_s : 0;          // this block's k-tiles: [kt0, kt0 + nt)
   const int nt = SPLITK ? (part + 1) * nt_all / g.splitk_s - kt0 : nt_all;
-  const bf16_t* const A_k0 = g.A + (size_t)kt0 * BK4;
-  const bf16_t* const W_k0 = g.W + (size_t)kt0 * BK4;
-  const bf16_t* a_k = A_k0;                                        // advance by BK4 elements per tile
+  const bf16_t* const A_k0 = g.A + (size_t)kt0 * BK;
+  const bf16_t* const W_k0 = g.W + (size_t)kt0 * BK;
+  const bf16_t* a_k = A_k0;                                        // advance by BK elements per tile
   const bf16_t* w_k = W_k0;
   auto issue_piece = [&](int q, char* st) {
     const bool isw = q >= 8;
@@ -647,35 +653,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int row = isw ? min(n0 + 8 * p + prow, g.N - 1) : min(m0 + 8 * p + prow, g.M - 1);
     if constexpr (GEMM6_ABL & 1) row = 8 * p + prow;
     const uint32_t voff = (uint32_t)(row * (isw ? g.ldw : g.lda) + lc) * 2u;
-    if (isw) glds16s_w(w_k, voff, st + A4_BYTES + p * 1024);
-    else glds16s_a(a_k, voff, st + p * 1024);
+    lds_dma<16>(isw ? w_k : a_k, voff, lds_addr(st + (isw ? OPER256_BYTES : 0) + p * 1024));
   };
 
   f32x4 acc[2][4][4];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc[0]);
+  zero_acc(acc[1]);
   const int frow = lane & 15, fchunk = lane >> 4;
   int a_off[8], w_off[4];
 #pragma unroll
   for (int i = 0; i < 8; ++i) a_off[i] = swz64(128 * wm + 16 * i + frow, fchunk);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) w_off[i] = A4_BYTES + swz64(64 * wn + 16 * i + frow, fchunk);
+  for (int i = 0; i < 4; ++i) w_off[i] = OPER256_BYTES + swz64(64 * wn + 16 * i + frow, fchunk);
   // L2 prefetch shares (see the loop): wave-uniform scalars
   const bool pf_on = g.pf_dist > 0 && grp == 1 && gsz >= 2;
   const int pf_P = 32 / gsz;
   const int pf_nw = __builtin_amdgcn_readfirstlane(2 * (256 / gsz)), pf_na = __builtin_amdgcn_readfirstlane(2 * (256 / pf_P));
-  const int pf_wrow0 = __builtin_amdgcn_readfirstlane(n0 + ((bid % per_group) % gsz) * (256 / gsz));
+  const int pf_wrow0 = __builtin_amdgcn_readfirstlane(n0 + ((tile.bid % list.per_group) % gsz) * (256 / gsz));
   const int pf_arow0 = __builtin_amdgcn_readfirstlane(m0 + (tn % pf_P) * (256 / pf_P));
 
   if (grp == 0) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) issue_piece(q, smem);
-    a_k += BK4;
-    w_k += BK4;
+    a_k += BK;
+    w_k += BK;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __builtin_amdgcn_s_barrier();
@@ -692,13 +693,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // (tn % P) * 256 / P ... of A (P = 32 / gsz), two half lines (64 B) a row, one per lane.
     if (pf_on && t + g.pf_dist < nt) {
       const int l = (wave - 4) * 64 + lane;
-      char* dump = smem + 2 * STAGE4 + (wave - 4) * 256;
-      const size_t koff = (size_t)(t + g.pf_dist) * BK4;
-      if (l < pf_nw) glds4s(W_k0 + koff, (uint32_t)(min(pf_wrow0 + (l >> 1), g.N - 1) * g.ldw + (l & 1) * 32) * 2u, dump);
-      if (l < pf_na) glds4s(A_k0 + koff, (uint32_t)(min(pf_arow0 + (l >> 1), g.M - 1) * g.lda + (l & 1) * 32) * 2u, dump);
+      char* dump = smem + 2 * STAGE256 + (wave - 4) * 256;
+      const size_t koff = (size_t)(t + g.pf_dist) * BK;
+      if (l < pf_nw) lds_dma<4>(W_k0 + koff, (uint32_t)(min(pf_wrow0 + (l >> 1), g.N - 1) * g.ldw + (l & 1) * 32) * 2u, lds_addr(dump));
+      if (l < pf_na) lds_dma<4>(A_k0 + koff, (uint32_t)(min(pf_arow0 + (l >> 1), g.M - 1) * g.lda + (l & 1) * 32) * 2u, lds_addr(dump));
     }
-    const char* st = smem + (t & 1) * STAGE4;
-    char* nx = smem + ((t + 1) & 1) * STAGE4;
+    const char* st = smem + (t & 1) * STAGE256;
+    char* nx = smem + ((t + 1) & 1) * STAGE256;
     const bool do_issue = grp == 0 && t + 1 < nt && !(GEMM6_ABL & 4);
     bf16x8 af[2][8], wf[2][4];
 #pragma unroll
@@ -714,7 +715,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if ((i & 1) && do_issue) issue_piece(ks * 8 + 4 + (i >> 1), nx);
       }
     }
-    if (do_issue) { a_k += BK4; w_k += BK4; }
+    if (do_issue) { a_k += BK; w_k += BK; }
     // the fragments are complete HERE (hipcc would otherwise sink the reads next to their MFMAs, into the M segment)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -786,20 +787,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     gemm_epilogue<EPI>(g, acc[0], m0 + 128 * wm, n0 + 64 * wn, frow, fchunk);
     gemm_epilogue<EPI>(g, acc[1], m0 + 128 * wm + 64, n0 + 64 * wn, frow, fchunk);
   }
-#ifdef MMPL_DEV_ABLATIONS
-  if constexpr (GEMM6_TIMING) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    tk3 = __builtin_readcyclecounter();
-    __syncthreads();
-    if (lane == 0 && (wave & 1) == 0) {                      // 4 of the 8 waves: the layout tools/bench_kernels.py gemmphases reads
-      float* tp = reinterpret_cast<float*>(g.C) + (blockIdx.x * 4 + (wave >> 1)) * 4;
-      tp[0] = (float)(tk1 - tk0);
-      tp[1] = (float)(tk2 - tk1);
-      tp[2] = (float)(tk3 - tk2);
-      tp[3] = (float)(2 * nt);                                // in 32-wide k stages
-    }
-  }
-#endif
+  GEMM_DEV_DUMP(lane == 0 && (wave & 1) == 0, blockIdx.x * 4 + (wave >> 1), nt);      // 4 of the 8 waves
   if (g.pf_dist > 0 && grp == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // prefetch DMAs target this block's LDS
   if (!persistent) return;
   __syncthreads();                 // the ring (and s_ticket) are free again: every wave is done with its epilogue's staging
@@ -832,22 +820,18 @@ MMPL_DEV void gemm128_ring_tile(const GemmArgs& g, char* smem, int m0, int n0) {
     const bf16_t* ak = g.A + (size_t)t * BK;
     const bf16_t* wk = g.W + (size_t)t * BK;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) glds16s(ak, a_vo[q], st + (4 * q + wave) * 1024);
+    for (int q = 0; q < 4; ++q) lds_dma<16>(ak, a_vo[q], lds_addr(st + (4 * q + wave) * 1024));
 #pragma unroll
-    for (int q = 0; q < 4; ++q) glds16s(wk, w_vo[q], st + TILE_BYTES + (4 * q + wave) * 1024);
+    for (int q = 0; q < 4; ++q) lds_dma<16>(wk, w_vo[q], lds_addr(st + TILE_BYTES + (4 * q + wave) * 1024));
   };
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int frow = lane & 15, fchunk = lane >> 4;
   int a_off[4], w_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int ar = 64 * wm + 16 * i + frow, wr = 64 * wn + 16 * i + frow;
-    a_off[i] = ar * 128 + ((fchunk ^ (ar & 7)) << 4);
-    w_off[i] = TILE_BYTES + wr * 128 + ((fchunk ^ (wr & 7)) << 4);
+    a_off[i] = swz64(64 * wm + 16 * i + frow, fchunk);
+    w_off[i] = TILE_BYTES + swz64(64 * wn + 16 * i + frow, fchunk);
   }
   const int pre = nt < NST - 1 ? nt : NST - 1;
   for (int t = 0; t < pre; ++t) issue(t);
@@ -861,18 +845,7 @@ MMPL_DEV void gemm128_ring_tile(const GemmArgs& g, char* smem, int m0, int n0) {
     if (t + NST - 1 < nt) issue(t + NST - 1);                    // into the stage k-tile t - 1 left (everybody is past it: barrier below)
     const char* st = smem + (t & (NST - 1)) * STG;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[4], wf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[i] = *reinterpret_cast<const bf16x8*>(st + (a_off[i] ^ (ks << 6)));
-        wf[i] = *reinterpret_cast<const bf16x8*>(st + (w_off[i] ^ (ks << 6)));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-    }
+    for (int ks = 0; ks < 2; ++ks) kstep4x4(acc, st, a_off, st, w_off, ks);
     // k-tile t + 1 must have landed: tiles t + 2 and t + 3 (those that exist) may still be on their way
     const int later = (t + 3 < nt ? 1 : 0) + (t + 2 < nt ? 1 : 0);
     if (later == 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
@@ -894,23 +867,12 @@ MMPL_DEV void gemm128_ring_tile(const GemmArgs& g, char* smem, int m0, int n0) {
 template <int EPI, bool RING>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_tail128_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tiles_m = (g.M + BM3 - 1) / BM3, tiles_n = (g.N + BN3 - 1) / BN3;
-  const int nwg = tiles_m * tiles_n;
-  const int my_xcd = blockIdx.x & 7, r = blockIdx.x >> 3, t_local = r >> 2, quad = r & 3;
-  // the XCD's tile list, as in gemm_bf16_v6_kernel
-  const int GROUP = g.group, per_group = GROUP * tiles_n;
-  const int rounds = g.sync_sweeps ? (tiles_m / GROUP) >> 3 : 0;
-  const int dealt = rounds * per_group, left = nwg - 8 * dealt, lq = left >> 3, lr = left & 7;
-  const int chunk_all = dealt + lq + (my_xcd < lr ? 1 : 0);
-  const int idx = chunk_all - chunk_all % g.splitk_per + t_local;
-  if (idx >= chunk_all) return;
-  int bid;
-  if (idx < dealt) bid = ((idx / per_group) * 8 + my_xcd) * per_group + idx % per_group;
-  else bid = 8 * dealt + (my_xcd < lr ? my_xcd * (lq + 1) : lr * (lq + 1) + (my_xcd - lr) * lq) + (idx - dealt);
-  const int first_m = (bid / per_group) * GROUP;
-  const int gsz = min(tiles_m - first_m, GROUP);
-  const int tm = first_m + (bid % per_group) % gsz, tn = (bid % per_group) / gsz;
-  const int m0 = tm * BM3 + 128 * (quad >> 1), n0 = tn * BN3 + 128 * (quad & 1);
+  const int r = blockIdx.x >> 3, t_local = r >> 2, quad = r & 3;
+  const XcdTileList list(g.M, g.N, g.group, g.sync_sweeps, blockIdx.x & 7);
+  const int idx = list.main_chunk(g.splitk_s, g.splitk_per) + t_local;      // behind what the main launch computed
+  if (idx >= list.chunk_all) return;
+  const TileAt tile = list.tile(idx);
+  const int m0 = tile.tm * BM256 + 128 * (quad >> 1), n0 = tile.tn * BN256 + 128 * (quad & 1);
   if (m0 >= g.M || n0 >= g.N) return;
   if constexpr (RING) gemm128_ring_tile<EPI>(g, smem, m0, n0);
   else gemm128_tile<EPI>(g, smem, m0, n0);
@@ -953,19 +915,18 @@ struct G8 {
   template <int S, int Q> MMPL_DEV void dma() {              // piece Q of the next tile into stage S: Q < 8 activation rows, else weight rows
     if constexpr (GEMM8_ABL & 1) return;
     constexpr int q = Q & 7;
-    const uint32_t m = dst0 + S * STAGE4 + (Q < 8 ? 0 : A4_BYTES) + 4096 * q;
-    if constexpr (Q < 8) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" GEMM_POL_A ::"v"(a_vo[q]), "s"(a_k), "s"(m) : "memory");
-    else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" GEMM_POL_W ::"v"(w_vo[q]), "s"(w_k), "s"(m) : "memory");
+    if constexpr (Q < 8) lds_dma<16>(a_k, a_vo[q], dst0 + S * STAGE256 + 4096 * q);
+    else lds_dma<16>(w_k, w_vo[q], dst0 + S * STAGE256 + OPER256_BYTES + 4096 * q);
   }
   // v6's L2 prefetch of the tile's SHARE of its operand slices (see gemm_bf16_v6_kernel), one k-tile ahead of the ring's DMA: two
   // LDS-DMA dwords per wave into a dump area nobody reads.  ALWAYS two ops per wave and k-tile (lanes outside the share repeat
   // lane 0's address), so that the loop's counted vmcnt waits stay compile-time constants.
   MMPL_DEV void prefetch() {
     if constexpr (GEMM8_ABL & 1) return;
-    const bf16_t* pw = w_k + BK4 <= w_last ? w_k + BK4 : w_last;      // (past the last k-tile: that tile again, never past the row)
-    const bf16_t* pa = a_k + BK4 <= a_last ? a_k + BK4 : a_last;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(pf_wo), "s"(pw), "s"(pf_dump) : "memory");
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(pf_ao), "s"(pa), "s"(pf_dump + 256u) : "memory");
+    const bf16_t* pw = w_k + BK <= w_last ? w_k + BK : w_last;      // (past the last k-tile: that tile again, never past the row)
+    const bf16_t* pa = a_k + BK <= a_last ? a_k + BK : a_last;
+    lds_dma<4>(pw, pf_wo, pf_dump);
+    lds_dma<4>(pa, pf_ao, pf_dump + 256u);
   }
 };
 
@@ -1005,27 +966,17 @@ template <int S, bool ISSUE, bool NEXT, bool FIRST = false> MMPL_DEV void gemm8_
     if constexpr (NEXT && g > GEMM8_BAR2 && (g - GEMM8_BAR2) % GEMM8_RD == 0 && (g - GEMM8_BAR2) / GEMM8_RD <= 16)
       k.template lds<S ^ 1, 0, (g - GEMM8_BAR2) / GEMM8_RD - 1>();
   });
-  if constexpr (ISSUE) { k.a_k += BK4; k.w_k += BK4; }
+  if constexpr (ISSUE) { k.a_k += BK; k.w_k += BK; }
 }
 
 template <int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_bf16_v8_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_ticket;
-  const int tiles_m = (g.M + BM3 - 1) / BM3, tiles_n = (g.N + BN3 - 1) / BN3;
-  const int nwg = tiles_m * tiles_n;
-  // tile order, tickets and the split between the main launch and the split-K tail launch: exactly v6's (see gemm_bf16_v6_kernel)
   const bool persistent = g.tile_counter != nullptr;
   const int my_xcd = blockIdx.x & 7;
-  const int GROUP = g.group;
-  const int per_group = GROUP * tiles_n;
-  const int full_groups = tiles_m / GROUP;
-  const int rounds = g.sync_sweeps ? full_groups >> 3 : 0;
-  const int dealt = rounds * per_group;
-  const int left = nwg - 8 * dealt;
-  const int lq = left >> 3, lr = left & 7;
-  const int chunk_all = dealt + lq + (my_xcd < lr ? 1 : 0);
-  const int chunk = g.splitk_s > 1 ? chunk_all - chunk_all % g.splitk_per : chunk_all;
+  const XcdTileList list(g.M, g.N, g.group, g.sync_sweeps, my_xcd);
+  const int chunk = list.main_chunk(g.splitk_s, g.splitk_per);
   const int blocks_x = (int)(gridDim.x >> 3) + (my_xcd < (int)(gridDim.x & 7) ? 1 : 0);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1037,43 +988,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   G8 k;
   {
-    const uint32_t ring = (uint32_t)(size_t)((__attribute__((address_space(3))) char*)smem);
+    const uint32_t ring = lds_addr(smem);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        k.ra[s][ks] = ring + s * STAGE4 + (swz64(128 * wm + frow, fchunk) ^ (ks << 6));
-        k.rw[s][ks] = ring + s * STAGE4 + A4_BYTES + (swz64(128 * wn + frow, fchunk) ^ (ks << 6));
+        k.ra[s][ks] = ring + s * STAGE256 + (swz64(128 * wm + frow, fchunk) ^ (ks << 6));
+        k.rw[s][ks] = ring + s * STAGE256 + OPER256_BYTES + (swz64(128 * wn + frow, fchunk) ^ (ks << 6));
       }
     k.dst0 = ring + 1024 * wave;
-    k.pf_dump = ring + 2 * STAGE4 + 512 * wave;
+    k.pf_dump = ring + 2 * STAGE256 + 512 * wave;
   }
   const int prow = lane >> 3, lc = ((lane & 7) ^ (prow & 7)) << 3;     // row within a piece, swizzled source chunk (elements)
-  const int nt = g.K / BK4;
+  const int nt = g.K / BK;
 
   for (;;) {
     int idx = blockIdx.x >> 3;
     if (persistent) {
-      if (threadIdx.x == 0) s_ticket = atomicAdd(g.tile_counter + my_xcd, 1);
-      __syncthreads();
-      const int ticket = s_ticket;
-      if (ticket >= chunk) {
-        if (ticket == chunk + blocks_x - 1 && threadIdx.x == 0) g.tile_counter[my_xcd] = 0;
-        return;
-      }
-      idx = ticket;
+      idx = draw_ticket(g.tile_counter, s_ticket, chunk, my_xcd, blocks_x);
+      if (idx < 0) return;
     } else if (idx >= chunk) {
       return;
     }
-    int bid;
-    if (idx < dealt) bid = ((idx / per_group) * 8 + my_xcd) * per_group + idx % per_group;
-    else bid = 8 * dealt + (my_xcd < lr ? my_xcd * (lq + 1) : lr * (lq + 1) + (my_xcd - lr) * lq) + (idx - dealt);
-    const int gid = bid / per_group;
-    const int first_m = gid * GROUP;
-    const int gsz = min(tiles_m - first_m, GROUP);
-    const int tm = first_m + (bid % per_group) % gsz;
-    const int tn = (bid % per_group) / gsz;
-    const int m0 = tm * BM3, n0 = tn * BN3;
+    const TileAt tile = list.tile(idx);
+    const int m0 = tile.tm * BM256, n0 = tile.tn * BN256;
 
     // piece p = 4 q + wave of an operand's 32: rows 8 p .. 8 p + 7 (clamped at the matrix edge; the epilogue never stores those rows)
 #pragma unroll
@@ -1083,14 +1021,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       k.w_vo[q] = (uint32_t)(min(n0 + 8 * p + prow, g.N - 1) * g.ldw + lc) * 2u;
     }
     k.a_k = g.A; k.w_k = g.W;
-    k.a_last = g.A + (size_t)(nt - 1) * BK4; k.w_last = g.W + (size_t)(nt - 1) * BK4;
+    k.a_last = g.A + (size_t)(nt - 1) * BK; k.w_last = g.W + (size_t)(nt - 1) * BK;
     if constexpr (GEMM8_PF) {
       // the share of this tile: rows tm_l * 256 / gsz ... of its W panel (the gsz tiles of a column panel split it), rows
       // (tn % P) * 256 / P ... of its A panel (P = 32 / gsz tiles of a row panel in flight on the XCD); one 64-byte half line per
       // lane, 256 lanes of the block = wave * 64 + lane; lanes past a share repeat its first line.  g.pf_dist == 0: own first rows.
-      const int P = 32 / gsz, nw = 2 * (256 / gsz), na = 2 * (256 / P);
+      const int gsz = tile.gsz, P = 32 / gsz, nw = 2 * (256 / gsz), na = 2 * (256 / P);
       const int l = wave * 64 + lane;
-      const int wrow0 = n0 + ((bid % per_group) % gsz) * (256 / gsz), arow0 = m0 + (tn % P) * (256 / P);
+      const int wrow0 = n0 + ((tile.bid % list.per_group) % gsz) * (256 / gsz), arow0 = m0 + (tile.tn % P) * (256 / P);
       const int lw = (g.pf_dist > 0 && l < nw) ? l : 0, la = (g.pf_dist > 0 && l < na) ? l : 0;
       k.pf_wo = (uint32_t)(min(wrow0 + (lw >> 1), g.N - 1) * g.ldw + (lw & 1) * 32) * 2u;
       k.pf_ao = (uint32_t)(min(arow0 + (la >> 1), g.M - 1) * g.lda + (la & 1) * 32) * 2u;
@@ -1100,11 +1038,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     // ---- prologue: tiles 0 and 1 into the two stages, tile 0's first-half fragments into registers
     sfor<16>([&k](auto q) { k.template dma<0, decltype(q)::value>(); });
-    k.a_k += BK4; k.w_k += BK4;
+    k.a_k += BK; k.w_k += BK;
     if (nt > 1) {
       sfor<16>([&k](auto q) { k.template dma<1, decltype(q)::value>(); });
       if constexpr (GEMM8_PF) k.prefetch();                          // (same queue pattern as a loop iteration: 16 pieces, 2 prefetch ops)
-      k.a_k += BK4; k.w_k += BK4;
+      k.a_k += BK; k.w_k += BK;
       asm volatile("s_waitcnt vmcnt(%c0)\n\ts_barrier" ::"i"(GEMM8_PF ? 18 : 16) : "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1190,20 +1128,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         gemm_epilogue<EPI>(g, acc[1], mw + 64, nw0 + 64 * nh, frow_e, fchunk_e);
       });
     }
-#ifdef MMPL_DEV_ABLATIONS
-    if constexpr (GEMM6_TIMING) {      // per-wave { prologue, k loop, epilogue } shader cycles over the output (tools/bench_kernels.py gemmphases)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      tk3 = __builtin_readcyclecounter();
-      __syncthreads();
-      if (lane == 0) {
-        float* tp = reinterpret_cast<float*>(g.C) + (blockIdx.x * 4 + wave) * 4;
-        tp[0] = (float)(tk1 - tk0);
-        tp[1] = (float)(tk2 - tk1);
-        tp[2] = (float)(tk3 - tk2);
-        tp[3] = (float)(2 * nt);
-      }
-    }
-#endif
+    GEMM_DEV_DUMP(lane == 0, blockIdx.x * 4 + wave, nt);
     if (!persistent) return;
     __syncthreads();                 // the ring (and s_ticket) are free again
   }
@@ -1214,12 +1139,13 @@ constexpr int GEMM_SYNC_SWEEPS = 1;   // GemmArgs.sync_sweeps of every v6 / v8 l
 // The launchers below decide nothing: which kernel, which tail, how many blocks, which epilogue form all come from the GemmPlan.
 template <int EPI>
 hipError_t launch_v6(const GemmArgs& g, const GemmPlan& p, hipStream_t s) {
-  constexpr int smem = 2 * STAGE4 + 1024;        // ring + the L2 prefetch's dump area
-  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v6_kernel<EPI>), smem); e != hipSuccess) return e;
-  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v6_kernel<EPI, true>), smem); e != hipSuccess) return e;
-  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_bf16_v8_kernel<EPI>), 2 * STAGE4 + 2048); e != hipSuccess) return e;
-  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_tail128_kernel<EPI, true>), 8 * TILE_BYTES); e != hipSuccess) return e;
-  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(gemm_tail128_kernel<EPI, false>), 4 * TILE_BYTES); e != hipSuccess) return e;
+  constexpr int smem = 2 * STAGE256 + 1024, smem8 = 2 * STAGE256 + 2048;        // ring + the L2 prefetch's dump area
+  const struct { const void* kernel; int smem; } dyn[] = {
+      {reinterpret_cast<const void*>(gemm_bf16_v6_kernel<EPI>), smem},        {reinterpret_cast<const void*>(gemm_bf16_v6_kernel<EPI, true>), smem},
+      {reinterpret_cast<const void*>(gemm_bf16_v8_kernel<EPI>), smem8},       {reinterpret_cast<const void*>(gemm_tail128_kernel<EPI, true>), 8 * TILE_BYTES},
+      {reinterpret_cast<const void*>(gemm_tail128_kernel<EPI, false>), 4 * TILE_BYTES}};
+  for (const auto& d : dyn)
+    if (hipError_t e = mmpl_dyn_smem_once(d.kernel, d.smem); e != hipSuccess) return e;
   GemmArgs g2 = g;
   g2.group = p.group;
   g2.staged_epilogue = p.staged_epilogue;
@@ -1233,7 +1159,7 @@ hipError_t launch_v6(const GemmArgs& g, const GemmPlan& p, hipStream_t s) {
   g2.splitk_per = p.cus_per_xcd;
   if (!p.tickets) g2.tile_counter = nullptr;                  // one round or less: nothing to balance
   if (p.main_blocks > 0) {
-    if (p.kernel == GEMM_KERNEL_V8) hipLaunchKernelGGL(gemm_bf16_v8_kernel<EPI>, dim3(p.main_blocks), dim3(256), 2 * STAGE4 + 2048, s, g2);
+    if (p.kernel == GEMM_KERNEL_V8) hipLaunchKernelGGL(gemm_bf16_v8_kernel<EPI>, dim3(p.main_blocks), dim3(256), smem8, s, g2);
     else hipLaunchKernelGGL(gemm_bf16_v6_kernel<EPI>, dim3(p.main_blocks), dim3(512), smem, s, g2);
   }
   if (p.tail == GEMM_TAIL_SPLITK) hipLaunchKernelGGL((gemm_bf16_v6_kernel<EPI, true>), dim3(p.tail_blocks), dim3(512), smem, s, g2);
@@ -1270,7 +1196,7 @@ GemmPlan plan_v6(const GemmArgs& g) {
   const int env_v8 = rc.gemm_v8;
   const bool use_v8 = env_v8 >= 0 ? env_v8 != 0 : g.N >= 8192;       // the wide GEMMs (qkv, ffn0): profiles/r04c_gemm_v8_*.log
   p.kernel = use_v8 ? GEMM_KERNEL_V8 : GEMM_KERNEL_V6;
-  const int tiles_m = (g.M + BM3 - 1) / BM3, tiles_n = (g.N + BN3 - 1) / BN3, tiles = tiles_m * tiles_n;
+  const int tiles_m = (g.M + BM256 - 1) / BM256, tiles_n = (g.N + BN256 - 1) / BN256, tiles = tiles_m * tiles_n;
   // M-tile group of the block order (how many row panels the tiles in flight on an XCD span).  Round 3 swept it on the kernels of the
   // time (profiles/r03d_*, r03C_*) and gave the narrow (N < 8192) GEMMs groups of 3 (2 for the long-K one) where the row panels divide
   // by 3; re-swept in round 6 on today's kernels (staged epilogue in phases, split-K tail; profiles/r06w_gemm_group_sweep_v6_shapes.log,
@@ -1298,16 +1224,15 @@ GemmPlan plan_v6(const GemmArgs& g) {
   p.cus_per_xcd = per;
   p.splitk_s = 1;
   if (g.tile_counter && !rc.gemm_no_splitk && g.epi != EPI_F32_SCALE) {
-    // every XCD's leftover = its list length mod the CUs of an XCD, same arithmetic as the kernels
-    const int per_group = p.group * tiles_n;
-    const int dealt = GEMM_SYNC_SWEEPS ? ((tiles_m / p.group) >> 3) * per_group : 0, left = tiles - 8 * dealt;
+    // every XCD's leftover = what a main launch that stops at the full rounds (splitk_s > 1) leaves of its list
     int tb = 0, main_tiles = 0;
     for (int x = 0; x < 8; ++x) {
-      const int chunk = dealt + (left >> 3) + (x < (left & 7) ? 1 : 0);
-      tb = chunk % per > tb ? chunk % per : tb;
-      main_tiles += chunk - chunk % per;
+      const XcdTileList list(g.M, g.N, p.group, GEMM_SYNC_SWEEPS, x);
+      const int main = list.main_chunk(2, per);
+      tb = list.chunk_all - main > tb ? list.chunk_all - main : tb;
+      main_tiles += main;
     }
-    if (g.K / BK4 >= 64) {
+    if (g.K / BK >= 64) {
       // Split-K launch for the partial last round.  With one tile per CU a GEMM of R * 256 + t tiles takes R + 1 rounds however small t
       // is (Wan 1.3B at 480p: 43 x 6 = 258 tiles for o / ffn2 at s1, 78 at s0; 14B / 720p s0: 580).  When every XCD's leftover fits one
       // round in s >= 2 parts, the main launch stops at the full rounds and the leftover tiles run as s blocks each over 1/s of K.
@@ -1317,7 +1242,7 @@ GemmPlan plan_v6(const GemmArgs& g) {
       // profiles/r03S_gemm_splitk_micro.log).  Needs the tile tickets and the scratch.
       int sp = tb > 0 ? per / tb : 1;
       sp = sp > 4 ? 4 : sp;
-      if (g.splitk_ws && g.splitk_cnt && sp >= 2 && (size_t)8 * tb * sp * (BM3 * BN3 * sizeof(float)) <= mmpl_gemm_splitk_ws_bytes()) {
+      if (g.splitk_ws && g.splitk_cnt && sp >= 2 && (size_t)8 * tb * sp * (BM256 * BN256 * sizeof(float)) <= mmpl_gemm_splitk_ws_bytes()) {
         p.tail = GEMM_TAIL_SPLITK; p.splitk_s = sp; p.tail_blocks = 8 * tb * sp;
       }
     } else if (!rc.gemm_no_subtile && tb > 0 && 2 * tb <= per) {
@@ -1362,7 +1287,7 @@ GemmPlan mmpl_gemm_plan(const GemmArgs& g) {
   return p;
 }
 
-size_t mmpl_gemm_splitk_ws_bytes() { return (size_t)256 * BM3 * BN3 * sizeof(float); }   // <= one part per CU
+size_t mmpl_gemm_splitk_ws_bytes() { return (size_t)256 * BM256 * BN256 * sizeof(float); }   // <= one part per CU
 
 hipError_t mmpl_launch_gemm(const GemmArgs& g, hipStream_t s) {
   if (g.M <= 0 || g.N <= 0) return hipSuccess;
