@@ -305,6 +305,59 @@ int mmpl_cfg_dpmpp_step_table(const void* flow_cond, const void* flow_uncond, vo
                               const MmplDpmppStep* table_dev, int* step_dev, float* timestep_dev,
                               const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream);
 
+/* The float32 latent chain of upstream Wan2.1 sampling (wan/text2video.py:182-250, wan/image2video.py:198-329): the latents, the CFG
+ * combine and every tensor operation of the multistep solver stay in float32; only the flows are bf16 (the forward's output) and
+ * only the forward's input is rounded to bf16 (x_bf16, what autocast does to the latents at the patch embedding).
+ * Per element of n values, every operation below is ONE IEEE fp32 operation (round to nearest even), in the order of the reference's
+ * tensor expressions; the device code is compiled with `#pragma clang fp contract(off)` and plain operators, so nothing is contracted
+ * into an FMA and `/` is the correctly rounded division.  fc, fu: the bf16 flows widened (exact).
+ *   f      = fu + guidance * (fc - fu)                                      (fc when flow_uncond is NULL)
+ *   m_conv = x - sigma_cur * f
+ * UniPC (fm_solvers_unipc.py:486-626, 350-484; order <= 2, bh2, predict_x0), `last` = last_sample:
+ *   corrector, if use_corrector:
+ *     xt_ = c_c1 * last - c_c2 * m0;   d1t = m_conv - m0
+ *     corr_order 1:  acc = 0 + c_rho_last * d1t
+ *     corr_order 2:  acc = c_rho0 * ((m1 - m0) / c_rk) + c_rho_last * d1t
+ *     x   = xt_ - c_c3 * acc
+ *   m1 <- m0;  m0 <- m_conv;  last <- x
+ *   predictor:
+ *     xt_ = p_c1 * x - p_c2 * m0
+ *     pred_order 1:  x <- xt_ - p_c3 * 0
+ *     pred_order 2:  x <- xt_ - p_c3 * (0.5 * ((m1 - m0) / p_rk))
+ * DPM-Solver++(2M) (fm_solvers.py:706-797, midpoint), MmplDpmppStep as it is:
+ *   m1 <- m0;  m0 <- m_conv
+ *   order 1:  x <- c1 * x - c2 * m0
+ *   order 2:  x <- (c1 * x - c2 * m0) - (0.5 * c2) * (inv_r0 * (m0 - m1))          (the reference multiplies by 1.0 / r0)
+ * then x_bf16 <- bf16(x), round to nearest even, unless x_bf16 is NULL.
+ * UniPC DIVIDES by rk where the reference divides, and the rhos are float32 (not rounded to bf16): MmplUniPCStepF32 carries c_rk /
+ * p_rk (unused, any non-zero value, where the order is 1).  The scalars are finite on every step (mmpl_amd/scheduler.py computes
+ * them).  Denormal inputs, scalars or intermediate results are outside the contract. */
+typedef struct MmplUniPCStepF32 {
+  float guidance, sigma_cur;
+  int use_corrector, corr_order;
+  float c_c1, c_c2, c_c3, c_rk, c_rho0, c_rho_last;
+  int pred_order;
+  float p_c1, p_c2, p_c3, p_rk;
+} MmplUniPCStepF32;
+/* flow_cond, flow_uncond: dev bf16 [n] (flow_uncond NULL = flow_cond is already the combined flow); x, m0, m1, last_sample: dev
+ * float32 [n], updated in place, 4-byte aligned; x_bf16: dev bf16 [n] out or NULL.  Rejected before any launch: a NULL among
+ * flow_cond / x / m0 / m1 / last_sample / s, a float pointer that is not 4-byte aligned, an order outside 1..2.  16 bytes per lane
+ * when every pointer is 16-byte aligned, element-wise otherwise.  No allocation, no host read: capturable. */
+int mmpl_cfg_unipc_step_f32(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
+                            void* x_bf16, size_t n, const MmplUniPCStepF32* s, mmpl_stream_t stream);
+int mmpl_cfg_dpmpp_step_f32(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* x_bf16, size_t n,
+                            const MmplDpmppStep* s, mmpl_stream_t stream);
+/* Device-resident forms, the protocol of mmpl_cfg_unipc_step_table: the scalars of step *step_dev are read from
+ * table_dev[*step_dev] (n_steps entries, device memory), then *step_dev += 1 and the next step's timestep
+ * (timestep_table_dev[*step_dev]) is written to timestep_dev[0..n_timestep).  Once *step_dev has reached n_steps a launch changes
+ * nothing, x_bf16 included.  Also rejected: a NULL table / counter / timestep pointer, n_steps < 1, n_timestep < 0. */
+int mmpl_cfg_unipc_step_f32_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
+                                  void* x_bf16, size_t n, const MmplUniPCStepF32* table_dev, int* step_dev, float* timestep_dev,
+                                  const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream);
+int mmpl_cfg_dpmpp_step_f32_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* x_bf16, size_t n,
+                                  const MmplDpmppStep* table_dev, int* step_dev, float* timestep_dev,
+                                  const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream);
+
 /* Few-step (Self-Forcing / CausVid) latent update of CausalInferencePipeline.inference (pipeline/causal_inference.py:176-197):
  * WanDiffusionWrapper._convert_flow_pred_to_x0 (utils/wan_wrapper.py:172-199) then FlowMatchScheduler.add_noise
  * (utils/scheduler.py:160-176), per element of n bf16 values:

@@ -8,7 +8,8 @@ Single process = the reference's sequential rollout (chunk k+1 starts from the l
 `Wan_fps_inference_1gpu.py:164-203`); several processes = the parallel scripts' wavefront (chunk c on rank c mod W,
 anchors handed over right after the anchor stage).  `--bidirectional` = plain Wan2.1 T2V instead: one whole clip per call
 (the reference's Bidirectional*InferencePipeline); with `--i2v --i2v_model --image FILE` the Wan2.1-I2V model type sampled the
-same way (upstream WanI2V.generate).  `--synthetic` runs without checkpoints (seeded weights and text
+same way (upstream WanI2V.generate's forward; `--fp32_latents` = upstream's float32 latent chain instead of the reference
+pipeline's bf16 one).  `--synthetic` runs without checkpoints (seeded weights and text
 embeddings) -- the only mode that can run in this repo's test environments.  Output: per prompt a uint8 tensor
 `[T, H, W, 3]` saved with torch.save (mp4 muxing via torchvision is outside the hot path; fps = 16).
 """
@@ -138,6 +139,20 @@ def solver_refusal(args, fewstep: bool):
     return None
 
 
+def fp32_refusal(args, fewstep: bool):
+    """Why --fp32_latents cannot run this command line (None = it can, or it was not asked for): upstream Wan2.1's float32 latent
+    chain (WanT2V.generate / WanI2V.generate) belongs to the whole-clip multistep sampler alone."""
+    if not getattr(args, "fp32_latents", False):
+        return None
+    if not getattr(args, "bidirectional", False):
+        return ("--fp32_latents: the float32 latent chain is upstream WanT2V.generate / WanI2V.generate's, the whole-clip sampler; "
+                "add --bidirectional (the causal FPS pipeline keeps the reference's bf16 latents)")
+    if fewstep:
+        return ("--fp32_latents: the few-step pipeline (config with denoising_step_list) has no multistep solver and keeps its "
+                "reference's bf16 latents; use a 50-step config")
+    return None
+
+
 def read_clip(path: str) -> torch.Tensor:
     """A clip as this CLI writes it -> uint8 [T, H, W, 3] on the host: the ``.pt`` tensor, or the MJPEG ``.avi`` of
     utils/video_io.py."""
@@ -204,6 +219,7 @@ def first_refusal(args, world: int, fewstep: bool):
     num_frame_per_block, kv_window and pixel_hw on ``args``."""
     checks = (lambda: bidirectional_refusal(args, world), lambda: stream_refusal(args, fewstep), lambda: preview_refusal(args),
               lambda: rolling_refusal(args, fewstep), lambda: solver_refusal(args, fewstep),
+              lambda: fp32_refusal(args, fewstep),
               lambda: fewstep_refusal(args, world) if fewstep and not args.bidirectional else None,
               lambda: extend_refusal(args, fewstep))
     return next((why for why in (check() for check in checks) if why is not None), None)
@@ -341,6 +357,10 @@ def main(argv=None):
     ap.add_argument("--sample_solver", default="unipc", choices=["unipc", "dpm++"],
                     help="the multistep solver of the 50-step pipeline: FlowUniPCMultistepScheduler or FlowDPMSolverMultistepScheduler "
                          "(DPM-Solver++(2M)), as in Wan2.1's generate.py")
+    ap.add_argument("--fp32_latents", action="store_true",
+                    help="--bidirectional with a 50-step config (T2V, or --i2v --i2v_model): upstream WanT2V.generate / WanI2V.generate's "
+                         "latent chain -- float32 noise, latents, CFG combine and solver, only the DiT's input rounded to bf16 -- instead "
+                         "of the reference pipeline's bf16 chain")
     ap.add_argument("--latent_hw", type=int, nargs=2, default=None, help="override the latent size (tests)")
     ap.add_argument("--cfg_split", action="store_true",
                     help="multi-GPU: WORLD/2 chunk lanes x (cond, uncond) rank pairs -- the reference's device_cond/device_uncond "
@@ -359,9 +379,11 @@ def main(argv=None):
                          "--duration N generates N * num_output_frames latent frames in ONE call, with --stream as well")
     ap.add_argument("--bidirectional", action="store_true",
                     help="plain (non-causal) Wan2.1 T2V: the whole --num_output_frames clip per forward, every frame attending to "
-                         "every frame -- BidirectionalDiffusionInferencePipeline (--sampling_steps CFG steps of --sample_solver), or "
+                         "every frame -- BidirectionalDiffusionInferencePipeline (--sampling_steps CFG steps of --sample_solver on the "
+                         "reference's bf16 latent chain, or on upstream generate.py's float32 one with --fp32_latents), or "
                          "BidirectionalInferencePipeline for a few-step config (one with denoising_step_list).  With --i2v --i2v_model "
-                         "--image FILE: the Wan2.1-I2V-14B-480P / -720P model type sampled the same way (WanI2V.generate)")
+                         "--image FILE: the Wan2.1-I2V-14B-480P / -720P model type sampled the same way (WanI2V.generate's forward and "
+                         "defaults; its float32 latent chain too with --fp32_latents)")
     ap.add_argument("--local_attn_size", type=int, default=None, help="few-step configs: override model_kwargs.local_attn_size "
                     "(the KV window in latent frames; -1 = 21)")
     ap.add_argument("--sink_size", type=int, default=None, help="few-step configs: override model_kwargs.sink_size (the first "
@@ -549,6 +571,8 @@ def build_bidirectional_pipeline(config, args, dev, geo, mcfg):
     if not is_fewstep(config):
         pipe.sampling_steps = args.sampling_steps
         pipe.sample_solver = args.sample_solver
+        if getattr(args, "fp32_latents", False):
+            pipe.latent_dtype = torch.float32
         if getattr(args, "sample_shift", None) is not None:
             pipe.shift = float(args.sample_shift)
     return pipe
@@ -566,7 +590,7 @@ def _main_bidirectional(config, args, dev, geo, mcfg):
         extra["image_condition"] = build_image_condition(pipe.vae, pipe.clip, _load_image(args.image, geo, dev), args.num_output_frames)
     for idx, prompt in enumerate(_prompts(args)):
         g = torch.Generator(device="cpu").manual_seed(args.seed)
-        noise = torch.randn(shape, generator=g).to(torch.bfloat16)
+        noise = torch.randn(shape, generator=g).to(getattr(pipe, "latent_dtype", torch.bfloat16))      # (--fp32_latents: as drawn)
         torch.manual_seed(args.seed)                         # the few-step re-noise draws: the device generator
         _save_clip(_to_u8(pipe.inference(noise.to(dev), [prompt], **extra)), args, idx, "bidirectional ")
 

@@ -833,4 +833,72 @@ int mmpl_cfg_unipc_step_table(const void* flow_cond, const void* flow_uncond, vo
   return 0;
 }
 
+// ---- the float32 latent chain (fp32_chain.hip): argument checks here, before the first launch
+static int f32_chain_ptrs(const char* where, F32ChainPtrs& a, const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1,
+                          void* last_sample, bool need_last, void* x_bf16, size_t n) {
+  if (!flow_cond || !x || !m0 || !m1 || (need_last && !last_sample)) return fail(where, "null argument");
+  const uintptr_t fl = (uintptr_t)x | (uintptr_t)m0 | (uintptr_t)m1 | (uintptr_t)last_sample;
+  if (fl & 3) return fail(where, "x, m0, m1 and last_sample are float32: 4-byte aligned");
+  if (((uintptr_t)flow_cond | (uintptr_t)flow_uncond | (uintptr_t)x_bf16) & 1) return fail(where, "bf16 pointers are 2-byte aligned");
+  a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.x = (float*)x; a.m0 = (float*)m0; a.m1 = (float*)m1;
+  a.last = (float*)last_sample; a.x_bf16 = (bf16_t*)x_bf16; a.n = n;
+  return 0;
+}
+static int f32_table_args(const char* where, const void* table_dev, const int* step_dev, const float* timestep_dev,
+                          const float* timestep_table_dev, int n_timestep, int n_steps) {
+  if (!table_dev || !step_dev || !timestep_dev || !timestep_table_dev) return fail(where, "null argument");
+  if (n_steps < 1) return fail(where, "n_steps < 1");
+  if (n_timestep < 0) return fail(where, "n_timestep < 0");
+  return 0;
+}
+
+int mmpl_cfg_unipc_step_f32(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
+                            void* x_bf16, size_t n, const MmplUniPCStepF32* st, mmpl_stream_t stream) {
+  const char* where = "mmpl_cfg_unipc_step_f32";
+  if (!st) return fail(where, "null step");
+  F32ChainPtrs a = {};
+  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, last_sample, true, x_bf16, n)) return 1;
+  if (st->pred_order != 1 && st->pred_order != 2) return fail(where, "pred_order must be 1 or 2");
+  if (st->use_corrector && st->corr_order != 1 && st->corr_order != 2) return fail(where, "corr_order must be 1 or 2");
+  ProfScope ps(K_UNIPC, 0, (hipStream_t)stream);
+  MMPL_HIP_TRY(mmpl_launch_unipc_f32(a, st, (hipStream_t)stream), where);
+  return 0;
+}
+
+int mmpl_cfg_dpmpp_step_f32(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* x_bf16, size_t n,
+                            const MmplDpmppStep* st, mmpl_stream_t stream) {
+  const char* where = "mmpl_cfg_dpmpp_step_f32";
+  if (!st) return fail(where, "null step");
+  F32ChainPtrs a = {};
+  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, nullptr, false, x_bf16, n)) return 1;
+  if (st->order != 1 && st->order != 2) return fail(where, "order must be 1 or 2");
+  ProfScope ps(K_UNIPC, 0, (hipStream_t)stream);
+  MMPL_HIP_TRY(mmpl_launch_dpmpp_f32(a, st, (hipStream_t)stream), where);
+  return 0;
+}
+
+int mmpl_cfg_unipc_step_f32_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
+                                  void* x_bf16, size_t n, const MmplUniPCStepF32* table_dev, int* step_dev, float* timestep_dev,
+                                  const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream) {
+  const char* where = "mmpl_cfg_unipc_step_f32_table";
+  if (f32_table_args(where, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps)) return 1;
+  F32ChainPtrs a = {};
+  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, last_sample, true, x_bf16, n)) return 1;
+  MMPL_HIP_TRY(mmpl_launch_unipc_f32_table(a, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps,
+                                           (hipStream_t)stream), where);
+  return 0;
+}
+
+int mmpl_cfg_dpmpp_step_f32_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* x_bf16, size_t n,
+                                  const MmplDpmppStep* table_dev, int* step_dev, float* timestep_dev,
+                                  const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream) {
+  const char* where = "mmpl_cfg_dpmpp_step_f32_table";
+  if (f32_table_args(where, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps)) return 1;
+  F32ChainPtrs a = {};
+  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, nullptr, false, x_bf16, n)) return 1;
+  MMPL_HIP_TRY(mmpl_launch_dpmpp_f32_table(a, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps,
+                                           (hipStream_t)stream), where);
+  return 0;
+}
+
 }  // extern "C"

@@ -261,6 +261,25 @@ struct UniPCStepDev {
 hipError_t mmpl_launch_unipc_table(const UniPCArgs& a, const UniPCStepDev* table, int* step, float* t_out, const float* t_tab,
                                    int n_t, int n_steps, hipStream_t s);
 
+// The float32 latent chain (fp32_chain.hip): CFG combine + one UniPC / DPM-Solver++ step on float32 x / m0 / m1 / last_sample with
+// bf16 flows and a bf16 shadow of the new x (x_bf16, may be null); the formulas are at the entries in include/mmpl_hip.h.  `st` is
+// host memory, `table` / `step` / `t_out` / `t_tab` device memory (the protocol of mmpl_launch_unipc_table).  The caller has checked
+// the pointers; a.last is unused by DPM-Solver++.
+struct MmplUniPCStepF32;
+struct MmplDpmppStep;
+struct F32ChainPtrs {
+  const bf16_t* flow_c; const bf16_t* flow_u;   // flow_u == null: flow_c is already the combined flow
+  float* x; float* m0; float* m1; float* last;
+  bf16_t* x_bf16;
+  size_t n;
+};
+hipError_t mmpl_launch_unipc_f32(const F32ChainPtrs& a, const MmplUniPCStepF32* st, hipStream_t s);
+hipError_t mmpl_launch_dpmpp_f32(const F32ChainPtrs& a, const MmplDpmppStep* st, hipStream_t s);
+hipError_t mmpl_launch_unipc_f32_table(const F32ChainPtrs& a, const MmplUniPCStepF32* table, int* step, float* t_out, const float* t_tab,
+                                       int n_t, int n_steps, hipStream_t s);
+hipError_t mmpl_launch_dpmpp_f32_table(const F32ChainPtrs& a, const MmplDpmppStep* table, int* step, float* t_out, const float* t_tab,
+                                       int n_t, int n_steps, hipStream_t s);
+
 // ---------------------------------------------------------------- umT5 glue (t5.hip): the launches of mmpl_t5_encode, one each
 // out[l][:] = emb[ids[l]][:]   (dim % 8 == 0, 16 bytes per access; ids in [0, vocab))
 hipError_t mmpl_launch_t5_gather(const int* ids, const bf16_t* emb, bf16_t* out, int L, int dim, hipStream_t s);

@@ -96,11 +96,13 @@ def cfg_step_buffers(pipe, engine, n_frames: int, concurrent: bool, second_works
 
 
 def cfg_step(forward: Callable[..., object], sched, flow: torch.Tensor, latents: torch.Tensor, t: torch.Tensor, device,
-             side: Optional["torch.cuda.Stream"], share: Optional[torch.Tensor], ws2: Optional[torch.Tensor]) -> None:
+             side: Optional["torch.cuda.Stream"], share: Optional[torch.Tensor], ws2: Optional[torch.Tensor],
+             latents_bf16: Optional[torch.Tensor] = None) -> None:
     """One denoise step's launches, eager or under capture: ``forward(0, flow[0], ...)`` (cond) and ``forward(1, flow[1], ...)``
     (uncond) -- fork / join on ``side`` with the private workspace ``ws2``, or (``side`` None) back to back, the uncond one taking
     block 0's self-attention from the cond one through ``share`` -- then flow = uncond + g (cond - uncond) and
-    latents = scheduler.step(flow) as one fused kernel whose scalars and next timestep come from device tables."""
+    latents = scheduler.step(flow) as one fused kernel whose scalars and next timestep come from device tables.  ``latents_bf16``:
+    the float32 chain's bf16 shadow of ``latents`` (what ``forward`` reads), rewritten by the same kernel."""
     if side is not None:
         main = torch.cuda.current_stream(device)
         side.wait_stream(main)                                        # fork
@@ -111,7 +113,10 @@ def cfg_step(forward: Callable[..., object], sched, flow: torch.Tensor, latents:
     else:
         forward(0, flow[0], share_out=share)
         forward(1, flow[1], share_in=share)
-    sched.step_cfg_table(flow[0], flow[1], latents, t)
+    if latents_bf16 is None:
+        sched.step_cfg_table(flow[0], flow[1], latents, t)
+    else:
+        sched.step_cfg_table(flow[0], flow[1], latents, t, sample_bf16=latents_bf16)
 
 
 # ------------------------------------------------------------------------------------------------ the two few-step pipelines

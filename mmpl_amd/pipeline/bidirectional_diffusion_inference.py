@@ -1,6 +1,10 @@
 """``BidirectionalDiffusionInferencePipeline`` -- drop-in for MMPL_t2v/pipeline/bidirectional_diffusion_inference.py: plain
-Wan2.1 text-to-video sampling (upstream ``WanT2V.generate``): the whole clip is denoised at once, every frame attending to every
-frame, by ``sampling_steps`` multistep-solver steps under classifier-free guidance.
+Wan2.1 text-to-video sampling: the whole clip is denoised at once, every frame attending to every frame, by ``sampling_steps``
+multistep-solver steps under classifier-free guidance.  The forward and the schedule are upstream ``WanT2V.generate``'s; the latent
+chain is chosen by ``latent_dtype``: ``torch.bfloat16`` (default) is the reference pipeline's -- bf16 noise, bf16 latents, a bf16
+rounding after every tensor operation of the solver --, ``torch.float32`` is upstream ``WanT2V.generate``'s -- float32 noise, latents,
+CFG combine and solver (``mmpl_cfg_*_step_f32``), the forwards reading the bf16 rounding of the latents that the solver kernel writes
+next to them (``mmpl_amd.generate.WanT2V`` / ``WanI2V`` wrap that mode in upstream's ``generate()`` signature).
 
 Same constructor / ``inference()`` signature and attributes (``generator``, ``text_encoder``, ``vae``, ``num_train_timesteps``,
 ``sampling_steps`` = 50, ``sample_solver`` = 'unipc' ('dpm++' accepted), ``shift`` = 8.0 -- hard-coded there too, ``args.timestep_shift``
@@ -15,14 +19,14 @@ is not read --, ``args``) and the same semantics.  What changed underneath:
     branches of the graph instead (second stream, private workspace);
   * the frame count is ``noise.shape[1]`` where the reference writes the literal 21; batch size 1.
 
-Over a ``model_type='i2v'`` generator (the released Wan2.1-I2V-14B-480P / -720P weights) this is upstream ``WanI2V.generate``
-(wan/image2video.py): ``inference(..., image_condition={"clip_fea": [257, 1280], "y": [20, F, h, w]})`` from
+Over a ``model_type='i2v'`` generator (the released Wan2.1-I2V-14B-480P / -720P weights) this is upstream ``WanI2V.generate``'s
+forward and conditioning (wan/image2video.py): ``inference(..., image_condition={"clip_fea": [257, 1280], "y": [20, F, h, w]})`` from
 ``i2v_condition.build_image_condition(vae, clip, image, n_latent_frames=F)``, the argument ``CausalFPSInferencePipeline.inference``
 has.  The step state gains a static frame-major ``y`` buffer that every forward of the step graph reads next to the latents
 (``mmpl_dit_forward_full_i2v``: no concatenation, no copy inside the graph); per call ``y`` is copied in and the generator's
 image K / V are rebuilt in place, so another image replays the SAME graph.  Both CFG branches see the image (upstream's
-``arg_null`` carries ``clip_fea`` and ``y`` too), so block 0 is still shared.  The latent chain stays this project's: bf16 latents
-and the fused ``step_cfg_table``, like the text-to-video path; upstream ``WanI2V.generate`` keeps its latents in fp32.  ``shift``
+``arg_null`` carries ``clip_fea`` and ``y`` too), so block 0 is still shared.  The latent chain is ``latent_dtype``'s, as for
+text-to-video: bf16 by default, upstream ``WanI2V.generate``'s float32 one with ``torch.float32``.  ``shift``
 and ``sampling_steps`` keep the defaults above -- ``WanI2V.generate``'s own (40 steps, shift 5.0, or 3.0 at 480p) are the caller's
 to set, as ``mmpl_amd.cli`` does.
 """
@@ -49,6 +53,9 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
         self.sampling_steps = 50
         self.sample_solver = 'unipc'
         self.shift = 8.0
+        # the latent chain: bfloat16 = the reference pipeline's (bf16 noise, latents and solver); float32 = upstream
+        # WanT2V.generate / WanI2V.generate's (float32 noise, latents, CFG combine and solver; the forwards read a bf16 shadow)
+        self.latent_dtype = torch.bfloat16
 
         self.args = args
 
@@ -56,7 +63,7 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
         self.concurrent_cfg: Optional[bool] = None    # None = where concurrent_cfg_pays says so; True / False = always / never
         self.share_block0 = True          # sequential branches: the uncond forward takes block 0's self-attention from the cond one
         self.graph_captures = 0           # hipGraphs constructed so far (tests: none after the first call)
-        self._steps: Dict[tuple, dict] = {}     # (frames, solver, steps, guidance, concurrent, share) -> static buffers, scheduler, graph
+        self._steps: Dict[tuple, dict] = {}     # (frames, solver, steps, guidance, concurrent, share, latent dtype, shift) -> static buffers, scheduler, graph
         self._stores = (self._steps,)
         self._side_stream = None
         self.crossattn_cache_pos = None
@@ -73,17 +80,21 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
         F = noise.shape[1]
         engine, dev = self.generator.engine, self.device
         concurrent = cfg_concurrent(self, engine, F)
+        if self.latent_dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"latent_dtype {self.latent_dtype}: torch.bfloat16 (the reference pipeline's chain) or torch.float32 (upstream's)")
         key = (F, self.sample_solver, int(self.sampling_steps), float(self.args.guidance_scale), concurrent,
-               bool(self.share_block0 and not concurrent))
+               bool(self.share_block0 and not concurrent), self.latent_dtype, float(self.shift))
         st = self._steps.get(key)
         if st is None:
             g = self.geometry
             shape = (F, 16, g.lat_h, g.lat_w)
             sched = self._initialize_sample_scheduler(noise)
-            latents = torch.empty(shape, dtype=torch.bfloat16, device=dev)
+            latents = torch.empty(shape, dtype=self.latent_dtype, device=dev)
+            sched._ensure_state(latents)                                  # (first: the state's dtype is the scheduler's mode)
             sched.build_step_table(self.args.guidance_scale, dev)
-            sched._ensure_state(latents)
-            st = dict(latents=latents, flow=torch.empty((2,) + shape, dtype=torch.bfloat16, device=dev),
+            # float32 chain: the forwards read the bf16 rounding of the latents, which the solver kernel writes next to them
+            shadow = torch.empty(shape, dtype=torch.bfloat16, device=dev) if self.latent_dtype == torch.float32 else None
+            st = dict(latents=latents, latents_bf16=shadow, flow=torch.empty((2,) + shape, dtype=torch.bfloat16, device=dev),
                       t=torch.empty(1, dtype=torch.float32, device=dev), sched=sched, n=len(sched.timesteps), graph=None,
                       timesteps=self.timesteps, concurrent=concurrent,
                       # i2v: the conditioning video, frame-major, read by both forwards of every step and never written by them
@@ -97,15 +108,27 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
         """One denoise step's launches (bidirectional_diffusion_inference.py:62-76): eager, or recorded into the step graph."""
         caches = (self.crossattn_cache_pos, self.crossattn_cache_neg)
         kw = {} if st["y"] is None else {"y": st["y"]}                    # i2v: both branches see the image (image2video.py arg_null)
-        cfg_step(lambda bi, out, **k: self.generator.flow_full(st["latents"], st["t"], caches[bi], out=out, **k, **kw),
+        x_in = st["latents"] if st["latents_bf16"] is None else st["latents_bf16"]
+        cfg_step(lambda bi, out, **k: self.generator.flow_full(x_in, st["t"], caches[bi], out=out, **k, **kw),
                  st["sched"], st["flow"], st["latents"], st["t"], self.device, self._side_stream if st["concurrent"] else None,
-                 st["share"], st["ws2"])
+                 st["share"], st["ws2"], latents_bf16=st["latents_bf16"])
 
     def inference(self, noise: torch.Tensor, text_prompts: List[str], return_latents=False,
                   image_condition: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
-        """noise [1, F, 16, h, w] (F up to 24).  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the latents [1, F, 16, h, w]).
+        """noise [1, F, 16, h, w] (F up to 24; with ``latent_dtype = torch.float32`` float32 noise is used unrounded and the returned
+        latents are float32).  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the latents [1, F, 16, h, w]).
         `image_condition`: {"clip_fea": [257, 1280], "y": [20, F, h, w]} (i2v_condition.build_image_condition) -- required over an
         i2v generator, a ValueError over a t2v one."""
+        latents = self.sample(noise, text_prompts, image_condition)
+        with torch.no_grad():
+            video = decode_video(self.vae, latents.to(torch.bfloat16))    # (float32 chain: the decoder reads the bf16 rounding)
+        if return_latents:
+            return video, latents.to(torch.float32 if self.latent_dtype == torch.float32 else noise.dtype)
+        return video
+
+    def sample(self, noise: torch.Tensor, text_prompts: List[str],
+               image_condition: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+        """The denoise loop of `inference` without the decode: noise [1, F, 16, h, w] -> latents [1, F, 16, h, w] in `latent_dtype`."""
         if image_condition is not None and not self.i2v:
             raise ValueError("BidirectionalDiffusionInferencePipeline: image_condition needs a model_type 'i2v' generator; this one is t2v")
         if self.i2v and (image_condition is None or image_condition.get("clip_fea") is None or image_condition.get("y") is None):
@@ -126,7 +149,9 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
 
             st = self._step_state(noise)
             self.timesteps = st["timesteps"]
-            st["latents"].copy_(noise[0].to(device=dev, dtype=torch.bfloat16))
+            st["latents"].copy_(noise[0].to(device=dev, dtype=self.latent_dtype))      # (float32: taken as it is, never rounded)
+            if st["latents_bf16"] is not None:
+                st["latents_bf16"].copy_(st["latents"])                   # step 1's shadow; the later ones come from the solver kernel
             if self.i2v:                                                  # in place: the step graph holds these addresses
                 y = self.generator.frame_major_y(image_condition["y"])
                 if y.shape[0] != num_frames:
@@ -146,8 +171,4 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
                     else:
                         self._step(st)
 
-            latents = st["latents"].unsqueeze(0).clone()
-            video = decode_video(self.vae, latents)
-        if return_latents:
-            return video, latents.to(noise.dtype)
-        return video
+            return st["latents"].unsqueeze(0).clone()

@@ -12,6 +12,11 @@ rotation) is ONE fused HIP kernel (``mmpl_cfg_unipc_step``) instead of ~25 tiny 
 ``sample_solver = 'dpm++'`` (MMPL_t2v/wan/utils/fm_solvers.py as configured by pipeline/casual_fps_inference.py:512-521), split the
 same way around ``mmpl_cfg_dpmpp_step`` and with the same device-facing interface, so the stage loop drives either object.
 
+Both classes have two modes, chosen by the dtype of the sample their solver state is built for (``_solver_state``): bfloat16 is
+the reference pipelines' chain (a bf16 rounding after every tensor operation), float32 is upstream Wan2.1's ``WanT2V.generate`` /
+``WanI2V.generate`` chain -- float32 sample and solver state, ``mmpl_cfg_unipc_step_f32`` / ``mmpl_cfg_dpmpp_step_f32``, the same
+scalar expressions with ``rk`` itself in place of ``1 / rk`` and rhos that are not rounded to bf16.
+
 ``FlowMatchScheduler`` is the train-time schedule the pipeline uses for ``add_noise``
 (MMPL_t2v/utils/scheduler.py:103-176).
 """
@@ -26,8 +31,57 @@ import torch
 from . import _lib
 
 
+def _solver_state(sched, sample: torch.Tensor, n_tensors: int) -> None:
+    """THE place where a scheduler's mode is chosen: by the dtype of the sample its solver state is built for.  bfloat16 = the
+    reference pipelines' chain (a bf16 rounding after every tensor operation); float32 = upstream Wan2.1's (`WanT2V.generate`:
+    float32 latents and solver state, ``mmpl_cfg_*_step_f32``).  `step_scalars` and `build_step_table` read `sched.latent_dtype`, so
+    a table is built after the state (`_ensure_state(sample)` first)."""
+    if sample.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"{type(sched).__name__}: the sample is {sample.dtype}; bfloat16 or float32")
+    st = sched._state
+    if st is None or st[0].shape != sample.shape or st[0].device != sample.device or st[0].dtype != sample.dtype:
+        sched._state = [torch.zeros_like(sample) for _ in range(n_tensors)]
+    sched.latent_dtype = sample.dtype
+
+
+def _shadow_ptr(sample: torch.Tensor, sample_bf16: Optional[torch.Tensor]):
+    """The bf16 shadow of a float32 sample (None = not wanted) as the x_bf16 argument."""
+    if sample_bf16 is not None:
+        assert sample_bf16.dtype == torch.bfloat16 and sample_bf16.is_contiguous() and sample_bf16.numel() == sample.numel()
+    return _lib.ptr(sample_bf16)
+
+
+def _table_rows(sched, guidance: float, device) -> None:
+    """`build_step_table` of both solvers: the scalars of every remaining step from a copy of `sched` (its own bookkeeping does not
+    advance), in the struct of its mode, and the timestep of every step."""
+    import copy
+    probe = copy.copy(sched)
+    probe._state = None
+    n = len(sched.timesteps) - sched.step_index
+    first = probe.step_scalars(guidance)
+    rows = (type(first) * n)()
+    rows[0] = first
+    for i in range(1, n):
+        rows[i] = probe.step_scalars(guidance)
+    raw = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).clone()
+    sched._table = raw.to(device)
+    sched._table_dtype = sched.latent_dtype
+    t_host = [float(t) for t in sched.timesteps[sched.step_index:]]
+    sched._t_table = torch.tensor(t_host, dtype=torch.float32, device=device)
+    sched._t_first = t_host[0]          # host copy: reset_step_table must not read the device table (a sync inside timed loops)
+    sched._counter = torch.zeros(1, dtype=torch.int32, device=device)
+    sched._table_n = n
+
+
+def _check_table_call(sched, sample: torch.Tensor, timestep: torch.Tensor) -> None:
+    assert sample.is_contiguous() and timestep.dtype == torch.float32 and timestep.is_contiguous()
+    if sched._table_dtype != sample.dtype:
+        raise TypeError(f"{type(sched).__name__}: the step table was built for a {sched._table_dtype} sample, this one is {sample.dtype}")
+
+
 class FlowUniPCMultistepScheduler:
     order = 1
+    latent_dtype = torch.bfloat16         # the mode: set by _ensure_state from the sample (see _solver_state)
 
     def __init__(self, num_train_timesteps: int = 1000, solver_order: int = 2, shift: float = 1.0,
                  use_dynamic_shifting: bool = False):
@@ -73,11 +127,11 @@ class FlowUniPCMultistepScheduler:
         alpha_t = 1 - sigma_t
         h = self._lam(sigma_t) - self._lam(sigma_s0)
         rks = []
-        inv_rk = 0.0
+        inv_rk, rk_f = 0.0, 1.0
         if order == 2:
             rk = (self._lam(self.sigmas[si - 2]) - self._lam(sigma_s0)) / h
             rks.append(rk)
-            inv_rk = (1.0 / rk).item()
+            inv_rk, rk_f = (1.0 / rk).item(), rk.item()
         rks.append(1.0)
         rks = torch.tensor(rks)
         hh = -h
@@ -91,11 +145,11 @@ class FlowUniPCMultistepScheduler:
             b.append(h_phi_k * factorial_i / B_h)
             factorial_i *= i + 1
             h_phi_k = h_phi_k / hh - 1 / factorial_i
-        if order == 1:
-            rhos = torch.tensor([0.5], dtype=torch.bfloat16)
+        if order == 1:                                                 # `.to(x.dtype)`: float32 rhos for a float32 sample
+            rhos = torch.tensor([0.5], dtype=self.latent_dtype)
         else:
-            rhos = torch.linalg.solve(torch.stack(R), torch.tensor(b)).to(torch.bfloat16)
-        return dict(c1=(sigma_t / sigma_s0).item(), c2=(alpha_t * h_phi_1).item(), c3=(alpha_t * B_h).item(), inv_rk=inv_rk,
+            rhos = torch.linalg.solve(torch.stack(R), torch.tensor(b)).to(self.latent_dtype)
+        return dict(c1=(sigma_t / sigma_s0).item(), c2=(alpha_t * h_phi_1).item(), c3=(alpha_t * B_h).item(), inv_rk=inv_rk, rk=rk_f,
                     rho0=rhos[0].float().item() if order == 2 else 0.0, rho_last=rhos[-1].float().item())
 
     def _predictor_scalars(self, order: int):
@@ -104,32 +158,38 @@ class FlowUniPCMultistepScheduler:
         sigma_t, sigma_s0 = self.sigmas[si + 1], self.sigmas[si]
         alpha_t = 1 - sigma_t
         h = self._lam(sigma_t) - self._lam(sigma_s0)
-        inv_rk = 0.0
+        inv_rk, rk_f = 0.0, 1.0
         if order == 2:
             rk = (self._lam(self.sigmas[si - 1]) - self._lam(sigma_s0)) / h
-            inv_rk = (1.0 / rk).item()
+            inv_rk, rk_f = (1.0 / rk).item(), rk.item()
         hh = -h
         h_phi_1 = torch.expm1(hh)
         B_h = torch.expm1(hh)
-        return dict(c1=(sigma_t / sigma_s0).item(), c2=(alpha_t * h_phi_1).item(), c3=(alpha_t * B_h).item(), inv_rk=inv_rk)
+        return dict(c1=(sigma_t / sigma_s0).item(), c2=(alpha_t * h_phi_1).item(), c3=(alpha_t * B_h).item(), inv_rk=inv_rk, rk=rk_f)
 
-    def step_scalars(self, guidance: float) -> _lib.MmplUniPCStep:
-        """Scalars of the step at the current step_index; advances the host-side order bookkeeping (:686-730)."""
+    def step_scalars(self, guidance: float):
+        """Scalars of the step at the current step_index; advances the host-side order bookkeeping (:686-730).  A MmplUniPCStep, or
+        in float32 mode a MmplUniPCStepF32: the same expressions, but rk itself where the bf16 struct carries 1 / rk (the kernel
+        divides, as the reference does) and rhos that were never rounded to bf16."""
         si = self.step_index
         use_corr = si > 0 and self._have_last
-        st = _lib.MmplUniPCStep()
+        f32 = self.latent_dtype == torch.float32
+        rk = "rk" if f32 else "inv_rk"
+        st = (_lib.MmplUniPCStepF32 if f32 else _lib.MmplUniPCStep)()
         st.guidance = float(guidance)
         st.sigma_cur = self.sigmas[si].item()
         st.use_corrector = int(use_corr)
         st.corr_order = self.this_order
         if use_corr:
             c = self._corrector_scalars(self.this_order)
-            st.c_c1, st.c_c2, st.c_c3, st.c_inv_rk, st.c_rho0, st.c_rho_last = c["c1"], c["c2"], c["c3"], c["inv_rk"], c["rho0"], c["rho_last"]
+            st.c_c1, st.c_c2, st.c_c3, st.c_rho0, st.c_rho_last = c["c1"], c["c2"], c["c3"], c["rho0"], c["rho_last"]
+            setattr(st, "c_" + rk, c[rk])
         this_order = min(self.solver_order, len(self.timesteps) - si)
         self.this_order = min(this_order, self.lower_order_nums + 1)
         p = self._predictor_scalars(self.this_order)
         st.pred_order = self.this_order
-        st.p_c1, st.p_c2, st.p_c3, st.p_inv_rk = p["c1"], p["c2"], p["c3"], p["inv_rk"]
+        st.p_c1, st.p_c2, st.p_c3 = p["c1"], p["c2"], p["c3"]
+        setattr(st, "p_" + rk, p[rk])
         self._have_last = True
         if self.lower_order_nums < self.solver_order:
             self.lower_order_nums += 1
@@ -138,17 +198,23 @@ class FlowUniPCMultistepScheduler:
 
     # -- device update -----------------------------------------------------------------------------
     def _ensure_state(self, sample: torch.Tensor):
-        if self._state is None or self._state[0].shape != sample.shape or self._state[0].device != sample.device:
-            self._state = [torch.zeros_like(sample) for _ in range(3)]      # m0, m1, last_sample
+        _solver_state(self, sample, 3)                                      # m0, m1, last_sample
 
     def step_cfg(self, flow_cond: torch.Tensor, flow_uncond: Optional[torch.Tensor], guidance: float,
-                 sample: torch.Tensor) -> torch.Tensor:
-        """CFG combine + scheduler step, fused; `sample` is updated in place and returned."""
-        assert sample.is_contiguous() and sample.dtype == torch.bfloat16 and flow_cond.is_contiguous()
+                 sample: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """CFG combine + scheduler step, fused; `sample` is updated in place and returned.  The flows are bf16.  A float32 `sample`
+        takes the float32 chain; `sample_bf16` (optional) then receives the bf16 rounding of the new sample."""
+        assert sample.is_contiguous() and flow_cond.is_contiguous() and flow_cond.dtype == torch.bfloat16
         self._ensure_state(sample)
         st = self.step_scalars(guidance)
         lib = _lib.load()
         m0, m1, last = self._state
+        if sample.dtype == torch.float32:
+            _lib.check(lib.mmpl_cfg_unipc_step_f32(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
+                                                   _lib.ptr(m1), _lib.ptr(last), _shadow_ptr(sample, sample_bf16), sample.numel(),
+                                                   C.byref(st), _lib.stream_ptr()), "mmpl_cfg_unipc_step_f32")
+            return sample
+        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
         _lib.check(lib.mmpl_cfg_unipc_step(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
                                            _lib.ptr(m1), _lib.ptr(last), sample.numel(), C.byref(st), _lib.stream_ptr()),
                    "mmpl_cfg_unipc_step")
@@ -159,21 +225,9 @@ class FlowUniPCMultistepScheduler:
         """Upload the scalars of ALL remaining steps (they depend only on the step index, never on data) plus the timestep
         of every step; `step_cfg_table` then reads entry *counter on the device.  The host-side step bookkeeping of THIS
         object is not advanced (the scalars come from a copy): after the table's last step the device kernel does nothing
-        (the counter is clamped), `reset_step_table` rewinds it for another pass over the same schedule."""
-        import copy
-        probe = copy.copy(self)
-        probe._state = None
-        n = len(self.timesteps) - self.step_index
-        rows = (_lib.MmplUniPCStep * n)()
-        for i in range(n):
-            rows[i] = probe.step_scalars(guidance)
-        raw = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).clone()
-        self._table = raw.to(device)
-        t_host = [float(t) for t in self.timesteps[self.step_index:]]
-        self._t_table = torch.tensor(t_host, dtype=torch.float32, device=device)
-        self._t_first = t_host[0]          # host copy: reset_step_table must not read the device table (a sync inside timed loops)
-        self._counter = torch.zeros(1, dtype=torch.int32, device=device)
-        self._table_n = n
+        (the counter is clamped), `reset_step_table` rewinds it for another pass over the same schedule.  The rows are those of
+        the mode `_ensure_state` chose (bf16 unless it has been called with a float32 sample)."""
+        _table_rows(self, guidance, device)
 
     def reset_step_table(self, timestep: torch.Tensor) -> None:
         """Rewind the device step counter, the solver history and `timestep` to the first entry of the uploaded table."""
@@ -183,12 +237,21 @@ class FlowUniPCMultistepScheduler:
                 t.zero_()
         timestep.fill_(self._t_first)
 
-    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor) -> None:
+    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor,
+                       sample_bf16: Optional[torch.Tensor] = None) -> None:
         """CFG combine + scheduler step with device-resident scalars (capturable: no host value enters the launch);
-        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous)."""
-        assert sample.is_contiguous() and sample.dtype == torch.bfloat16 and timestep.dtype == torch.float32 and timestep.is_contiguous()
+        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous).  A float32
+        `sample` (the table was built for one) takes the float32 chain and writes its bf16 rounding to `sample_bf16`."""
+        _check_table_call(self, sample, timestep)
         self._ensure_state(sample)
         m0, m1, last = self._state
+        if sample.dtype == torch.float32:
+            _lib.check(_lib.load().mmpl_cfg_unipc_step_f32_table(
+                _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), _lib.ptr(last),
+                _shadow_ptr(sample, sample_bf16), sample.numel(), _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep),
+                _lib.ptr(self._t_table), timestep.numel(), self._table_n, _lib.stream_ptr()), "mmpl_cfg_unipc_step_f32_table")
+            return
+        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
         _lib.check(_lib.load().mmpl_cfg_unipc_step_table(
             _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), _lib.ptr(last), sample.numel(),
             _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep), _lib.ptr(self._t_table), timestep.numel(), self._table_n,
@@ -197,7 +260,7 @@ class FlowUniPCMultistepScheduler:
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
         """Reference call shape (fm_solvers_unipc.py:655).  `timestep` is accepted and ignored like the reference's
         internal step counter does after the first call."""
-        out = self.step_cfg(model_output.contiguous(), None, 0.0, sample.contiguous().clone())
+        out = self.step_cfg(model_output.to(torch.bfloat16).contiguous(), None, 0.0, sample.contiguous().clone())   # (flows are bf16)
         return (out,) if not return_dict else {"prev_sample": out}
 
 
@@ -227,8 +290,9 @@ class FlowDPMSolverMultistepScheduler:
     Split like the UniPC class above: the per-step scalars (sigma ratio, alpha_t (exp(-h) - 1), 1 / r0) are computed on the host with
     the reference's own torch fp32 0-dim tensor operations, the tensor update (CFG combine, x0 conversion, history rotation, first /
     second order update) is ONE fused HIP kernel (``mmpl_cfg_dpmpp_step``), and the device-facing interface is the UniPC class's, so
-    the stage loop drives either object.  The solver state is two bf16 tensors (m0, m1); there is no corrector and no last sample."""
+    the stage loop drives either object.  The solver state is two tensors of the sample's dtype (m0, m1); there is no corrector and no last sample."""
     order = 1
+    latent_dtype = torch.bfloat16         # the mode: set by _ensure_state from the sample (see _solver_state)
     _SUPPORTED = dict(solver_order=2, prediction_type="flow_prediction", shift=1.0, use_dynamic_shifting=False, thresholding=False,
                       algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, euler_at_final=False,
                       final_sigmas_type="zero", lambda_min_clipped=-float("inf"), variance_type=None, invert_sigmas=False)
@@ -319,16 +383,23 @@ class FlowDPMSolverMultistepScheduler:
 
     # -- device update -----------------------------------------------------------------------------
     def _ensure_state(self, sample: torch.Tensor):
-        if self._state is None or self._state[0].shape != sample.shape or self._state[0].device != sample.device:
-            self._state = [torch.zeros_like(sample) for _ in range(2)]      # m0, m1
+        _solver_state(self, sample, 2)                                      # m0, m1
 
     def step_cfg(self, flow_cond: torch.Tensor, flow_uncond: Optional[torch.Tensor], guidance: float,
-                 sample: torch.Tensor) -> torch.Tensor:
-        """CFG combine + scheduler step, fused; `sample` is updated in place and returned."""
-        assert sample.is_contiguous() and sample.dtype == torch.bfloat16 and flow_cond.is_contiguous()
+                 sample: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """CFG combine + scheduler step, fused; `sample` is updated in place and returned.  The flows are bf16.  A float32 `sample`
+        takes the float32 chain (the same scalars: the reference multiplies by 1.0 / r0 there too); `sample_bf16` (optional) then
+        receives the bf16 rounding of the new sample."""
+        assert sample.is_contiguous() and flow_cond.is_contiguous() and flow_cond.dtype == torch.bfloat16
         self._ensure_state(sample)
         st = self.step_scalars(guidance)
         m0, m1 = self._state
+        if sample.dtype == torch.float32:
+            _lib.check(_lib.load().mmpl_cfg_dpmpp_step_f32(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
+                                                           _lib.ptr(m1), _shadow_ptr(sample, sample_bf16), sample.numel(), C.byref(st),
+                                                           _lib.stream_ptr()), "mmpl_cfg_dpmpp_step_f32")
+            return sample
+        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
         _lib.check(_lib.load().mmpl_cfg_dpmpp_step(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
                                                    _lib.ptr(m1), sample.numel(), C.byref(st), _lib.stream_ptr()),
                    "mmpl_cfg_dpmpp_step")
@@ -338,20 +409,7 @@ class FlowDPMSolverMultistepScheduler:
     def build_step_table(self, guidance: float, device) -> None:
         """Upload the scalars and the timestep of every remaining step; `step_cfg_table` reads entry *counter on the device.  The
         host-side step_index of THIS object is not advanced (the scalars come from a copy)."""
-        import copy
-        probe = copy.copy(self)
-        probe._state = None
-        n = len(self.timesteps) - self.step_index
-        rows = (_lib.MmplDpmppStep * n)()
-        for i in range(n):
-            rows[i] = probe.step_scalars(guidance)
-        raw = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).clone()
-        self._table = raw.to(device)
-        t_host = [float(t) for t in self.timesteps[self.step_index:]]
-        self._t_table = torch.tensor(t_host, dtype=torch.float32, device=device)
-        self._t_first = t_host[0]          # host copy: reset_step_table must not read the device table (a sync inside timed loops)
-        self._counter = torch.zeros(1, dtype=torch.int32, device=device)
-        self._table_n = n
+        _table_rows(self, guidance, device)
 
     def reset_step_table(self, timestep: torch.Tensor) -> None:
         """Rewind the device step counter, the solver history and `timestep` to the first entry of the uploaded table."""
@@ -361,12 +419,21 @@ class FlowDPMSolverMultistepScheduler:
                 t.zero_()
         timestep.fill_(self._t_first)
 
-    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor) -> None:
+    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor,
+                       sample_bf16: Optional[torch.Tensor] = None) -> None:
         """CFG combine + scheduler step with device-resident scalars (capturable: no host value enters the launch);
-        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous)."""
-        assert sample.is_contiguous() and sample.dtype == torch.bfloat16 and timestep.dtype == torch.float32 and timestep.is_contiguous()
+        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous).  A float32
+        `sample` (the table was built for one) takes the float32 chain and writes its bf16 rounding to `sample_bf16`."""
+        _check_table_call(self, sample, timestep)
         self._ensure_state(sample)
         m0, m1 = self._state
+        if sample.dtype == torch.float32:
+            _lib.check(_lib.load().mmpl_cfg_dpmpp_step_f32_table(
+                _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), _shadow_ptr(sample, sample_bf16),
+                sample.numel(), _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep), _lib.ptr(self._t_table),
+                timestep.numel(), self._table_n, _lib.stream_ptr()), "mmpl_cfg_dpmpp_step_f32_table")
+            return
+        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
         _lib.check(_lib.load().mmpl_cfg_dpmpp_step_table(
             _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), sample.numel(),
             _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep), _lib.ptr(self._t_table), timestep.numel(), self._table_n,
@@ -375,7 +442,7 @@ class FlowDPMSolverMultistepScheduler:
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
         """Reference call shape (fm_solvers.py:706).  `timestep` is accepted and ignored: the steps are counted, as the reference's
         internal step counter does after the first call."""
-        out = self.step_cfg(model_output.contiguous(), None, 0.0, sample.contiguous().clone())
+        out = self.step_cfg(model_output.to(torch.bfloat16).contiguous(), None, 0.0, sample.contiguous().clone())   # (flows are bf16)
         return (out,) if not return_dict else {"prev_sample": out}
 
 
