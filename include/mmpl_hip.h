@@ -129,6 +129,28 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int n_
                         int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
                         void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
                         mmpl_stream_t stream);
+/* mmpl_dit_forward_at over a BATCH: n_groups independent samples of frames_per_group frames each, in the launches of ONE forward over
+ * n_frames = n_groups * frames_per_group frames.  Everything but attention works per row or per frame already, and every sample's
+ * K / V slots lie in the one cache allocation, so the batch is an ordinary forward except that the self-attention is block-diagonal:
+ * the query rows of sample g see sample g's visible slots only (one grouped launch of attn_w64_kernel, see mmpl_attn_fwd_groups_ex).
+ *   x_in / out, t_dev, frame_ids, write_slots: per frame as mmpl_dit_forward_at, sample-major (frame g * frames_per_group + i is frame i of
+ *                sample g); n_frames <= cfg.max_frames.
+ *   visible_slots: host, n_groups lists of n_visible slots each, back to back.  The caller gives each sample slots of its own (sample g
+ *                of a window of W slots: g * W .. g * W + W - 1 of a cache of n_groups * W); write slots of different samples must differ.
+ *   cross_k / cross_v: host arrays of n_groups device pointers.  When every sample's pair is the same pointers (one prompt for all) the
+ *                text cross-attention is the ONE launch of mmpl_dit_forward_at over all rows; otherwise one such launch per sample on
+ *                that sample's rows.  cross_rows is one statement for all samples: it must hold for each of them (the largest of the
+ *                samples' `distinct_rows` does).
+ * Rejected before the first launch, each with its own message: n_groups < 1, n_frames > max_frames, a non-NULL share_out / share_in /
+ * attn_history (pass NULL), an i2v handle (image K / V attached), a visible or write slot outside [0, n_slots), write slots of two
+ * samples that coincide.  n_groups == 1 launches what mmpl_dit_forward_at launches, bit for bit.  The workspace is
+ * mmpl_dit_workspace_bytes(h, n_frames).  Sample g's result equals a mmpl_dit_forward_at call on that sample alone up to the choices
+ * the GEMM and the attention launchers make from the row count (tile order, split tails): bit-equal where those agree. */
+int mmpl_dit_forward_groups(MmplDit* h, const void* x_in, const float* t_dev, int n_groups, int frames_per_group, const int* frame_ids,
+                            const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache, int n_slots,
+                            const void* const* cross_k, const void* const* cross_v, int cross_rows, void* share_out, const void* share_in,
+                            void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                            mmpl_stream_t stream);
 size_t mmpl_dit_attn_history_bytes(const MmplDit* h, int n_frames);
 /* The non-causal WanModel.forward (model.py, behind WanDiffusionWrapper(is_causal=False).forward, utils/wan_wrapper.py) over a WHOLE
  * clip: the blocks of mmpl_dit_forward with frame i rotated at temporal position i, every frame attending to every frame, and no
@@ -665,6 +687,29 @@ int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const
                      const unsigned char* page_group, int ldk, int ldv, int n_pages, int page_rows, int Lq, int num_heads,
                      float softmax_scale, void* workspace, size_t workspace_bytes, int variant, int q_prescaled, int cross,
                      int last_row_copies, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream);
+
+/* n_groups self-attentions of equal shape in one call, for tests/test_attn_groups_gpu.py: the samples of a batched forward, each
+ * seeing its own pages only.  The arguments of mmpl_attn_fwd_ex (without cross and last_row_copies) plus the groups:
+ *   q, o    [n_groups * group_rows, ld]: group g's queries are rows g * group_rows .. (group_rows need not be a multiple of 256: every
+ *           group has ceil(group_rows / 256) query blocks of its own).  Rows past n_groups * group_rows and columns >= 128 * num_heads
+ *           of o are not written.
+ *   group_n_pages  host array of n_groups ints, each 1 .. 24; k_pages, v_pages, page_group (or NULL): host arrays of their sum, the
+ *           groups' lists back to back; every page [page_rows, ldk / ldv].
+ *   history NULL, or n_groups regions of mmpl_attn_history_bytes(group_rows, num_heads) bytes, group g's at g times that.
+ * One grouped launch of attn_w64_kernel's body (attn_w64_groups_kernel: (group, head) is a virtual head of the work-item decode)
+ * runs when every group resolves to the 64-rows-per-wave kernel, history is NULL and the groups' lists, each merged by itself, hold
+ * at most 24 pages in all; otherwise the call makes one launch of mmpl_attn_fwd_ex's kind per group, which computes the same
+ * (the lock-step variant, MMPL_ATTN_V1, a history, more than 24 merged pages).  Block for block the grouped launch does what the
+ * per-group launches do, so the results are bit-equal wherever neither splits its tail round.
+ *   plan_out NULL or 10 host ints (all 0 when the call is rejected): [0] .. [7] as mmpl_attn_fwd_ex -- of the grouped launch
+ *           ([1] merged pages of all groups, [2] KV tiles of the longest group; the split-KV tail is decided by the same rule from
+ *           the total item count and the shortest group's tiles), or of group 0's launch on the per-group path;
+ *           [8] 1 = one grouped launch, 0 = one launch per group; [9] work items n_groups * num_heads * ceil(group_rows / 256).
+ * Every check runs before the first HIP call and a rejected call launches nothing. */
+int mmpl_attn_fwd_groups_ex(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
+                            const unsigned char* page_group, const int* group_n_pages, int n_groups, int group_rows, int ldk, int ldv,
+                            int page_rows, int num_heads, float softmax_scale, void* workspace, size_t workspace_bytes, int variant,
+                            int q_prescaled, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream);
 
 /* The norm / RoPE / elementwise kernels (elementwise.hip) one launch at a time, for tests/test_rowpass_exact_gpu.py.  mmpl_layernorm,
  * mmpl_qknorm_rope and mmpl_qknorm_rope_at are unchanged.  Every check runs before the first HIP call, with one message per check; a

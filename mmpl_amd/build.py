@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmmpl_hip.so")
-SOURCES = ["device_state.hip", "gemm.hip", "attention.hip", "attn_w64.hip", "elementwise.hip", "vae_kernels.hip", "vae.hip", "taehv_kernels.hip", "taehv.hip", "taehv_enc_kernels.hip", "taehv_enc.hip","kernel_entry.hip", "t5.hip", "i2v.hip", "fewstep.hip", "dpmpp.hip", "fp32_chain.hip", "probe.hip", "api.hip"]
+SOURCES = ["device_state.hip", "gemm.hip", "attention.hip", "attn_w64.hip", "attn_w64_groups.hip", "elementwise.hip", "vae_kernels.hip", "vae.hip", "taehv_kernels.hip", "taehv.hip", "taehv_enc_kernels.hip", "taehv_enc.hip","kernel_entry.hip", "t5.hip", "i2v.hip", "fewstep.hip", "dpmpp.hip", "fp32_chain.hip", "probe.hip", "api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed"] + os.environ.get("MMPL_EXTRA_HIPCC_FLAGS", "").split()
 
 
@@ -39,6 +39,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "mmpl_hip.h"))
+    headers.append(os.path.join(CSRC, "attn_w64.hip"))       # attn_w64_groups.hip includes it
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     # the compile flags are part of the staleness key: a library built with timing / ablation defines
     # (MMPL_EXTRA_HIPCC_FLAGS, tools/*_sweep.sh) must never survive into a later plain build, whatever the mtimes say

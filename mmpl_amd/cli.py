@@ -153,6 +153,39 @@ def fp32_refusal(args, fewstep: bool):
     return None
 
 
+MAX_FORWARD_FRAMES = 8               # the engine's largest forward (MmplDitConfig.max_frames at most): what a batch's samples share
+
+
+def sample_groups(n_samples: int, num_frame_per_block: int, max_frames: int = MAX_FORWARD_FRAMES):
+    """--num_samples N as consecutive slices [lo, hi) of at most ``max_frames // num_frame_per_block`` samples: one
+    CausalInferencePipeline.inference call each (a call's samples run as ONE forward of samples x block frames)."""
+    g = max(max_frames // max(num_frame_per_block, 1), 1)
+    return [(lo, min(lo + g, n_samples)) for lo in range(0, n_samples, g)]
+
+
+def samples_refusal(args, fewstep: bool):
+    """Why --num_samples N cannot run this command line (None = it can, or N is 1): several samples per prompt are the few-step
+    causal pipeline's batched inference() (one noise draw [N, F, 16, h, w], as the reference's --num_samples)."""
+    n = int(getattr(args, "num_samples", 1))
+    if n == 1:
+        return None
+    if n < 1:
+        return f"--num_samples {n}: at least 1"
+    if not fewstep:
+        return ("--num_samples: batched generation needs a few-step config (one with denoising_step_list, e.g. self_forcing_dmd.yaml); "
+                "the 50-step pipeline generates one sample per prompt")
+    if getattr(args, "bidirectional", False):
+        return "--num_samples: the --bidirectional pipelines denoise one whole clip per call; batched generation is the causal few-step pipeline's"
+    if getattr(args, "stream", False):
+        return "--num_samples: --stream hands out ONE video block by block (inference_stream keeps batch size 1); drop --stream"
+    if getattr(args, "extend", None):
+        return "--num_samples: --extend continues one clip on the streaming path, which keeps batch size 1"
+    block = int(getattr(args, "num_frame_per_block", 1))
+    if block > MAX_FORWARD_FRAMES:
+        return f"--num_samples: num_frame_per_block {block} exceeds the engine's largest forward ({MAX_FORWARD_FRAMES} frames)"
+    return None
+
+
 def read_clip(path: str) -> torch.Tensor:
     """A clip as this CLI writes it -> uint8 [T, H, W, 3] on the host: the ``.pt`` tensor, or the MJPEG ``.avi`` of
     utils/video_io.py."""
@@ -221,7 +254,7 @@ def first_refusal(args, world: int, fewstep: bool):
               lambda: rolling_refusal(args, fewstep), lambda: solver_refusal(args, fewstep),
               lambda: fp32_refusal(args, fewstep),
               lambda: fewstep_refusal(args, world) if fewstep and not args.bidirectional else None,
-              lambda: extend_refusal(args, fewstep))
+              lambda: extend_refusal(args, fewstep), lambda: samples_refusal(args, fewstep))
     return next((why for why in (check() for check in checks) if why is not None), None)
 
 
@@ -238,14 +271,14 @@ def _to_u8(video: torch.Tensor) -> torch.Tensor:
     return (video * 255.0).clamp(0, 255).to(torch.uint8)
 
 
-def _save_clip(frames: torch.Tensor, args, idx: int, what: str = "") -> None:
-    """uint8 frames, [1, T, 3, H, W] or already the written layout [T, H, W, 3] on the host -> ``idx``-0.pt (torch.save) and the
-    video file next to it (Wan_fps_inference_1gpu.py:225)."""
+def _save_clip(frames: torch.Tensor, args, idx: int, what: str = "", sample: int = 0) -> None:
+    """uint8 frames, [1, T, 3, H, W] or already the written layout [T, H, W, 3] on the host -> ``idx``-``sample``.pt (torch.save)
+    and the video file next to it (Wan_fps_inference_1gpu.py:225)."""
     out = frames[0].permute(0, 2, 3, 1).contiguous().cpu() if frames.dim() == 5 else frames
-    path = os.path.join(args.output_folder, f"{idx}-0.pt")
+    path = os.path.join(args.output_folder, f"{idx}-{sample}.pt")
     torch.save(out, path)
     from .utils.video_io import write_video
-    vpath = write_video(os.path.join(args.output_folder, f"{idx}-0.mp4"), out, fps=16)
+    vpath = write_video(os.path.join(args.output_folder, f"{idx}-{sample}.mp4"), out, fps=16)
     print(f"[mmpl_amd.cli] {what}prompt {idx}: {tuple(out.shape)} frames @16 fps -> {vpath} (+ {path})")
 
 
@@ -323,7 +356,7 @@ def build_fewstep_pipeline(config, args, dev, geo, mcfg):
     config.rolling_kv = bool(getattr(args, "rolling", False))
     gen, enc, vae, _ = _build_models(args, dev, geo, mcfg, lambda model_config: WanDiffusionWrapper(
         "Wan2.1-T2V-14B" if args.model == "14B" else "Wan2.1-T2V-1.3B", **kw, is_causal=True, model_config=model_config, geometry=geo,
-        device=dev))
+        device=dev, **({"max_frames": MAX_FORWARD_FRAMES} if int(getattr(args, "num_samples", 1)) > 1 else {})))
     preview = build_preview_vae(args, dev, geo) if getattr(args, "preview_vae", None) is not None else None
     pipe = CausalInferencePipeline(config, dev, generator=gen, text_encoder=enc, vae=vae, preview_vae=preview)
     pipe.independent_first_frame = False
@@ -392,6 +425,11 @@ def main(argv=None):
                     help="few-step configs with --stream --preview_vae: continue FILE, a clip this CLI wrote (.pt uint8 [T, H, W, 3] or "
                          "its MJPEG .avi) -- its last frames are encoded by the tiny autoencoder into the pipeline's initial_latent "
                          "and --num_output_frames NEW latent frames follow; the written clip is the context frames plus the new ones")
+    ap.add_argument("--num_samples", type=int, default=1, metavar="N",
+                    help="few-step configs: N videos per prompt from ONE noise draw [N, F, 16, h, w] (the reference's --num_samples), "
+                         "written as {idx}-{sample}; 8 // num_frame_per_block samples run per call as one batched forward.  With more "
+                         "samples than that the re-noise draws follow call by call, so they match the reference's order only up to "
+                         "that many")
     ap.add_argument("--extend_context", type=int, default=None, metavar="N",
                     help="with --extend: latent frames of context (the clip's last 4 N frames); default num_frame_per_block, a multiple of it")
     args = ap.parse_args(argv)
@@ -517,7 +555,8 @@ def _main_fewstep(config, args, dev, geo, mcfg):
     --duration * num_output_frames latent frames; fewstep_refusal keeps --duration at 1 otherwise)."""
     pipe = build_fewstep_pipeline(config, args, dev, geo, mcfg)
     os.makedirs(args.output_folder, exist_ok=True)
-    shape = [1, args.num_output_frames * args.duration, 16, geo.lat_h, geo.lat_w]
+    n_samples = int(getattr(args, "num_samples", 1))
+    shape = [n_samples, args.num_output_frames * args.duration, 16, geo.lat_h, geo.lat_w]
     context_px, initial = None, None
     if getattr(args, "extend", None):
         # --extend FILE: the clip's last 4 N frames -> N latent frames (a video of their own, from zero memories) = initial_latent
@@ -545,6 +584,14 @@ def _main_fewstep(config, args, dev, geo, mcfg):
                       f"{time.perf_counter() - t0:.3f} s" + (" (time to the first frames)" if not parts else ""))
                 parts.append(frames)
             out = torch.cat(parts)                                                                             # [T, H, W, 3]
+        elif n_samples > 1:
+            # ONE noise draw for all samples (Wan_fps_inference_1gpu.py:132-155); each call takes the next slice of it and draws its
+            # own re-noise [samples, F, 16, h, w] per step from the device generator, call after call
+            for lo, hi in sample_groups(n_samples, pipe.num_frame_per_block, pipe.generator.engine.max_frames):
+                video = _to_u8(pipe.inference(noise[lo:hi].to(dev), [prompt] * (hi - lo), return_latents=False))
+                for k in range(lo, hi):
+                    _save_clip(video[k - lo:k - lo + 1], args, idx, "few-step ", sample=k)
+            continue
         else:
             out = _to_u8(pipe.inference(noise.to(dev), [prompt], return_latents=False))
         _save_clip(out, args, idx, "few-step ")

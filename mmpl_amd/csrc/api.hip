@@ -378,6 +378,10 @@ struct FwdCall {
   void *k_cache, *v_cache, *share_out, *attn_history, *out, *workspace;
   size_t workspace_bytes;
   mmpl_stream_t stream;
+  // mmpl_dit_forward_groups with more than one sample (0 = every other entry): nF = n_groups * frames_per_group frames, sample-major;
+  // visible_slots holds n_groups lists of n_visible; group_cross_k / _v the samples' text K / V (cross_k / cross_v are then sample 0's)
+  int n_groups;
+  const void *const *group_cross_k, *const *group_cross_v;
   int run() const;
 };
 
@@ -393,9 +397,10 @@ int FwdCall::run() const {
   if (n_write != 0 && n_write != nF) return fail(me, "write_slots must be all >= 0 or all -1");
   if (share_out && share_in) return fail(me, "share_out and share_in are exclusive (producer or consumer of block 0's self-attention)");
   const bool persist = n_write == nF;
-  const int n_pages = n_visible + (persist ? 0 : nF);
+  const int G = n_groups > 1 ? n_groups : 1, Fg = nF / G;       // samples, frames of each
+  const int n_pages = n_visible + (persist ? 0 : Fg);            // ... and the pages each attends to
   if (n_pages < 1 || n_pages > MMPL_MAX_PAGES) return fail(me, "too many / no visible KV pages");
-  for (int i = 0; i < n_visible; ++i)
+  for (int i = 0; i < G * n_visible; ++i)
     if (visible_slots[i] < 0 || visible_slots[i] >= n_slots) return fail(me, "visible slot out of range");
   const int nT = full ? 1 : nF;                            // timestep rows
   FwdWs w = carve_fwd(h, nF, workspace, nT);
@@ -510,19 +515,27 @@ int FwdCall::run() const {
     } else {
     {
         AttnArgs a = {};
-        a.q = w.big; a.ldq = 3 * d; a.o = w.attn; a.ldo = d; a.ldk = d; a.ldv = d; a.page_rows = S; a.Lq = Lq; a.H = H; a.scale = scale;
+        a.q = w.big; a.ldq = 3 * d; a.o = w.attn; a.ldo = d; a.ldk = d; a.ldv = d; a.page_rows = S; a.Lq = Lq / G; a.H = H; a.scale = scale;
+        // sample g (the only one unless this is mmpl_dit_forward_groups): its visible slots, then its own frames' scratch pages
+        AttnGroupPages pages[MMPL_MAX_GROUPS] = {};
         int np = 0;
-        for (int i = 0; i < n_visible; ++i, ++np) {
-          a.k_pages[np] = kc + (size_t)visible_slots[i] * S * d;
-          a.v_pages[np] = vc + (size_t)visible_slots[i] * S * d;
-        }
-        if (!persist)
-          for (int i = 0; i < nF; ++i, ++np) {
-            a.k_pages[np] = w.ksc + (size_t)i * S * d;
-            a.v_pages[np] = w.vsc + (size_t)i * S * d;
-            a.page_group[np] = 1;                      // the workspace, not the cache allocation (order independent of their addresses)
+        for (int g = 0; g < G; ++g) {
+          AttnGroupPages& pg = pages[g];
+          np = 0;
+          for (int i = 0; i < n_visible; ++i, ++np) {
+            pg.k_pages[np] = kc + (size_t)visible_slots[g * n_visible + i] * S * d;
+            pg.v_pages[np] = vc + (size_t)visible_slots[g * n_visible + i] * S * d;
           }
+          if (!persist)
+            for (int i = g * Fg; i < (g + 1) * Fg; ++i, ++np) {
+              pg.k_pages[np] = w.ksc + (size_t)i * S * d;
+              pg.v_pages[np] = w.vsc + (size_t)i * S * d;
+              pg.page_group[np] = 1;                   // the workspace, not the cache allocation (order independent of their addresses)
+            }
+          pg.n_pages = np;
+        }
         a.n_pages = np;
+        for (int i = 0; i < np; ++i) { a.k_pages[i] = pages[0].k_pages[i]; a.v_pages[i] = pages[0].v_pages[i]; a.page_group[i] = pages[0].page_group[i]; }
         a.variant = self_variant;
         a.q_prescaled = prescale_q;
         a.split_ws = (float*)w.xn;                    // norm1's output is dead once the QKV GEMM has consumed it
@@ -530,7 +543,8 @@ int FwdCall::run() const {
         a.redo_stats = h->attn_stats;
         a.history = attn_history ? (unsigned char*)attn_history + (size_t)l * hist_layer : nullptr;
         ProfScope ps(K_ATTN_SELF, 4.0 * Lq * (double)np * S * d, s);
-        MMPL_HIP_TRY(mmpl_launch_attention(a, s), "self attention");
+        if (G > 1) MMPL_HIP_TRY(mmpl_launch_attention_groups(a, G, pages, s), "self attention (grouped)");
+        else MMPL_HIP_TRY(mmpl_launch_attention(a, s), "self attention");
       }
       TRY(gemm(w.attn, d, h->Lw(l, L_O_W), d, h->Lw(l, L_O_B), w.x, d, Lq, d, d, EPI_GATE_RES, w.x, d, em + 2 * d, mfs, S, s, tc, w.splitk));
       if (l == 0 && share_out) MMPL_HIP_TRY(hipMemcpyAsync(share_out, w.x, (size_t)Lq * d * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "share block-0 x");
@@ -556,9 +570,21 @@ int FwdCall::run() const {
       else if (ctx_n >= 0) { a.page_rows = ctx_n + 1; a.last_row_copies = T - ctx_n; }   // padded tail = one key, weighted (precompute_context)
       a.k_pages[0] = (const bf16_t*)cross_k + (size_t)l * T * d;
       a.v_pages[0] = (const bf16_t*)cross_v + (size_t)l * T * d;
-      {
+      bool one_context = true;                               // every sample reads the same text K / V: one launch over all rows
+      for (int g = 1; g < G; ++g) one_context = one_context && group_cross_k[g] == cross_k && group_cross_v[g] == cross_v;
+      if (one_context) {
         ProfScope ps(K_ATTN_CROSS, 4.0 * Lq * (double)T * d, s);
         MMPL_HIP_TRY(mmpl_launch_attention(a, s), "cross attention");
+      } else {
+        for (int g = 0; g < G; ++g) {                        // ... else one launch per sample, on its rows
+          AttnArgs ag = a;
+          ag.Lq = Lq / G;
+          ag.q = a.q + (size_t)g * ag.Lq * a.ldq; ag.o = a.o + (size_t)g * ag.Lq * a.ldo;
+          ag.k_pages[0] = (const bf16_t*)group_cross_k[g] + (size_t)l * T * d;
+          ag.v_pages[0] = (const bf16_t*)group_cross_v[g] + (size_t)l * T * d;
+          ProfScope ps(K_ATTN_CROSS, 4.0 * ag.Lq * (double)T * d, s);
+          MMPL_HIP_TRY(mmpl_launch_attention(ag, s), "cross attention (per sample)");
+        }
       }
       if (h->img_k) {
         // Wan-I2V: the query also attends to the image tokens; the two outputs are summed in bf16 before the o-projection
@@ -641,6 +667,42 @@ int mmpl_dit_forward_at(MmplDit* h, const void* x_in, const float* t_dev, int nF
   a.cross_k = cross_k; a.cross_v = cross_v; a.cross_rows = cross_rows; a.share_out = share_out; a.share_in = share_in;
   a.attn_history = attn_history; a.out = out; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
   a.frame_base_dev = frame_base_dev; a.stream = stream;
+  return a.run();
+}
+
+int mmpl_dit_forward_groups(MmplDit* h, const void* x_in, const float* t_dev, int n_groups, int frames_per_group, const int* frame_ids,
+                            const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache, int n_slots,
+                            const void* const* cross_k, const void* const* cross_v, int cross_rows, void* share_out, const void* share_in,
+                            void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                            mmpl_stream_t stream) {
+  const char* me = "mmpl_dit_forward_groups";
+  if (!h) return fail(me, "null handle");
+  if (n_groups < 1) return fail(me, "n_groups < 1");
+  if (n_groups > MMPL_MAX_GROUPS) return fail(me, "more than 8 groups");
+  if (frames_per_group < 1) return fail(me, "frames_per_group < 1");
+  if ((long long)n_groups * frames_per_group > h->cfg.max_frames) return fail(me, "n_groups * frames_per_group exceeds max_frames");
+  if (share_out) return fail(me, "share_out is not available to a grouped forward (pass NULL)");
+  if (share_in) return fail(me, "share_in is not available to a grouped forward (pass NULL)");
+  if (attn_history) return fail(me, "attn_history is not available to a grouped forward: the grouped self-attention is stateless (pass NULL)");
+  if (h->img_k) return fail(me, "an i2v handle (image K / V attached) has no grouped forward");
+  if (!frame_ids || !write_slots || !cross_k || !cross_v || (n_visible > 0 && !visible_slots)) return fail(me, "null argument");
+  const int nF = n_groups * frames_per_group;
+  for (int g = 0; g < n_groups; ++g) {
+    if (!cross_k[g] || !cross_v[g]) return fail(me, "null argument");
+    for (int i = g * frames_per_group; i < (g + 1) * frames_per_group; ++i) {
+      if (write_slots[i] >= n_slots) return fail(me, "write slot out of range");
+      for (int j = 0; j < g * frames_per_group && write_slots[i] >= 0; ++j)
+        if (write_slots[j] == write_slots[i]) return fail(me, "two groups write the same slot");
+    }
+    for (int i = 0; i < n_visible; ++i)
+      if (visible_slots[g * n_visible + i] < 0 || visible_slots[g * n_visible + i] >= n_slots) return fail(me, "visible slot out of range");
+  }
+  FwdCall a = {};
+  a.me = me; a.h = h; a.x_in = x_in; a.t_dev = t_dev; a.nF = nF; a.frame_ids = frame_ids; a.write_slots = write_slots;
+  a.visible_slots = visible_slots; a.n_visible = n_visible; a.k_cache = k_cache; a.v_cache = v_cache; a.n_slots = n_slots;
+  a.cross_k = cross_k[0]; a.cross_v = cross_v[0]; a.cross_rows = cross_rows;
+  a.out = out; a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.frame_base_dev = frame_base_dev; a.stream = stream;
+  if (n_groups > 1) { a.n_groups = n_groups; a.group_cross_k = cross_k; a.group_cross_v = cross_v; }   // (one group: mmpl_dit_forward_at's launches)
   return a.run();
 }
 

@@ -392,12 +392,16 @@ __global__ __launch_bounds__(512, 2) void attn_cross_kernel(AttnArgs a, int qb_p
 
 
 // Combine the `sp` KV-range partials of each tail query block: O = sum_p w_p O_p / sum_p w_p l_p, w_p = 2^((m_p - m) c).
-__global__ __launch_bounds__(256) void attn_merge_kernel(AttnArgs a, int local_base, int sp, int tb) {
+// (n_groups > 0: the tail of a grouped launch -- (group, head) is the virtual head, the group's rows of o start at group * Lq)
+MMPL_DEV void attn_merge_block(const AttnArgs& a, int n_groups, int local_base, int sp, int tb) {
   __shared__ float wgt[QB][4];
   const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
   const int n_qb = (a.Lq + QB - 1) / QB;
   int head, qb;
-  if (!mmpl_attn_item(a.H, n_qb, xcd, local_base + k, head, qb)) return;
+  if (!mmpl_attn_item(n_groups ? n_groups * a.H : a.H, n_qb, xcd, local_base + k, head, qb)) return;
+  const int grp = n_groups ? head / a.H : 0;
+  head -= grp * a.H;
+  bf16_t* o = a.o + (size_t)grp * a.Lq * a.ldo;
   const float* base = a.split_ws + (size_t)(xcd * tb + k) * sp * (QB * 130);
   const float c = a.scale * 1.4426950408889634f;
   {
@@ -425,9 +429,13 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(AttnArgs a, int local_b
       uint2 o2;
       o2.x = pack2bf(acc[0], acc[1]);
       o2.y = pack2bf(acc[2], acc[3]);
-      *reinterpret_cast<uint2*>(a.o + (size_t)q_out * a.ldo + head * 128 + ch * 4) = o2;
+      *reinterpret_cast<uint2*>(o + (size_t)q_out * a.ldo + head * 128 + ch * 4) = o2;
     }
   }
+}
+__global__ __launch_bounds__(256) void attn_merge_kernel(AttnArgs a, int local_base, int sp, int tb) { attn_merge_block(a, 0, local_base, sp, tb); }
+__global__ __launch_bounds__(256) void attn_merge_groups_kernel(AttnGroupArgs ga, int local_base, int sp, int tb) {
+  attn_merge_block(ga.a, ga.n_groups, local_base, sp, tb);
 }
 
 }  // namespace
@@ -577,6 +585,85 @@ hipError_t mmpl_launch_attention(const AttnArgs& a_in, hipStream_t s) {
   if (p.sp > 1) {
     mmpl_launch_attention_w64(a, 8 * p.tail_items * p.sp, p.main_blocks / 8, p.sp, true, s);
     hipLaunchKernelGGL(attn_merge_kernel, dim3(8 * p.tail_items), dim3(256), 0, s, a, p.main_blocks / 8, p.sp, p.tail_items);
+  }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// n_groups attentions of equal shape (kernels.h: AttnGroupArgs, AttnGroupPlan).
+AttnGroupPlan mmpl_attn_groups_plan(const AttnArgs& common, int n_groups, const AttnGroupPages* lists) {
+  AttnGroupPlan gp = {};
+  gp.invalid = 1;
+  if (n_groups < 1 || n_groups > MMPL_MAX_GROUPS || !lists || common.Lq <= 0 || common.H <= 0) return gp;
+  const size_t hist_bytes = mmpl_attention_history_bytes(common.Lq, common.H);
+  bool can_group = !common.history;
+  int pages = 0, tiles_min = 0, tiles_max = 0;
+  AttnGroupArgs& ga = gp.ga;
+  for (int g = 0; g < n_groups; ++g) {
+    const AttnGroupPages& l = lists[g];
+    if (l.n_pages < 1 || l.n_pages > MMPL_MAX_PAGES) return gp;
+    AttnArgs& a = gp.single[g];
+    a = common;
+    a.q = common.q + (size_t)g * common.Lq * common.ldq;
+    a.o = common.o + (size_t)g * common.Lq * common.ldo;
+    if (common.history) a.history = common.history + (size_t)g * hist_bytes;
+    a.n_pages = l.n_pages;
+    for (int i = 0; i < l.n_pages; ++i) { a.k_pages[i] = l.k_pages[i]; a.v_pages[i] = l.v_pages[i]; a.page_group[i] = l.page_group[i]; }
+    const AttnPlan p = mmpl_attn_plan(a);                     // this group by itself: checks, order, merge
+    if (p.invalid) return gp;
+    if (g == 0) gp.p = p;
+    if (p.kernel != ATTN_KERNEL_W64 || pages + p.n_pages > MMPL_MAX_PAGES) can_group = false;
+    if (!can_group) continue;
+    if (g == 0) ga.a = p.args;
+    ga.page_first[g] = pages;
+    for (int i = 0; i < p.n_pages; ++i, ++pages) {
+      ga.a.k_pages[pages] = p.args.k_pages[i]; ga.a.v_pages[pages] = p.args.v_pages[i];
+      ga.a.page_rows_each[pages] = p.args.page_rows_each[i]; ga.a.page_group[pages] = p.args.page_group[i];
+    }
+    tiles_min = g == 0 || p.kv_tiles < tiles_min ? p.kv_tiles : tiles_min;
+    tiles_max = p.kv_tiles > tiles_max ? p.kv_tiles : tiles_max;
+  }
+  const int n_qb = (common.Lq + QB - 1) / QB;
+  gp.invalid = 0;
+  gp.n_groups = n_groups;
+  gp.items = n_groups * common.H * n_qb;
+  if (!can_group) return gp;                                  // one existing launch per group
+  gp.grouped = 1;
+  ga.n_groups = n_groups;
+  ga.page_first[n_groups] = pages;
+  ga.a.n_pages = pages;
+  AttnPlan& p = gp.p;
+  p.n_pages = pages;
+  p.kv_tiles = tiles_max;
+  // the tail round, by mmpl_attn_plan's rule on the virtual heads' items (see there)
+  const int per_xcd = mmpl_cus_per_xcd(), hv = n_groups * common.H, total = gp.items;
+  const int b = (hv & 7) == 0 ? total / 8 : (total + 7) / 8, tb = b % per_xcd;
+  int sp = 1;
+  if (!mmpl_config().attn_nosplit && ga.a.split_ws && b > per_xcd && tb > 0 && per_xcd / tb >= 2) {
+    sp = per_xcd / tb > 4 ? 4 : per_xcd / tb;
+    if (tiles_min / sp < 8 || (size_t)8 * tb * sp * QB * 130 * sizeof(float) > ga.a.split_ws_bytes) sp = 1;
+  }
+  p.sp = sp;
+  p.tail_items = sp == 1 ? 0 : tb;
+  p.main_blocks = 8 * (b - p.tail_items);
+  return gp;
+}
+
+hipError_t mmpl_launch_attention_groups(const AttnArgs& common, int n_groups, const AttnGroupPages* lists, hipStream_t s) {
+  const AttnGroupPlan gp = mmpl_attn_groups_plan(common, n_groups, lists);
+  if (gp.invalid) return hipErrorInvalidValue;
+  if (!gp.grouped) {
+    for (int g = 0; g < gp.n_groups; ++g)
+      if (hipError_t e = mmpl_launch_attention(gp.single[g], s); e != hipSuccess) return e;
+    return hipSuccess;
+  }
+  const AttnPlan& p = gp.p;
+  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_groups_symbol(0), mmpl_attention_w64_smem()); e != hipSuccess) return e;
+  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_groups_symbol(1), mmpl_attention_w64_smem()); e != hipSuccess) return e;
+  mmpl_launch_attention_w64_groups(gp.ga, p.main_blocks, 0, 1, false, s);
+  if (p.sp > 1) {
+    mmpl_launch_attention_w64_groups(gp.ga, 8 * p.tail_items * p.sp, p.main_blocks / 8, p.sp, true, s);
+    hipLaunchKernelGGL(attn_merge_groups_kernel, dim3(8 * p.tail_items), dim3(256), 0, s, gp.ga, p.main_blocks / 8, p.sp, p.tail_items);
   }
   return hipGetLastError();
 }

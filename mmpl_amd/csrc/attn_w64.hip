@@ -447,8 +447,12 @@ template <int MODE> MMPL_DEV void w64_pass(Ctx& k) {
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
 }
 
-template <bool SPLIT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void attn_w64_kernel(AttnArgs a, int local_base, int sp) {
+// The work of one block.  GROUPED (AttnGroupArgs, kernels.h): (group, head) is the virtual head of the item decode; the block then works
+// on its group's rows of q / o and on its group's pages [p0, p0 + n_pages), exactly as a block of an ungrouped launch with Lq = the
+// group's rows does -- the steady loop is the same, and every trip count stays block-uniform.  Ungrouped: grp = row0 = p0 = 0 are
+// compile-time constants and nothing of this exists.
+template <bool SPLIT, bool GROUPED>
+MMPL_DEV void w64_block(const AttnArgs& a, int n_groups, const int* page_first, int local_base, int sp) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 5, l31 = lane & 31;
@@ -464,8 +468,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       local = local_base + tail_idx;
       tail_idx = xcd * (gridDim.x / (8 * sp)) + tail_idx;
     }
-    if (!mmpl_attn_item(a.H, n_qb, xcd, local, head, qb)) return;     // grid padding (head counts that are no multiple of 8)
+    if (!mmpl_attn_item(GROUPED ? n_groups * a.H : a.H, n_qb, xcd, local, head, qb)) return;     // grid padding (head counts that are no multiple of 8)
   }
+  int grp = 0;
+  if constexpr (GROUPED) {
+    grp = head / a.H;
+    head -= grp * a.H;
+  }
+  const size_t row0 = GROUPED ? (size_t)grp * a.Lq : 0;                // the group's first row of q / o
+  const int p0 = GROUPED ? page_first[grp] : 0;                        // ... and its pages
+  const int n_pages = GROUPED ? page_first[grp + 1] - p0 : a.n_pages;
 
   // the accumulator file is ours: this statement makes the kernel descriptor allocate all 256 entries
   asm volatile("s_nop 0" ::: ALL_AGPRS);
@@ -480,7 +492,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int X = 0; X < 2; ++X) {
       const int qrow = min(qb * QB + wave * 64 + 32 * X + l31, a.Lq - 1);
-      const bf16_t* qp = qbase + (size_t)qrow * a.ldq;
+      const bf16_t* qp = qbase + (row0 + (size_t)qrow) * a.ldq;
       u32x4 qf[8];
 #pragma unroll
       for (int cc = 0; cc < 8; ++cc) {
@@ -497,14 +509,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 
   int T_all = 0;
-  for (int p = 0; p < a.n_pages; ++p) T_all += (a.page_rows_each[p] + KVB - 1) / KVB;
+  for (int p = 0; p < n_pages; ++p) T_all += (a.page_rows_each[p0 + p] + KVB - 1) / KVB;
   const int t_first = SPLIT ? (int)((long long)part * T_all / sp) : 0;
   const int T = SPLIT ? (int)((long long)(part + 1) * T_all / sp) - t_first : T_all;     // tiles of THIS block
 
   Ctx k;
   k.hi = hi;
-  k.k_pages = a.k_pages; k.v_pages = a.v_pages;
-  k.ldk = a.ldk; k.ldv = a.ldv; k.rows_each = a.page_rows_each; k.head = head; k.T = T;
+  k.k_pages = a.k_pages + p0; k.v_pages = a.v_pages + p0;
+  k.ldk = a.ldk; k.ldv = a.ldv; k.rows_each = a.page_rows_each + p0; k.head = head; k.T = T;
   k.drow = lane >> 4; k.dchunk = lane & 15;
   k.prow = 16 * wave + k.drow;                        // LDS row of piece 4w; piece 4w + k: + 4 k
   k.t_first = t_first;
@@ -540,8 +552,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   extern __shared__ __attribute__((aligned(16))) char w64_smem[];
   volatile int* redo = reinterpret_cast<volatile int*>(w64_smem + 2 * RING * TILE);
   const size_t hidx = (((size_t)head * n_qb + qb) << 2) | (SPLIT ? part : 0);
-  unsigned char* hist = a.history ? a.history + hidx : nullptr;
-  short* hmem = a.history ? a.history_mem + hidx * 128 + wave * 32 + l31 : nullptr;
+  unsigned char* hist = !GROUPED && a.history ? a.history + hidx : nullptr;        // (a grouped launch is stateless)
+  short* hmem = !GROUPED && a.history ? a.history_mem + hidx * 128 + wave * 32 + l31 : nullptr;
   int hstate = 0;
   if (hist) hstate = __builtin_amdgcn_readfirstlane((int)*reinterpret_cast<volatile unsigned char*>(hist));
   const bool try_fast = (hstate & 31) <= 1;
@@ -627,7 +639,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const float inv = 1.0f / l_tot;
       const int q_out = qb * QB + rr;
       if (q_out < a.Lq) {
-        bf16_t* op = a.o + (size_t)q_out * a.ldo + head * 128 + 4 * hi;
+        bf16_t* op = a.o + (row0 + (size_t)q_out) * a.ldo + head * 128 + 4 * hi;
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
@@ -642,8 +654,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
+template <bool SPLIT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void attn_w64_kernel(AttnArgs a, int local_base, int sp) {
+  w64_block<SPLIT, false>(a, 1, nullptr, local_base, sp);
+}
+// (instantiated by attn_w64_groups.hip alone: this translation unit keeps the two kernels tests/test_isa_audit.py counts)
+template <bool SPLIT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void attn_w64_groups_kernel(AttnGroupArgs ga, int local_base, int sp) {
+  w64_block<SPLIT, true>(ga.a, ga.n_groups, ga.page_first, local_base, sp);
+}
+
 }  // namespace
 
+#ifndef MMPL_ATTN_W64_GROUPS_TU
 int mmpl_attention_w64_smem() { return W64_SMEM; }
 const void* mmpl_attention_w64_symbol(int split) {
   return split ? reinterpret_cast<const void*>(attn_w64_kernel<true>) : reinterpret_cast<const void*>(attn_w64_kernel<false>);
@@ -652,3 +675,4 @@ void mmpl_launch_attention_w64(const AttnArgs& a, int blocks, int local_base, in
   if (split) hipLaunchKernelGGL(attn_w64_kernel<true>, dim3(blocks), dim3(256), W64_SMEM, s, a, local_base, sp);
   else hipLaunchKernelGGL(attn_w64_kernel<false>, dim3(blocks), dim3(256), W64_SMEM, s, a, local_base, sp);
 }
+#endif

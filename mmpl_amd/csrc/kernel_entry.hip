@@ -304,6 +304,65 @@ int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const
   LAUNCH(mmpl_launch_attention(a, (hipStream_t)stream), me);
 }
 
+// mmpl_launch_attention_groups on plain arguments: the checks of mmpl_attn_fwd_ex, once for the common arguments and once per page.
+int mmpl_attn_fwd_groups_ex(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
+                            const unsigned char* page_group, const int* group_n_pages, int n_groups, int group_rows, int ldk, int ldv,
+                            int page_rows, int num_heads, float softmax_scale, void* workspace, size_t workspace_bytes, int variant,
+                            int q_prescaled, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_attn_fwd_groups_ex";
+  if (plan_out)
+    for (int i = 0; i < 10; ++i) plan_out[i] = 0;
+  REJECT(!q || !o || !k_pages || !v_pages || !group_n_pages, me, "null argument");
+  REJECT(n_groups < 1, me, "n_groups < 1");
+  REJECT(n_groups > MMPL_MAX_GROUPS, me, "more than 8 groups");
+  REJECT(page_rows < 1 || group_rows < 1 || num_heads < 1, me, "non-positive size");
+  REJECT(!(softmax_scale > 0.f) || softmax_scale > 3.0e38f, me, "softmax_scale must be positive and finite");
+  REJECT(variant != ATTN_AUTO && variant != ATTN_LOCKSTEP && variant != ATTN_W64 && variant != ATTN_W64 + 1, me, "unknown kernel variant");
+  REJECT(ldq % 8, me, "ldq % 8");
+  REJECT(ldo % 8, me, "ldo % 8");
+  REJECT(ldk % 8, me, "ldk % 8");
+  REJECT(ldv % 8, me, "ldv % 8");
+  REJECT(ldq < 128 * num_heads, me, "ldq < 128 * num_heads");
+  REJECT(ldo < 128 * num_heads, me, "ldo < 128 * num_heads");
+  REJECT(ldk < 128 * num_heads, me, "ldk < 128 * num_heads");
+  REJECT(ldv < 128 * num_heads, me, "ldv < 128 * num_heads");
+  REJECT(misaligned(q, 16), me, "q not 16-byte aligned");
+  REJECT(misaligned(o, 16), me, "o not 16-byte aligned");
+  REJECT(misaligned(workspace, 16), me, "workspace not 16-byte aligned");
+  REJECT(misaligned(history, 2), me, "history not 2-byte aligned");
+  REJECT(misaligned(stats_dev, 8), me, "stats not 8-byte aligned");
+  AttnArgs a = {};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv;
+  a.page_rows = page_rows; a.Lq = group_rows; a.H = num_heads; a.scale = softmax_scale;
+  a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
+  a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
+  a.q_prescaled = variant == ATTN_W64 + 1 || q_prescaled != 0;
+  a.history = (unsigned char*)history;
+  a.redo_stats = (unsigned long long*)stats_dev;
+  REJECT(a.q_prescaled && mmpl_attn_resolve_variant(a) != ATTN_W64, me, "a prescaled q runs on the 64-rows-per-wave kernel only");
+  AttnGroupPages lists[MMPL_MAX_GROUPS] = {};
+  for (int g = 0, at = 0; g < n_groups; ++g) {
+    REJECT(group_n_pages[g] < 1, me, "a group with n_pages < 1");
+    REJECT(group_n_pages[g] > MMPL_MAX_PAGES, me, "a group with more than 24 pages");
+    lists[g].n_pages = group_n_pages[g];
+    for (int i = 0; i < group_n_pages[g]; ++i, ++at) {
+      REJECT(!k_pages[at] || !v_pages[at], me, "null page");
+      REJECT(misaligned(k_pages[at], 16) || misaligned(v_pages[at], 16), me, "page not 16-byte aligned");
+      lists[g].k_pages[i] = (const bf16_t*)k_pages[at]; lists[g].v_pages[i] = (const bf16_t*)v_pages[at];
+      lists[g].page_group[i] = page_group ? page_group[at] : 0;
+    }
+  }
+  const AttnGroupPlan gp = mmpl_attn_groups_plan(a, n_groups, lists);
+  REJECT(gp.invalid, me, "invalid argument");                 // the launcher's own rejections, all stated above: a guard
+  if (plan_out) {
+    const AttnPlan& p = gp.p;
+    plan_out[0] = p.kernel; plan_out[1] = p.n_pages; plan_out[2] = p.kv_tiles; plan_out[3] = p.main_blocks;
+    plan_out[4] = p.tail_items; plan_out[5] = p.sp; plan_out[6] = p.qb_per_block; plan_out[7] = p.blocks_per_head;
+    plan_out[8] = gp.grouped; plan_out[9] = gp.items;
+  }
+  LAUNCH(mmpl_launch_attention_groups(a, n_groups, lists, (hipStream_t)stream), me);
+}
+
 int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long fs1, int C0, int C1, int up, int ntaps,
                     const void* Wfrag, const void* bias, int Nw, int N, int T, int Ho, int Wo, void* dst, long long fsd, int ldd,
                     int Nsplit, int relu, const void* skip, long long fss, void* keep, mmpl_stream_t stream) {

@@ -115,6 +115,19 @@ __device__ __forceinline__ bool mmpl_attn_item(int H, int n_qb, int xcd, int loc
   qb = item % n_qb;
   return true;
 }
+// Grouped launch of attn_w64_kernel (attn_w64_groups.hip): n_groups independent attentions of equal shape in ONE launch -- the
+// samples of a batched few-step forward, whose query rows must see their own sample's cache slots only.  `a` is an ordinary AttnArgs
+// with Lq = the rows of ONE group (any count: every group has ceil(Lq / 256) query blocks of its own, the last one partial, no block
+// straddles two groups); group g's queries are rows g * Lq .. of a.q / a.o, and it walks pages page_first[g] .. page_first[g + 1] - 1
+// of a.k_pages / a.v_pages / a.page_rows_each (each group's list merged and ordered by itself; a.n_pages = page_first[n_groups] <=
+// MMPL_MAX_PAGES).  (group, head) is a virtual head of mmpl_attn_item's decode: n_groups * H of them.  Stateless: a.history is NULL.
+// A second struct, not fields of AttnArgs: an ungrouped launch carries and runs exactly what it did before this existed.
+constexpr int MMPL_MAX_GROUPS = 8;
+struct AttnGroupArgs {
+  AttnArgs a;
+  int n_groups;
+  int page_first[MMPL_MAX_GROUPS + 1];
+};
 enum { ATTN_AUTO = 0, ATTN_LOCKSTEP = 1, ATTN_W64 = 3 };      // (2 was the round-1 ping-pong kernel, removed)
 // The kernel ATTN_AUTO resolves to for a self-attention launch whose producer can fold the softmax scale into q before q is
 // rounded to bf16 (the DiT forward: qknorm_kernel's q_scale).  ATTN_W64 computes exp2(K.q) without a per-score multiply, so it
@@ -125,6 +138,9 @@ int mmpl_attention_self_variant();
 int mmpl_attention_w64_smem();
 const void* mmpl_attention_w64_symbol(int split);
 void mmpl_launch_attention_w64(const AttnArgs& a, int blocks, int local_base, int sp, bool split, hipStream_t s);
+// attn_w64_groups.hip: the grouped instantiations of the same kernel body (same shared memory)
+const void* mmpl_attention_w64_groups_symbol(int split);
+void mmpl_launch_attention_w64_groups(const AttnGroupArgs& ga, int blocks, int local_base, int sp, bool split, hipStream_t s);
 size_t mmpl_attention_split_ws_bytes();     // upper bound of what a launch can use
 // What mmpl_launch_attention does with an AttnArgs: every choice of the launcher is made by mmpl_attn_plan and nowhere else (the
 // launcher reads it from the plan; mmpl_attn_fwd_ex reports it to the tests).  Host arithmetic on the arguments and the run-time
@@ -151,6 +167,30 @@ AttnPlan mmpl_attn_plan(const AttnArgs& a);
 inline size_t mmpl_attention_history_state_bytes(int Lq, int H) { return ((size_t)H * ((Lq + 255) / 256) * 4 + 255) & ~(size_t)255; }
 inline size_t mmpl_attention_history_bytes(int Lq, int H) { return mmpl_attention_history_state_bytes(Lq, H) + (size_t)H * ((Lq + 255) / 256) * 4 * 128 * sizeof(short); }
 hipError_t mmpl_launch_attention(const AttnArgs& a, hipStream_t s);
+// n_groups attentions of equal shape (AttnGroupArgs above), as the caller states them: `common` is the AttnArgs of ONE group (q / o:
+// group 0's first row; Lq = rows of a group; its own page fields are ignored), lists[g] the pages of group g.  common.history, when
+// not NULL, is n_groups regions of mmpl_attention_history_bytes(Lq, H), group g's at g times that.
+struct AttnGroupPages {
+  int n_pages;
+  const bf16_t* k_pages[MMPL_MAX_PAGES]; const bf16_t* v_pages[MMPL_MAX_PAGES];
+  unsigned char page_group[MMPL_MAX_PAGES];
+};
+// Every choice of mmpl_launch_attention_groups is made here.  Each group's list is planned by itself first (mmpl_attn_plan: checks,
+// order, merge).  ONE grouped launch needs every group on attn_w64_kernel (so not MMPL_ATTN_V1), no history and at most MMPL_MAX_PAGES
+// merged pages in all; anything else runs as one mmpl_launch_attention per group (grouped == 0), which computes the same.  The grouped
+// launch's split-KV tail follows mmpl_attn_plan's rule on the TOTAL item count n_groups * H * ceil(Lq / 256) (and on the shortest
+// group's KV tiles, where the rule asks for 8 tiles per part).
+struct AttnGroupPlan {
+  int invalid;            // the launcher answers hipErrorInvalidValue and launches nothing
+  int grouped;            // 1: one grouped launch of `ga` by `p`; 0: n_groups launches of single[g]
+  int n_groups, items;    // items: (group, head, query block) work items in all
+  AttnPlan p;             // grouped: kernel, n_pages (all groups), kv_tiles (the longest group's), main_blocks, tail_items, sp;
+                          // per group: group 0's plan
+  AttnGroupArgs ga;
+  AttnArgs single[MMPL_MAX_GROUPS];   // what each group's own launch receives (before its own plan)
+};
+AttnGroupPlan mmpl_attn_groups_plan(const AttnArgs& common, int n_groups, const AttnGroupPages* lists);
+hipError_t mmpl_launch_attention_groups(const AttnArgs& common, int n_groups, const AttnGroupPages* lists, hipStream_t s);
 
 // ---------------------------------------------------------------- norms / rope / elementwise (elementwise.hip)
 // LayerNorm (eps, fp32 stats) fused with per-frame modulation  y = bf16(bf16(LN(x)) * bf16(1+scale)) + shift

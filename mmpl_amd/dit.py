@@ -314,6 +314,39 @@ class DitEngine:
                 _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base), _lib.stream_ptr()), "mmpl_dit_forward")
         return out
 
+    def forward_groups(self, x: torch.Tensor, t: torch.Tensor, n_groups: int, frame_ids: Sequence[int], write_slots: Sequence[int],
+                       visible_slots: Sequence[Sequence[int]], k_cache: torch.Tensor, v_cache: torch.Tensor,
+                       cross: Sequence[Tuple[torch.Tensor, torch.Tensor]], out: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None, cross_rows: Optional[int] = None,
+                       frame_base: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`forward` over a batch of `n_groups` independent samples in the launches of one forward (mmpl_dit_forward_groups).
+        x: [n_groups * F, in_dim, lat_h, lat_w], sample-major; t, frame_ids, write_slots: per frame, likewise.  visible_slots: one list
+        per sample, all of one length -- each sample attends to ITS slots of the one cache only, so give sample g slots of its own
+        (`KVCache(engine, W, batch=G)`: g * W ..).  cross: one (cross_k, cross_v) per sample; when all are the same tensors the text
+        cross-attention is one launch over all rows, else one per sample.  cross_rows: must hold for every sample's contents (the
+        largest of their `CrossKV.rows`).  n_groups * F <= max_frames.  No share buffers, no attention history, no i2v."""
+        nF = x.shape[0]
+        assert n_groups >= 1 and nF % n_groups == 0, (n_groups, nF)
+        assert x.is_contiguous() and x.dtype == torch.bfloat16 and x.shape[1:] == (self.in_dim, self.lat_h, self.lat_w)
+        assert t.dtype == torch.float32 and t.numel() == nF and t.is_cuda
+        assert len(visible_slots) == n_groups and len({len(v) for v in visible_slots}) == 1 and len(cross) == n_groups
+        assert len(frame_ids) == nF and len(write_slots) == nF
+        if frame_base is not None:
+            assert frame_base.dtype == torch.int32 and frame_base.numel() == 1 and frame_base.device == x.device
+        out = self._checked_out(x, None, None, None, out)
+        ws = self.workspace(nF) if workspace is None else workspace
+        n_slots = k_cache.shape[1] // self.S
+        ia = lambda v: (C.c_int * max(len(v), 1))(*[int(i) for i in v])
+        pa = lambda ts: (C.c_void_p * n_groups)(*[tt.data_ptr() for tt in ts])
+        with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
+            _lib.check(self._lib.mmpl_dit_forward_groups(
+                self._h, _lib.ptr(x), _lib.ptr(t), n_groups, nF // n_groups, ia(frame_ids), ia(write_slots),
+                ia([s for v in visible_slots for s in v]), len(visible_slots[0]), _lib.ptr(k_cache), _lib.ptr(v_cache), n_slots,
+                pa([c[0] for c in cross]), pa([c[1] for c in cross]), self.text_len if cross_rows is None else int(cross_rows),
+                None, None, None, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base), _lib.stream_ptr()),
+                "mmpl_dit_forward_groups")
+        return out
+
     def _checked_out(self, x: torch.Tensor, share_out, share_in, attn_history, out: Optional[torch.Tensor]) -> torch.Tensor:
         """Both forwards' checks of the optional tensors (share buffers, attention history) against x's frame count and device;
         returns `out`, allocated when None."""

@@ -67,11 +67,12 @@ class CausalInferencePipeline(GeneratorPipeline):
         self.noise_generator: Optional[torch.Generator] = None       # None = the device's default generator (torch.randn_like)
         self.graph_captures = 0           # hipGraphs constructed so far (tests: none after the first call)
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
-        self._bufs: Dict[int, dict] = {}  # static per-block buffers, by frames per block
-        self._out: Dict[int, torch.Tensor] = {}                     # static output latents, by frame count
+        self._bufs: Dict[object, dict] = {}  # static per-block buffers, by frames per block (a batch: by (frames per block, B))
+        self._out: Dict[object, torch.Tensor] = {}                  # static output latents, by frame count (a batch: (frame count, B))
+        self._caches: Dict[int, tuple] = {}                         # (kv_cache1, crossattn_cache) by batch: the graphs hold their addresses
         self._roll_bufs: Dict[tuple, torch.Tensor] = {}             # rolling blocks past the window: static x0, by graph key
         self._frame_base: Optional[torch.Tensor] = None             # ... and the int32 device scalar their RoPE positions start from
-        self._stores = (self._graphs, self._bufs, self._out, self._roll_bufs)
+        self._stores = (self._graphs, self._bufs, self._out, self._roll_bufs)     # (not _caches: kv_cache1 outlives the graphs, as ever)
         self._side: Optional[torch.cuda.Stream] = None              # inference_stream: the decode stream
         self._stage: Optional[torch.Tensor] = None                  # inference_stream: pinned uint8 staging, [2, frames, H, W, 3]
 
@@ -99,23 +100,28 @@ class CausalInferencePipeline(GeneratorPipeline):
         """(engine timestep, sigma of the x0 conversion, sigma of the next step's add_noise) per step: a forward at every one."""
         return fewstep_scalars(self.generator, self.denoising_step_list, len(self.denoising_step_list))
 
-    def _block_buffers(self, F: int) -> dict:
-        b = self._bufs.get(F)
+    def _block_buffers(self, F: int, B: int = 1) -> dict:
+        """x / flow [B*F, 16, h, w] and t [B*F], sample-major; the bank [n - 1, B, F, 16, h, w] (one draw of the reference's
+        [B, F, 16, h, w] per step: bank[i] viewed [B*F, ...] is the step's noise in x's layout)."""
+        key = F if B == 1 else (F, B)
+        b = self._bufs.get(key)
         if b is None:
             g, dev = self.geometry, self.device
             n = len(self.denoising_step_list)
-            shape = (F, 16, g.lat_h, g.lat_w)
+            frame = (16, g.lat_h, g.lat_w)
+            shape = (B * F,) + frame
             b = dict(x=torch.empty(shape, dtype=torch.bfloat16, device=dev), flow=torch.empty(shape, dtype=torch.bfloat16, device=dev),
-                     t=torch.empty(F, dtype=torch.float32, device=dev),
-                     bank=torch.empty((max(n - 1, 1),) + shape, dtype=torch.bfloat16, device=dev))
-            self._bufs[F] = b
+                     t=torch.empty(B * F, dtype=torch.float32, device=dev),
+                     bank=torch.empty((max(n - 1, 1),) + ((F,) if B == 1 else (B, F)) + frame, dtype=torch.bfloat16, device=dev))
+            self._bufs[key] = b
         return b
 
-    def _output(self, T: int) -> torch.Tensor:
-        o = self._out.get(T)
+    def _output(self, T: int, B: int = 1) -> torch.Tensor:
+        key = T if B == 1 else (T, B)
+        o = self._out.get(key)
         if o is None:
             g = self.geometry
-            o = self._out[T] = torch.zeros(1, T, 16, g.lat_h, g.lat_w, dtype=torch.bfloat16, device=self.device)
+            o = self._out[key] = torch.zeros(B, T, 16, g.lat_h, g.lat_w, dtype=torch.bfloat16, device=self.device)
         return o
 
     def _run_block(self, b: dict, out_blk: torch.Tensor, start: int, write, vis, scalars, frame_base=None) -> None:
@@ -135,12 +141,13 @@ class CausalInferencePipeline(GeneratorPipeline):
         gen.flow(out_blk, b["t"], start, write, vis, kv, cross, out=b["flow"], frame_base=frame_base)
 
     def _context_forward(self, lat: torch.Tensor, start: int) -> None:
-        """A clean-latent forward at t = 0 that only fills the cache (initial_latent, causal_inference.py:130-159)."""
-        x = lat.to(device=self.device, dtype=torch.bfloat16).contiguous()
-        write, vis, le = self.generator.slots(self.kv_cache1, start, x.shape[0], rolling=self.rolling_kv)
+        """A clean-latent forward at t = 0 that only fills the cache (initial_latent, causal_inference.py:130-159); lat [B, F, ...]."""
+        B, F = lat.shape[:2]
+        x = lat.to(device=self.device, dtype=torch.bfloat16).reshape((B * F,) + tuple(lat.shape[2:])).contiguous()
+        write, vis, le = self.generator.slots(self.kv_cache1, start, F, rolling=self.rolling_kv, **({"batch": B} if B > 1 else {}))
         t = torch.zeros(x.shape[0], dtype=torch.float32, device=self.device)
         self.generator.flow(x, t, start, write, vis, self.kv_cache1, self.crossattn_cache)
-        self.generator.set_cache_ends(self.kv_cache1, start + x.shape[0], le)
+        self.generator.set_cache_ends(self.kv_cache1, start + F, le)
 
     def _blocks(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None):
         """The denoising loop ``inference()`` and ``inference_stream()`` share (causal_inference.py:82-211), as a generator over
@@ -149,7 +156,16 @@ class CausalInferencePipeline(GeneratorPipeline):
         frames ``output[0, start:start + n_frames]`` are complete in stream order on the current stream.  The caller holds
         ``torch.no_grad()`` around every resumption."""
         batch_size, num_frames, num_channels, height, width = noise.shape
-        assert batch_size == 1, "batch size 1 (as every reference entry point)"
+        B = batch_size
+        if len(text_prompts) != B:
+            raise ValueError(f"{len(text_prompts)} prompts for a noise batch of {B}")
+        if initial_latent is not None and initial_latent.shape[0] != B:
+            raise ValueError(f"initial_latent holds {initial_latent.shape[0]} samples, the noise {B}")
+        max_frames = self.generator.engine.max_frames
+        if B * self.num_frame_per_block > max_frames:                     # the batch runs as ONE forward over B * F frames
+            raise ValueError(f"batch {B} x num_frame_per_block {self.num_frame_per_block} = {B * self.num_frame_per_block} frames "
+                             f"per forward exceeds the engine's limit of {max_frames} (max_frames): at most "
+                             f"{max_frames // self.num_frame_per_block} samples per call")
         assert (num_channels, height, width) == (16, self.geometry.lat_h, self.geometry.lat_w), tuple(noise.shape)
         schedule = self.block_schedule(num_frames, initial_latent)
         num_input_frames = initial_latent.shape[1] if initial_latent is not None else 0
@@ -165,17 +181,25 @@ class CausalInferencePipeline(GeneratorPipeline):
                 rolling_slots(0, F, W, int(self.generator.model.sink_size))   # sink_size / block size against the window
         conditional_dict = self.text_encoder(text_prompts=text_prompts)
 
-        if self.kv_cache1 is None:
-            self.kv_cache1 = self.generator.new_kv_cache()
-            self.crossattn_cache = self.generator.new_crossattn_cache()
+        gen = self.generator
+        if self.kv_cache1 is not None:                                    # (the current pair, a caller-installed one included)
+            self._caches.setdefault(getattr(self.kv_cache1, "batch", 1), (self.kv_cache1, self.crossattn_cache))
+        if B not in self._caches:
+            self._caches[B] = (gen.new_kv_cache(), gen.new_crossattn_cache()) if B == 1 else (gen.new_kv_cache(batch=B), gen.new_crossattn_cache(B))
         else:                                                             # :113-123
-            for blk in self.crossattn_cache:
+            for blk in self._caches[B][1]:
                 blk["is_init"] = False
-            self.generator.set_cache_ends(self.kv_cache1, 0, 0)
-        self.crossattn_cache.fill(conditional_dict["prompt_embeds"])
+            self.generator.set_cache_ends(self._caches[B][0], 0, 0)
+        self.kv_cache1, self.crossattn_cache = self._caches[B]
+        # one prompt for every sample: sample 0's text K / V serve all, and the text cross-attention stays one launch
+        shared = B > 1 and all(p == text_prompts[0] for p in text_prompts)
+        if B == 1:
+            self.crossattn_cache.fill(conditional_dict["prompt_embeds"])
+        else:
+            self.crossattn_cache.fill(conditional_dict["prompt_embeds"], shared=shared)
 
         noise_bf = noise.to(device=dev, dtype=torch.bfloat16).contiguous()
-        output = self._output(num_output_frames)
+        output = self._output(num_output_frames, B)
         output.zero_()
         current_start_frame = 0
         if initial_latent is not None:                                    # :126-159
@@ -185,7 +209,7 @@ class CausalInferencePipeline(GeneratorPipeline):
                 assert (num_input_frames - 1) % F == 0
                 num_input_blocks = (num_input_frames - 1) // F
                 output[:, :1] = init[:, :1]
-                self._context_forward(init[0, :1], current_start_frame)
+                self._context_forward(init[:, :1], current_start_frame)
                 current_start_frame += 1
             else:
                 assert num_input_frames % F == 0
@@ -193,7 +217,7 @@ class CausalInferencePipeline(GeneratorPipeline):
             for _ in range(num_input_blocks):
                 ref = init[:, current_start_frame:current_start_frame + F]
                 output[:, current_start_frame:current_start_frame + F] = ref
-                self._context_forward(ref[0], current_start_frame)
+                self._context_forward(ref, current_start_frame)
                 current_start_frame += F
         yield 0, current_start_frame, output
 
@@ -202,26 +226,33 @@ class CausalInferencePipeline(GeneratorPipeline):
         draws = iter(self.renoise_override) if self.renoise_override is not None else None
         for F in schedule:
             s = current_start_frame
-            b = self._block_buffers(F)
-            write, vis, le = self.generator.slots(self.kv_cache1, s, F, rolling=self.rolling_kv)   # (rolling: checks the RoPE range)
-            b["x"].copy_(noise_bf[0, s - num_input_frames:s - num_input_frames + F])
+            b = self._block_buffers(F, B)
+            write, vis, le = self.generator.slots(self.kv_cache1, s, F, rolling=self.rolling_kv,      # (rolling: checks the RoPE range)
+                                                  **({"batch": B} if B > 1 else {}))
+            b["x"].view((B, F) + tuple(b["x"].shape[1:])).copy_(noise_bf[:, s - num_input_frames:s - num_input_frames + F])
             fill_bank(b["bank"], n - 1, draws, self.noise_generator)
             rolled = self.rolling_kv and s + F > W                        # a frame at or past the window: position-free launches
+            # a batch's block is [B*F, ...] sample-major, which is no slice of output [B, T, ...]: like a rolled block it writes its x0
+            # into a static buffer of its own that is then copied out; the graph keys of a batch carry B and whether the samples
+            # share one context (B == 1: the keys, buffers and graphs this pipeline always had)
+            batch_key = (B, shared) if B > 1 else ()
+            vis_key = tuple(map(tuple, vis)) if B > 1 else tuple(vis)
             if not rolled:
                 out_blk, rel, base = output[0, s:s + F], s, None
                 key = (s, F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), num_output_frames, tuple(write),
-                       tuple(vis))
+                       vis_key) + batch_key
             else:
                 # the slots say WHERE in the ring the block sits, and that repeats; WHEN it sits there is the device scalar, and
                 # its x0 goes to a buffer of the pattern's own: neither the start frame nor an address of `output` is in the launches
-                key = ("rolling", F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), tuple(write), tuple(vis))
+                key = ("rolling", F, tuple(scalars[0]), float(getattr(self.args, "context_noise", 0)), tuple(write), vis_key) + batch_key
                 if self._frame_base is None:
                     self._frame_base = torch.zeros((), dtype=torch.int32, device=dev)
+                rel, base = 0, self._frame_base
+                base.fill_(s)                                             # in stream order ahead of the launches that read it
+            if rolled or B > 1:
                 out_blk = self._roll_bufs.get(key)
                 if out_blk is None:
                     out_blk = self._roll_bufs[key] = torch.empty_like(b["x"])
-                rel, base = 0, self._frame_base
-                base.fill_(s)                                             # in stream order ahead of the launches that read it
             g = self._graphs.get(key)
             if g is not None:
                 g.replay()
@@ -229,16 +260,19 @@ class CausalInferencePipeline(GeneratorPipeline):
                 g = eager_then_capture(self, lambda: self._run_block(b, out_blk, rel, write, vis, scalars, base))
                 if g is not None:
                     self._graphs[key] = g
-            if rolled:
-                output[0, s:s + F].copy_(out_blk)                         # on the compute stream: complete before the yield's consumers
+            if rolled or B > 1:                                           # on the compute stream: complete before the yield's consumers
+                output[:, s:s + F].copy_(out_blk.view((B, F) + tuple(out_blk.shape[1:])))
             self.generator.set_cache_ends(self.kv_cache1, s + F, le)
             current_start_frame += F
             yield s, F, output
 
     def inference(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
                   return_latents: bool = False, profile: bool = False, low_memory: bool = False):
-        """noise [1, F, 16, h, w]; initial_latent [1, n, 16, h, w] or None.  Returns video [1, T, 3, 8h, 8w] in [0, 1] (and the
-        latents [1, n + F, 16, h, w]).  low_memory is accepted and has no effect (everything stays resident)."""
+        """noise [B, F, 16, h, w]; one prompt per sample; initial_latent [B, n, 16, h, w] or None.  Returns video [B, T, 3, 8h, 8w] in
+        [0, 1] (and the latents [B, n + F, 16, h, w]).  The samples of a batch are independent and run as ONE forward over
+        B * num_frame_per_block frames per step (DitEngine.forward_groups), so B * num_frame_per_block <= the engine's max_frames;
+        the re-noise draws are one [B, F, 16, h, w] per non-final step, the reference's.  low_memory is accepted and has no effect
+        (everything stays resident)."""
         dev = self.device
         with torch.no_grad():
             if profile:
@@ -274,7 +308,7 @@ class CausalInferencePipeline(GeneratorPipeline):
                 vae_start.record()
 
             latents = output.clone().to(noise.dtype)
-            video = decode_video(self.vae, output.clone(), use_cache=False)
+            video = torch.cat([decode_video(self.vae, output[g:g + 1].clone(), use_cache=False) for g in range(output.shape[0])])
 
             if profile:
                 vae_end.record()
@@ -349,6 +383,9 @@ class CausalInferencePipeline(GeneratorPipeline):
         if decoder not in ("vae", "preview"):
             raise ValueError(f"decoder {decoder!r}: 'vae' or 'preview'")
         preview = decoder == "preview"
+        if noise.shape[0] != 1:
+            raise ValueError(f"inference_stream keeps batch size 1 (the noise holds {noise.shape[0]} samples): the block-wise decode "
+                             "streams one video; batches run through inference()")
         if preview and self.preview_vae is None:
             raise ValueError("decoder='preview' needs a preview decoder: CausalInferencePipeline(..., preview_vae=TAEHVWrapper(...))")
         compute = torch.cuda.current_stream(self.device)

@@ -65,19 +65,22 @@ def _conditioning_video(y, engine: DitEngine, who: str) -> torch.Tensor:
 
 
 class KVCache(list):
-    """list of per-layer dicts like the reference's kv_cache; `k_all` / `v_all`: [L, n_slots*S, dim]."""
+    """list of per-layer dicts like the reference's kv_cache; `k_all` / `v_all`: [L, batch*n_slots*S, dim].  ``batch`` samples
+    share the one allocation, sample g owning frame slots ``g*n_slots .. g*n_slots + n_slots - 1`` (DitEngine.forward_groups); the
+    per-layer views are the reference's [batch, n_slots*S, H, 128]."""
 
-    def __init__(self, engine: DitEngine, n_slots: int = 15):
+    def __init__(self, engine: DitEngine, n_slots: int = 15, batch: int = 1):
         super().__init__()
         self.engine = engine
-        self.k_all, self.v_all = engine.new_kv_cache(n_slots)
+        self.n_slots, self.batch = int(n_slots), int(batch)
+        self.k_all, self.v_all = engine.new_kv_cache(self.batch * self.n_slots)
         self.vis: List[int] = []          # token offsets, shared by every layer (the reference keeps L identical copies)
         # what the self-attention's softmax passes did on this branch's previous forward (DitEngine.new_attn_history): travels with
         # the cache because it is per CFG branch; the pipeline zeroes it at every stage boundary.  None = stateless attention.
         self.attn_history: Optional[torch.Tensor] = None
         H = engine.cfg["num_heads"]
         for l in range(engine.L):
-            self.append({"k": self.k_all[l].view(1, -1, H, 128), "v": self.v_all[l].view(1, -1, H, 128),
+            self.append({"k": self.k_all[l].view(self.batch, -1, H, 128), "v": self.v_all[l].view(self.batch, -1, H, 128),
                          "global_end_index": torch.tensor([0], dtype=torch.long),
                          "local_end_index": torch.tensor([0], dtype=torch.long),
                          "attention_vis_index": self.vis})
@@ -98,27 +101,41 @@ class KVCache(list):
 
 
 class CrossAttnCache(list):
-    """list of per-layer dicts {"k","v","is_init"}; K/V for all layers are filled by one precompute call."""
+    """list of per-layer dicts {"k","v","is_init"}; K/V for all layers are filled by one precompute call per sample.  ``batch``
+    samples: `k_b` / `v_b` [batch, L, text_len, dim], `k_all` / `v_all` sample 0's; the per-layer views are [batch, text_len, H, 128]."""
 
-    def __init__(self, engine: DitEngine):
+    def __init__(self, engine: DitEngine, batch: int = 1):
         super().__init__()
-        self.engine = engine
-        self.k_all = torch.zeros(engine.L, engine.text_len, engine.dim, dtype=torch.bfloat16, device=engine.device)
-        self.v_all = torch.zeros_like(self.k_all)
+        self.engine, self.batch = engine, int(batch)
+        self.k_b = torch.zeros(self.batch, engine.L, engine.text_len, engine.dim, dtype=torch.bfloat16, device=engine.device)
+        self.v_b = torch.zeros_like(self.k_b)
+        self.k_all, self.v_all = self.k_b[0], self.v_b[0]
         self.rows = engine.text_len       # rows `rows .. text_len-1` of k_all / v_all repeat one row (CrossKV.rows of the contents)
+        self.shared = self.batch == 1     # every sample reads sample 0's K / V (one prompt for all): `pairs`
         H = engine.cfg["num_heads"]
         for l in range(engine.L):
-            self.append({"k": self.k_all[l].view(1, -1, H, 128), "v": self.v_all[l].view(1, -1, H, 128), "is_init": False})
+            self.append({"k": self.k_b[:, l].view(self.batch, -1, H, 128), "v": self.v_b[:, l].view(self.batch, -1, H, 128), "is_init": False})
 
     @property
     def is_init(self) -> bool:
         return all(b["is_init"] for b in self)
 
-    def fill(self, prompt_embeds: torch.Tensor):
-        """prompt_embeds: [T, D], or a text encoder's [1, T, D]."""
-        self.rows = self.engine.precompute_context(_unbatched(prompt_embeds), out=(self.k_all, self.v_all)).rows
+    def fill(self, prompt_embeds: torch.Tensor, shared: bool = False):
+        """prompt_embeds: [T, D], or a text encoder's [batch, T, D].  ``shared``: the caller's statement that every sample's prompt is
+        the same one -- sample 0's K / V are computed and serve all (the forward's text cross-attention is then one launch)."""
+        pe = prompt_embeds.unsqueeze(0) if prompt_embeds.dim() == 2 else prompt_embeds
+        if self.batch > 1 and pe.shape[0] != self.batch:
+            raise ValueError(f"CrossAttnCache: {pe.shape[0]} prompts for a batch of {self.batch}")
+        self.shared = bool(shared) or self.batch == 1
+        rows = [self.engine.precompute_context(pe[g], out=(self.k_all, self.v_all) if g == 0 else (self.k_b[g], self.v_b[g])).rows
+                for g in range(1 if self.shared else self.batch)]
+        self.rows = max(rows)             # (the statement holds for every sample at the largest of their counts)
         for b in self:
             b["is_init"] = True
+
+    def pairs(self):
+        """(cross_k, cross_v) per sample, as DitEngine.forward_groups takes them."""
+        return [(self.k_b[0 if self.shared else g], self.v_b[0 if self.shared else g]) for g in range(self.batch)]
 
 
 class _HeldGraph:
@@ -179,8 +196,8 @@ class _GeneratorBase(torch.nn.Module):
     def get_scheduler(self) -> FlowMatchScheduler:
         return self.scheduler
 
-    def new_crossattn_cache(self) -> CrossAttnCache:
-        return CrossAttnCache(self.engine)
+    def new_crossattn_cache(self, batch: int = 1) -> CrossAttnCache:
+        return CrossAttnCache(self.engine, batch)
 
 
 class WanFPSWrapper(_GeneratorBase):
@@ -574,9 +591,9 @@ class WanDiffusionWrapper(_GeneratorBase):
         """max_attention_size in frames: 32760 tokens = 21 frames (local_attn_size == -1) or local_attn_size (causal_model.py:76)."""
         return self.geometry.frames_per_chunk if self.local_attn_size == -1 else self.local_attn_size
 
-    def new_kv_cache(self, n_slots: Optional[int] = None) -> KVCache:
-        """The reference's kv_cache1 (causal_inference.py:278-297): local_attn_size frames, or 32760 tokens = 21 frames."""
-        return KVCache(self.engine, self.window_frames if n_slots is None else n_slots)
+    def new_kv_cache(self, n_slots: Optional[int] = None, batch: int = 1) -> KVCache:
+        """The reference's kv_cache1 (causal_inference.py:278-297): local_attn_size frames, or 32760 tokens = 21 frames, per sample."""
+        return KVCache(self.engine, self.window_frames if n_slots is None else n_slots, batch)
 
     # -- host scalars of the reference's timestep -> sigma lookups ------------------------------------------------------------
     def sigma_x0(self, timestep) -> float:
@@ -591,18 +608,27 @@ class WanDiffusionWrapper(_GeneratorBase):
         return float(s.sigmas[torch.argmin((s.timesteps.unsqueeze(0) - t.unsqueeze(1)).abs(), dim=1)].item())
 
     # -- device pieces (capturable) ------------------------------------------------------------------------------------------
-    def slots(self, kv_cache: KVCache, start_frame: int, n_frames: int, rolling: bool = False):
+    def slots(self, kv_cache: KVCache, start_frame: int, n_frames: int, rolling: bool = False, batch: int = 1):
         """(write_slots, visible_slots, local_end) of a forward at `start_frame` against `kv_cache`'s current bookkeeping.
         ``rolling``: the rolling window with ``model.sink_size`` sink frames (``rolling_slots``) over a cache of exactly
-        ``window_frames`` slots; local_end is then ``min(start + n, window)``, what ``set_cache_ends`` records."""
-        n_slots = kv_cache.k_all.shape[1] // self.engine.S
+        ``window_frames`` slots; local_end is then ``min(start + n, window)``, what ``set_cache_ends`` records.
+        ``batch`` > 1 (a ``KVCache(..., batch=G)``; every sample is at the same frame): sample g's slots are sample 0's plus
+        ``g * kv_cache.n_slots`` -- write_slots sample-major for all ``G * n_frames`` frames, visible_slots one list per sample."""
+        G = getattr(kv_cache, "batch", 1)
+        if batch != G:
+            raise ValueError(f"slots: batch {batch} against a KV cache for {G} samples")
+        n_slots = kv_cache.k_all.shape[1] // self.engine.S // G          # frame slots of ONE sample
         if rolling:
             if n_slots != self.window_frames:
                 raise ValueError(f"rolling KV window: the cache holds {n_slots} frame slots, the window is {self.window_frames}")
             write, vis = rolling_slots(start_frame, n_frames, self.window_frames, int(self.model.sink_size))
-            return write, vis, min(start_frame + n_frames, self.window_frames)
-        return causal_slots(start_frame, n_frames, n_slots, self.window_frames, int(kv_cache[0]["local_end_index"][0]),
-                            int(kv_cache[0]["global_end_index"][0]))
+            le = min(start_frame + n_frames, self.window_frames)
+        else:
+            write, vis, le = causal_slots(start_frame, n_frames, n_slots, self.window_frames, int(kv_cache[0]["local_end_index"][0]),
+                                          int(kv_cache[0]["global_end_index"][0]))
+        if batch == 1:
+            return write, vis, le
+        return [w + g * n_slots for g in range(batch) for w in write], [[v + g * n_slots for v in vis] for g in range(batch)], le
 
     @staticmethod
     def set_cache_ends(kv_cache: KVCache, global_end_frame: int, local_end_frame: int) -> None:
@@ -617,7 +643,14 @@ class WanDiffusionWrapper(_GeneratorBase):
              frame_base: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One CausalWanModel._forward_inference on explicit slots: x [F, 16, h, w] bf16, t [F] float32 on the device.  Stateless
         attention; the text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch).
-        ``frame_base`` (int32 device scalar): `start_frame` is then relative to its value at execution time (DitEngine.forward)."""
+        ``frame_base`` (int32 device scalar): `start_frame` is then relative to its value at execution time (DitEngine.forward).
+        A ``KVCache(..., batch=G)``: x [G*F, 16, h, w] and t [G*F] sample-major, slots as ``slots(..., batch=G)`` gives them, every
+        sample at `start_frame` (DitEngine.forward_groups)."""
+        G = getattr(kv_cache, "batch", 1)
+        if G > 1:
+            frames = [start_frame + i for _ in range(G) for i in range(x.shape[0] // G)]
+            return self.engine.forward_groups(x, t, G, frames, write_slots, visible_slots, kv_cache.k_all, kv_cache.v_all,
+                                              crossattn_cache.pairs(), out=out, frame_base=frame_base)
         frames = [start_frame + i for i in range(x.shape[0])]
         return self.engine.forward(x, t, frames, write_slots, visible_slots, kv_cache.k_all, kv_cache.v_all, crossattn_cache.k_all,
                                    crossattn_cache.v_all, out=out, frame_base=frame_base)
