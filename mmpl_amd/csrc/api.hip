@@ -865,102 +865,116 @@ int mmpl_qknorm_rope_at(MmplDit* h, void* q, int ldq, const void* k, int ldk, co
   return 0;
 }
 
+}  // extern "C"
+
+// ---- the samplers (sampler.hip): every argument check here, before the first launch.  The eight entries keep the accept / reject
+// sets they had when they were written apart: what differs between them is a parameter of the helpers below, not harmonised.
+// T = storage type of x / m0 / m1 / last_sample.  Float storage checks the alignment of every pointer, bf16 storage does not;
+// limit_n: the "n too large" bound of the bf16 DPM-Solver++ entries.
+template <class T>
+static int sampler_ptrs(const char* where, SamplerPtrs<T>& a, const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1,
+                        void* last_sample, bool need_last, void* x_bf16, size_t n, bool limit_n) {
+  if (!flow_cond || !x || !m0 || !m1 || (need_last && !last_sample)) return fail(where, "null argument");
+  if (limit_n && n / 8 >= (size_t)0x7fffffff * 256) return fail(where, "n too large");
+  if (sizeof(T) == 4) {
+    const uintptr_t fl = (uintptr_t)x | (uintptr_t)m0 | (uintptr_t)m1 | (uintptr_t)last_sample;
+    if (fl & 3) return fail(where, "x, m0, m1 and last_sample are float32: 4-byte aligned");
+    if (((uintptr_t)flow_cond | (uintptr_t)flow_uncond | (uintptr_t)x_bf16) & 1) return fail(where, "bf16 pointers are 2-byte aligned");
+  }
+  a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.x = (T*)x; a.m0 = (T*)m0; a.m1 = (T*)m1;
+  a.last = (T*)last_sample; a.x_bf16 = (bf16_t*)x_bf16; a.n = n;
+  return 0;
+}
+// the orders a step struct may carry (null = fine); bf16 UniPC has never checked its own
+static const char* bad_order(const MmplUniPCStep&) { return nullptr; }
+static const char* bad_order(const MmplDpmppStep& st) { return st.order != 1 && st.order != 2 ? "order must be 1 or 2" : nullptr; }
+static const char* bad_order(const MmplUniPCStepF32& st) {
+  if (st.pred_order != 1 && st.pred_order != 2) return "pred_order must be 1 or 2";
+  if (st.use_corrector && st.corr_order != 1 && st.corr_order != 2) return "corr_order must be 1 or 2";
+  return nullptr;
+}
+
+template <class T, class Step>
+static int sampler_step(const char* where, const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
+                        bool need_last, void* x_bf16, size_t n, const Step* st, mmpl_stream_t stream, bool limit_n = false) {
+  if (!st) return fail(where, "null step");
+  SamplerPtrs<T> a = {};
+  if (sampler_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, last_sample, need_last, x_bf16, n, limit_n)) return 1;
+  if (const char* bad = bad_order(*st)) return fail(where, bad);
+  ProfScope ps(K_UNIPC, 0, (hipStream_t)stream);
+  MMPL_HIP_TRY(mmpl_launch_sampler(a, st, (hipStream_t)stream), where);
+  return 0;
+}
+
+// The table arguments come first.  bf16 storage: one text, n_timestep >= 1; float storage: a text per fault, n_timestep >= 0.
+template <class T, class Step>
+static int sampler_step_table(const char* where, const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1,
+                              void* last_sample, bool need_last, void* x_bf16, size_t n, const Step* table_dev, int* step_dev,
+                              float* timestep_dev, const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream,
+                              bool limit_n = false) {
+  const bool null_arg = !table_dev || !step_dev || !timestep_dev || !timestep_table_dev;
+  if (sizeof(T) == 4) {
+    if (null_arg) return fail(where, "null argument");
+    if (n_steps < 1) return fail(where, "n_steps < 1");
+    if (n_timestep < 0) return fail(where, "n_timestep < 0");
+  } else if (null_arg || n_steps < 1 || n_timestep < 1) {
+    return fail(where, "bad arguments");
+  }
+  SamplerPtrs<T> a = {};
+  if (sampler_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, last_sample, need_last, x_bf16, n, limit_n)) return 1;
+  MMPL_HIP_TRY(mmpl_launch_sampler_table(a, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps, (hipStream_t)stream),
+               where);
+  return 0;
+}
+
+extern "C" {
+
 int mmpl_cfg_unipc_step(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
                         size_t n, const MmplUniPCStep* st, mmpl_stream_t stream) {
-  if (!st) return fail("mmpl_cfg_unipc_step", "null step");
-  if (!flow_cond || !x || !m0 || !m1 || !last_sample) return fail("mmpl_cfg_unipc_step", "null argument");
-  UniPCArgs a = {};
-  a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.guidance = st->guidance; a.x = (bf16_t*)x;
-  a.m0 = (bf16_t*)m0; a.m1 = (bf16_t*)m1; a.last_sample = (bf16_t*)last_sample; a.n = n; a.sigma_cur = st->sigma_cur;
-  a.use_corrector = st->use_corrector; a.corr_order = st->corr_order; a.c_c1 = st->c_c1; a.c_c2 = st->c_c2; a.c_c3 = st->c_c3;
-  a.c_inv_rk = st->c_inv_rk; a.c_rho0 = st->c_rho0; a.c_rho_last = st->c_rho_last; a.pred_order = st->pred_order;
-  a.p_c1 = st->p_c1; a.p_c2 = st->p_c2; a.p_c3 = st->p_c3; a.p_inv_rk = st->p_inv_rk;
-  ProfScope ps(K_UNIPC, 0, (hipStream_t)stream);
-  MMPL_HIP_TRY(mmpl_launch_unipc(a, (hipStream_t)stream), "mmpl_cfg_unipc_step");
-  return 0;
+  return sampler_step<bf16_t>("mmpl_cfg_unipc_step", flow_cond, flow_uncond, x, m0, m1, last_sample, true, nullptr, n, st, stream);
 }
 
 int mmpl_cfg_unipc_step_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
                               size_t n, const MmplUniPCStep* table_dev, int* step_dev, float* timestep_dev,
                               const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream) {
-  if (!table_dev || !step_dev || !timestep_dev || !timestep_table_dev || n_steps < 1 || n_timestep < 1)
-    return fail("mmpl_cfg_unipc_step_table", "bad arguments");
-  if (!flow_cond || !x || !m0 || !m1 || !last_sample) return fail("mmpl_cfg_unipc_step_table", "null argument");
-  static_assert(sizeof(MmplUniPCStep) == sizeof(UniPCStepDev), "table layout");
-  UniPCArgs a = {};
-  a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.x = (bf16_t*)x;
-  a.m0 = (bf16_t*)m0; a.m1 = (bf16_t*)m1; a.last_sample = (bf16_t*)last_sample; a.n = n;
-  MMPL_HIP_TRY(mmpl_launch_unipc_table(a, (const UniPCStepDev*)table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps,
-                                  (hipStream_t)stream), "mmpl_cfg_unipc_step_table");
-  return 0;
+  return sampler_step_table<bf16_t>("mmpl_cfg_unipc_step_table", flow_cond, flow_uncond, x, m0, m1, last_sample, true, nullptr, n, table_dev,
+                                    step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps, stream);
 }
 
-// ---- the float32 latent chain (fp32_chain.hip): argument checks here, before the first launch
-static int f32_chain_ptrs(const char* where, F32ChainPtrs& a, const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1,
-                          void* last_sample, bool need_last, void* x_bf16, size_t n) {
-  if (!flow_cond || !x || !m0 || !m1 || (need_last && !last_sample)) return fail(where, "null argument");
-  const uintptr_t fl = (uintptr_t)x | (uintptr_t)m0 | (uintptr_t)m1 | (uintptr_t)last_sample;
-  if (fl & 3) return fail(where, "x, m0, m1 and last_sample are float32: 4-byte aligned");
-  if (((uintptr_t)flow_cond | (uintptr_t)flow_uncond | (uintptr_t)x_bf16) & 1) return fail(where, "bf16 pointers are 2-byte aligned");
-  a.flow_c = (const bf16_t*)flow_cond; a.flow_u = (const bf16_t*)flow_uncond; a.x = (float*)x; a.m0 = (float*)m0; a.m1 = (float*)m1;
-  a.last = (float*)last_sample; a.x_bf16 = (bf16_t*)x_bf16; a.n = n;
-  return 0;
+int mmpl_cfg_dpmpp_step(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, size_t n,
+                        const MmplDpmppStep* st, mmpl_stream_t stream) {
+  return sampler_step<bf16_t>("mmpl_cfg_dpmpp_step", flow_cond, flow_uncond, x, m0, m1, nullptr, false, nullptr, n, st, stream, true);
 }
-static int f32_table_args(const char* where, const void* table_dev, const int* step_dev, const float* timestep_dev,
-                          const float* timestep_table_dev, int n_timestep, int n_steps) {
-  if (!table_dev || !step_dev || !timestep_dev || !timestep_table_dev) return fail(where, "null argument");
-  if (n_steps < 1) return fail(where, "n_steps < 1");
-  if (n_timestep < 0) return fail(where, "n_timestep < 0");
-  return 0;
+
+int mmpl_cfg_dpmpp_step_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, size_t n,
+                              const MmplDpmppStep* table_dev, int* step_dev, float* timestep_dev,
+                              const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream) {
+  return sampler_step_table<bf16_t>("mmpl_cfg_dpmpp_step_table", flow_cond, flow_uncond, x, m0, m1, nullptr, false, nullptr, n, table_dev,
+                                    step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps, stream, true);
 }
 
 int mmpl_cfg_unipc_step_f32(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
                             void* x_bf16, size_t n, const MmplUniPCStepF32* st, mmpl_stream_t stream) {
-  const char* where = "mmpl_cfg_unipc_step_f32";
-  if (!st) return fail(where, "null step");
-  F32ChainPtrs a = {};
-  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, last_sample, true, x_bf16, n)) return 1;
-  if (st->pred_order != 1 && st->pred_order != 2) return fail(where, "pred_order must be 1 or 2");
-  if (st->use_corrector && st->corr_order != 1 && st->corr_order != 2) return fail(where, "corr_order must be 1 or 2");
-  ProfScope ps(K_UNIPC, 0, (hipStream_t)stream);
-  MMPL_HIP_TRY(mmpl_launch_unipc_f32(a, st, (hipStream_t)stream), where);
-  return 0;
+  return sampler_step<float>("mmpl_cfg_unipc_step_f32", flow_cond, flow_uncond, x, m0, m1, last_sample, true, x_bf16, n, st, stream);
 }
 
 int mmpl_cfg_dpmpp_step_f32(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* x_bf16, size_t n,
                             const MmplDpmppStep* st, mmpl_stream_t stream) {
-  const char* where = "mmpl_cfg_dpmpp_step_f32";
-  if (!st) return fail(where, "null step");
-  F32ChainPtrs a = {};
-  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, nullptr, false, x_bf16, n)) return 1;
-  if (st->order != 1 && st->order != 2) return fail(where, "order must be 1 or 2");
-  ProfScope ps(K_UNIPC, 0, (hipStream_t)stream);
-  MMPL_HIP_TRY(mmpl_launch_dpmpp_f32(a, st, (hipStream_t)stream), where);
-  return 0;
+  return sampler_step<float>("mmpl_cfg_dpmpp_step_f32", flow_cond, flow_uncond, x, m0, m1, nullptr, false, x_bf16, n, st, stream);
 }
 
 int mmpl_cfg_unipc_step_f32_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* last_sample,
                                   void* x_bf16, size_t n, const MmplUniPCStepF32* table_dev, int* step_dev, float* timestep_dev,
                                   const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream) {
-  const char* where = "mmpl_cfg_unipc_step_f32_table";
-  if (f32_table_args(where, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps)) return 1;
-  F32ChainPtrs a = {};
-  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, last_sample, true, x_bf16, n)) return 1;
-  MMPL_HIP_TRY(mmpl_launch_unipc_f32_table(a, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps,
-                                           (hipStream_t)stream), where);
-  return 0;
+  return sampler_step_table<float>("mmpl_cfg_unipc_step_f32_table", flow_cond, flow_uncond, x, m0, m1, last_sample, true, x_bf16, n,
+                                   table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps, stream);
 }
 
 int mmpl_cfg_dpmpp_step_f32_table(const void* flow_cond, const void* flow_uncond, void* x, void* m0, void* m1, void* x_bf16, size_t n,
                                   const MmplDpmppStep* table_dev, int* step_dev, float* timestep_dev,
                                   const float* timestep_table_dev, int n_timestep, int n_steps, mmpl_stream_t stream) {
-  const char* where = "mmpl_cfg_dpmpp_step_f32_table";
-  if (f32_table_args(where, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps)) return 1;
-  F32ChainPtrs a = {};
-  if (f32_chain_ptrs(where, a, flow_cond, flow_uncond, x, m0, m1, nullptr, false, x_bf16, n)) return 1;
-  MMPL_HIP_TRY(mmpl_launch_dpmpp_f32_table(a, table_dev, step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps,
-                                           (hipStream_t)stream), where);
-  return 0;
+  return sampler_step_table<float>("mmpl_cfg_dpmpp_step_f32_table", flow_cond, flow_uncond, x, m0, m1, nullptr, false, x_bf16, n, table_dev,
+                                   step_dev, timestep_dev, timestep_table_dev, n_timestep, n_steps, stream);
 }
 
 }  // extern "C"

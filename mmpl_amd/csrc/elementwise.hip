@@ -1,5 +1,5 @@
 // HBM-bound kernels of the Wan DiT forward: LayerNorm+modulate, full-dim QK RMSNorm + 3-axis RoPE + KV page
-// write, patchify / unpatchify, timestep sinusoid, modulation prep, CFG + UniPC step.
+// write, patchify / unpatchify, timestep sinusoid, modulation prep.
 // All of them move 16 B per lane, a wave works on one token row at a time (the two big ones walk a range of rows with the next
 // row's loads in flight), fp32 statistics, and round to bf16 exactly where the reference's bf16 module boundaries round
 // (DESIGN.md "numerics"); every fp32 expression whose rounding matters is written with explicit fmaf under contract(off).
@@ -380,61 +380,6 @@ __global__ void silu_kernel(const bf16_t* x, bf16_t* y, size_t n) {
     y[i] = f2bf(silu(bf2f(x[i])));
 }
 
-// ------------------------------------------------------------------ CFG + FlowUniPC (order <= 2, bh2, predict_x0)
-// Every tensor op of fm_solvers_unipc.py:315-331 / 486-626 / 350-484 on a bf16 tensor rounds to bf16; this kernel
-// performs the same chain per element with the same rounding points.  Scalars come from the host scheduler.
-MMPL_DEV void unipc_body(const UniPCArgs& a) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-    float flow = bf2f(a.flow_c[i]);
-    if (a.flow_u) {
-      const float fu = bf2f(a.flow_u[i]);
-      flow = rbf(fu + rbf(a.guidance * rbf(flow - fu)));            // casual_fps_inference.py:366-367
-    }
-    float x = bf2f(a.x[i]);
-    const float m_conv = rbf(x - rbf(a.sigma_cur * flow));           // convert_model_output
-    float m0 = bf2f(a.m0[i]), m1 = bf2f(a.m1[i]);
-    if (a.use_corrector) {
-      const float ls = bf2f(a.last_sample[i]);
-      const float xt_ = rbf(rbf(a.c_c1 * ls) - rbf(a.c_c2 * m0));
-      const float d1t = rbf(m_conv - m0);
-      float acc = rbf(a.c_rho_last * d1t);
-      if (a.corr_order == 2) {
-        const float d1 = rbf(rbf(m1 - m0) * a.c_inv_rk);
-        acc = rbf(rbf(a.c_rho0 * d1) + acc);
-      }
-      x = rbf(xt_ - rbf(a.c_c3 * acc));
-    }
-    m1 = m0;
-    m0 = m_conv;
-    a.m1[i] = f2bf(m1);
-    a.m0[i] = f2bf(m0);
-    a.last_sample[i] = f2bf(x);
-    float xt = rbf(rbf(a.p_c1 * x) - rbf(a.p_c2 * m0));
-    if (a.pred_order == 2) {
-      const float d1 = rbf(rbf(m1 - m0) * a.p_inv_rk);
-      xt = rbf(xt - rbf(a.p_c3 * rbf(0.5f * d1)));
-    }
-    a.x[i] = f2bf(xt);
-  }
-}
-__global__ void unipc_kernel(UniPCArgs a) { unipc_body(a); }
-__global__ void unipc_table_kernel(UniPCArgs a, const UniPCStepDev* table, const int* step, int n_steps) {
-  if (*step >= n_steps) return;          // a replay beyond the uploaded table must not apply garbage coefficients
-  const UniPCStepDev st = table[*step];
-  a.guidance = st.guidance; a.sigma_cur = st.sigma_cur; a.use_corrector = st.use_corrector; a.corr_order = st.corr_order;
-  a.c_c1 = st.c_c1; a.c_c2 = st.c_c2; a.c_c3 = st.c_c3; a.c_inv_rk = st.c_inv_rk; a.c_rho0 = st.c_rho0; a.c_rho_last = st.c_rho_last;
-  a.pred_order = st.pred_order; a.p_c1 = st.p_c1; a.p_c2 = st.p_c2; a.p_c3 = st.p_c3; a.p_inv_rk = st.p_inv_rk;
-  unipc_body(a);
-}
-__global__ void unipc_advance_kernel(int* step, float* t_out, const float* t_tab, int n_t, int n_steps) {
-  if (*step >= n_steps) return;
-  const int nxt = *step + 1;
-  __syncthreads();
-  if (threadIdx.x == 0) *step = nxt;
-  const float t = t_tab[nxt < n_steps ? nxt : n_steps - 1];
-  for (int i = threadIdx.x; i < n_t; i += blockDim.x) t_out[i] = t;
-}
-
 inline int grid_for(size_t n, int block = 256) {
   size_t g = (n + block - 1) / block;
   return (int)(g > 2048 * 4 ? 2048 * 4 : (g == 0 ? 1 : g));
@@ -667,15 +612,5 @@ hipError_t mmpl_launch_sinusoid(const float* t, bf16_t* out, int F, int freq_dim
 }
 hipError_t mmpl_launch_silu(const bf16_t* x, bf16_t* y, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(silu_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, y, n);
-  return hipGetLastError();
-}
-hipError_t mmpl_launch_unipc(const UniPCArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(unipc_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-hipError_t mmpl_launch_unipc_table(const UniPCArgs& a, const UniPCStepDev* table, int* step, float* t_out, const float* t_tab,
-                                   int n_t, int n_steps, hipStream_t s) {
-  hipLaunchKernelGGL(unipc_table_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a, table, step, n_steps);
-  hipLaunchKernelGGL(unipc_advance_kernel, dim3(1), dim3(64), 0, s, step, t_out, t_tab, n_t, n_steps);
   return hipGetLastError();
 }

@@ -279,46 +279,27 @@ hipError_t mmpl_launch_rows_equal_last(const bf16_t* x, int ld, int rows, int d,
 hipError_t mmpl_launch_sinusoid(const float* t, bf16_t* out, int F, int freq_dim, hipStream_t s);
 hipError_t mmpl_launch_silu(const bf16_t* x, bf16_t* y, size_t n, hipStream_t s);
 
-// CFG combine + one FlowUniPC step (elementwise.hip); scalars computed on the host exactly as the reference does
-struct UniPCArgs {
+// The samplers (sampler.hip): CFG combine + one UniPC / DPM-Solver++ step on x / m0 / m1 / last of storage type T (bf16_t or float)
+// with bf16 flows; the formulas are in sampler.hip's header and at the entries in include/mmpl_hip.h.  Defined for the four pairs
+// (bf16_t, MmplUniPCStep), (bf16_t, MmplDpmppStep), (float, MmplUniPCStepF32), (float, MmplDpmppStep).  The caller has checked the
+// pointers; a.last is unused by DPM-Solver++.
+template <class T>
+struct SamplerPtrs {
   const bf16_t* flow_c; const bf16_t* flow_u;   // flow_u == null: flow_c is already the combined flow
-  float guidance;
-  bf16_t* x;          // sample in / next sample out
-  bf16_t* m0; bf16_t* m1; bf16_t* last_sample;   // solver state (updated in place)
-  size_t n;
-  float sigma_cur;
-  int use_corrector, corr_order; float c_c1, c_c2, c_c3, c_inv_rk, c_rho0, c_rho_last;
-  int pred_order; float p_c1, p_c2, p_c3, p_inv_rk;
-};
-hipError_t mmpl_launch_unipc(const UniPCArgs& a, hipStream_t s);
-// Device-resident form for a hipGraph of a whole denoise step: the scalars of step *step come from table[*step] (same
-// layout as MmplUniPCStep), then *step is advanced and the NEXT step's timestep is written to t_out[0..n_t) (the tensor
-// the two DiT forwards of the next replay read).  `a` carries the pointers and n only.
-struct UniPCStepDev {
-  float guidance, sigma_cur; int use_corrector, corr_order; float c_c1, c_c2, c_c3, c_inv_rk, c_rho0, c_rho_last;
-  int pred_order; float p_c1, p_c2, p_c3, p_inv_rk;
-};
-hipError_t mmpl_launch_unipc_table(const UniPCArgs& a, const UniPCStepDev* table, int* step, float* t_out, const float* t_tab,
-                                   int n_t, int n_steps, hipStream_t s);
-
-// The float32 latent chain (fp32_chain.hip): CFG combine + one UniPC / DPM-Solver++ step on float32 x / m0 / m1 / last_sample with
-// bf16 flows and a bf16 shadow of the new x (x_bf16, may be null); the formulas are at the entries in include/mmpl_hip.h.  `st` is
-// host memory, `table` / `step` / `t_out` / `t_tab` device memory (the protocol of mmpl_launch_unipc_table).  The caller has checked
-// the pointers; a.last is unused by DPM-Solver++.
-struct MmplUniPCStepF32;
-struct MmplDpmppStep;
-struct F32ChainPtrs {
-  const bf16_t* flow_c; const bf16_t* flow_u;   // flow_u == null: flow_c is already the combined flow
-  float* x; float* m0; float* m1; float* last;
-  bf16_t* x_bf16;
+  T* x;                                         // sample in / next sample out
+  T* m0; T* m1; T* last;                        // solver state (updated in place)
+  bf16_t* x_bf16;                               // float storage only: the bf16 rounding of the new x (may be null)
   size_t n;
 };
-hipError_t mmpl_launch_unipc_f32(const F32ChainPtrs& a, const MmplUniPCStepF32* st, hipStream_t s);
-hipError_t mmpl_launch_dpmpp_f32(const F32ChainPtrs& a, const MmplDpmppStep* st, hipStream_t s);
-hipError_t mmpl_launch_unipc_f32_table(const F32ChainPtrs& a, const MmplUniPCStepF32* table, int* step, float* t_out, const float* t_tab,
-                                       int n_t, int n_steps, hipStream_t s);
-hipError_t mmpl_launch_dpmpp_f32_table(const F32ChainPtrs& a, const MmplDpmppStep* table, int* step, float* t_out, const float* t_tab,
-                                       int n_t, int n_steps, hipStream_t s);
+// st: host memory, the scalars computed on the host exactly as the reference does
+template <class T, class Step>
+hipError_t mmpl_launch_sampler(const SamplerPtrs<T>& a, const Step* st, hipStream_t s);
+// Device-resident form for a hipGraph of a whole denoise step: the scalars of step *step come from table[*step] (device memory,
+// n_steps rows), then *step is advanced and the NEXT step's timestep is written to t_out[0..n_t) (the tensor the two DiT forwards
+// of the next replay read).  A counter outside 0 .. n_steps - 1 changes nothing.
+template <class T, class Step>
+hipError_t mmpl_launch_sampler_table(const SamplerPtrs<T>& a, const Step* table, int* step, float* t_out, const float* t_tab, int n_t,
+                                     int n_steps, hipStream_t s);
 
 // ---------------------------------------------------------------- umT5 glue (t5.hip): the launches of mmpl_t5_encode, one each
 // out[l][:] = emb[ids[l]][:]   (dim % 8 == 0, 16 bytes per access; ids in [0, vocab))

@@ -79,47 +79,119 @@ def _check_table_call(sched, sample: torch.Tensor, timestep: torch.Tensor) -> No
         raise TypeError(f"{type(sched).__name__}: the step table was built for a {sched._table_dtype} sample, this one is {sample.dtype}")
 
 
-class FlowUniPCMultistepScheduler:
+class _DeviceSolver:
+    """The device-facing half of both schedulers: the solver state, the fused step and the device-resident step table.  A subclass
+    sets `_n_state` (state tensors of the sample's shape and dtype: m0, m1 and, for UniPC, last_sample) and `_stem` -- the C entry is
+    ``mmpl_cfg_{_stem}_step{_f32}{_table}`` -- and has `step_scalars(guidance)`, `sigmas`, `timesteps` and `step_index`."""
     order = 1
     latent_dtype = torch.bfloat16         # the mode: set by _ensure_state from the sample (see _solver_state)
+    _n_state: int
+    _stem: str
 
-    def __init__(self, num_train_timesteps: int = 1000, solver_order: int = 2, shift: float = 1.0,
-                 use_dynamic_shifting: bool = False):
-        assert solver_order == 2 and not use_dynamic_shifting
-        self.num_train_timesteps = num_train_timesteps
-        self.solver_order = solver_order
+    def _train_sigmas(self, num_train_timesteps: int, shift: float) -> None:
+        """The constructor's schedule: the train-time sigmas under `shift`, until `set_timesteps` replaces them."""
         alphas = np.linspace(1, 1 / num_train_timesteps, num_train_timesteps)[::-1].copy()
         sigmas = torch.from_numpy(1.0 - alphas).to(dtype=torch.float32)
-        sigmas = shift * sigmas / (1 + (shift - 1) * sigmas)
+        sigmas = shift * sigmas / (1 + (shift - 1) * sigmas)               # shift 1: unchanged, bit for bit
+        self.num_train_timesteps = num_train_timesteps
         self.sigmas = sigmas
         self.sigma_min = self.sigmas[-1].item()
         self.sigma_max = self.sigmas[0].item()
-        self.shift = shift
         self.timesteps = sigmas * num_train_timesteps
         self.num_inference_steps = None
         self._state = None
 
-    def set_timesteps(self, num_inference_steps: int, device=None, shift: Optional[float] = None):
-        sigmas = np.linspace(self.sigma_max, self.sigma_min, num_inference_steps + 1).copy()[:-1]
-        if shift is None:
-            shift = self.shift
+    def _inference_sigmas(self, sigmas: np.ndarray, shift: float) -> None:
+        """`set_timesteps`: `sigmas` (numpy, without the trailing 0) under `shift` become the schedule; the step count rewinds."""
         sigmas = shift * sigmas / (1 + (shift - 1) * sigmas)
         timesteps = sigmas * self.num_train_timesteps
         sigmas = np.concatenate([sigmas, [0]]).astype(np.float32)
         self.sigmas = torch.from_numpy(sigmas)                       # stays on the host, like the reference
-        self.timesteps = torch.from_numpy(timesteps).to(dtype=torch.int64)
+        self.timesteps = torch.from_numpy(timesteps).to(dtype=torch.int64)      # truncated: the first one is 1000
         self.num_inference_steps = len(timesteps)
-        self.lower_order_nums = 0
         self.step_index = 0
-        self.this_order = 1
-        self._have_last = False
         self._state = None
 
-    # -- host scalars ------------------------------------------------------------------------------
     @staticmethod
     def _lam(sigma):
         return torch.log(1 - sigma) - torch.log(sigma)
 
+    # -- device update -----------------------------------------------------------------------------
+    def _ensure_state(self, sample: torch.Tensor):
+        _solver_state(self, sample, self._n_state)
+
+    def _call(self, table: bool, flow_cond, flow_uncond, sample: torch.Tensor, sample_bf16, *tail) -> None:
+        """One of the four entries of this solver: `tail` is what follows n in its signature, without the stream."""
+        f32 = sample.dtype == torch.float32
+        assert f32 or sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
+        name = f"mmpl_cfg_{self._stem}_step" + ("_f32" if f32 else "") + ("_table" if table else "")
+        shadow = (_shadow_ptr(sample, sample_bf16),) if f32 else ()
+        _lib.check(getattr(_lib.load(), name)(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample),
+                                              *[_lib.ptr(t) for t in self._state], *shadow, sample.numel(), *tail, _lib.stream_ptr()), name)
+
+    def step_cfg(self, flow_cond: torch.Tensor, flow_uncond: Optional[torch.Tensor], guidance: float,
+                 sample: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """CFG combine + scheduler step, fused; `sample` is updated in place and returned.  The flows are bf16.  A float32 `sample`
+        takes the float32 chain (DPM-Solver++: the same scalars, the reference multiplies by 1.0 / r0 there too); `sample_bf16`
+        (optional) then receives the bf16 rounding of the new sample."""
+        assert sample.is_contiguous() and flow_cond.is_contiguous() and flow_cond.dtype == torch.bfloat16
+        self._ensure_state(sample)
+        st = self.step_scalars(guidance)
+        self._call(False, flow_cond, flow_uncond, sample, sample_bf16, C.byref(st))
+        return sample
+
+    # -- device-resident step table: one hipGraph per denoise step, replayed with no host work in between --------------
+    def build_step_table(self, guidance: float, device) -> None:
+        """Upload the scalars of ALL remaining steps (they depend only on the step index, never on data) plus the timestep
+        of every step; `step_cfg_table` then reads entry *counter on the device.  The host-side step bookkeeping of THIS
+        object is not advanced (the scalars come from a copy): after the table's last step the device kernel does nothing
+        (the counter is clamped), `reset_step_table` rewinds it for another pass over the same schedule.  The rows are those of
+        the mode `_ensure_state` chose (bf16 unless it has been called with a float32 sample)."""
+        _table_rows(self, guidance, device)
+
+    def reset_step_table(self, timestep: torch.Tensor) -> None:
+        """Rewind the device step counter, the solver history and `timestep` to the first entry of the uploaded table."""
+        self._counter.zero_()
+        if self._state is not None:
+            for t in self._state:
+                t.zero_()
+        timestep.fill_(self._t_first)
+
+    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor,
+                       sample_bf16: Optional[torch.Tensor] = None) -> None:
+        """CFG combine + scheduler step with device-resident scalars (capturable: no host value enters the launch);
+        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous).  A float32
+        `sample` (the table was built for one) takes the float32 chain and writes its bf16 rounding to `sample_bf16`."""
+        _check_table_call(self, sample, timestep)
+        self._ensure_state(sample)
+        self._call(True, flow_cond, flow_uncond, sample, sample_bf16, _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep),
+                   _lib.ptr(self._t_table), timestep.numel(), self._table_n)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
+        """Reference call shape (fm_solvers_unipc.py:655, fm_solvers.py:706).  `timestep` is accepted and ignored: the steps are
+        counted, as the reference's internal step counter does after the first call."""
+        out = self.step_cfg(model_output.to(torch.bfloat16).contiguous(), None, 0.0, sample.contiguous().clone())   # (flows are bf16)
+        return (out,) if not return_dict else {"prev_sample": out}
+
+
+class FlowUniPCMultistepScheduler(_DeviceSolver):
+    _n_state, _stem = 3, "unipc"          # m0, m1, last_sample
+
+    def __init__(self, num_train_timesteps: int = 1000, solver_order: int = 2, shift: float = 1.0,
+                 use_dynamic_shifting: bool = False):
+        assert solver_order == 2 and not use_dynamic_shifting
+        self.solver_order = solver_order
+        self.shift = shift
+        self._train_sigmas(num_train_timesteps, shift)
+
+    def set_timesteps(self, num_inference_steps: int, device=None, shift: Optional[float] = None):
+        sigmas = np.linspace(self.sigma_max, self.sigma_min, num_inference_steps + 1).copy()[:-1]
+        self._inference_sigmas(sigmas, self.shift if shift is None else shift)
+        self.lower_order_nums = 0
+        self.this_order = 1
+        self._have_last = False
+
+    # -- host scalars ------------------------------------------------------------------------------
     def _corrector_scalars(self, order: int):
         """fm_solvers_unipc.py:549-618."""
         si = self.step_index
@@ -196,73 +268,6 @@ class FlowUniPCMultistepScheduler:
         self.step_index += 1
         return st
 
-    # -- device update -----------------------------------------------------------------------------
-    def _ensure_state(self, sample: torch.Tensor):
-        _solver_state(self, sample, 3)                                      # m0, m1, last_sample
-
-    def step_cfg(self, flow_cond: torch.Tensor, flow_uncond: Optional[torch.Tensor], guidance: float,
-                 sample: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """CFG combine + scheduler step, fused; `sample` is updated in place and returned.  The flows are bf16.  A float32 `sample`
-        takes the float32 chain; `sample_bf16` (optional) then receives the bf16 rounding of the new sample."""
-        assert sample.is_contiguous() and flow_cond.is_contiguous() and flow_cond.dtype == torch.bfloat16
-        self._ensure_state(sample)
-        st = self.step_scalars(guidance)
-        lib = _lib.load()
-        m0, m1, last = self._state
-        if sample.dtype == torch.float32:
-            _lib.check(lib.mmpl_cfg_unipc_step_f32(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
-                                                   _lib.ptr(m1), _lib.ptr(last), _shadow_ptr(sample, sample_bf16), sample.numel(),
-                                                   C.byref(st), _lib.stream_ptr()), "mmpl_cfg_unipc_step_f32")
-            return sample
-        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
-        _lib.check(lib.mmpl_cfg_unipc_step(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
-                                           _lib.ptr(m1), _lib.ptr(last), sample.numel(), C.byref(st), _lib.stream_ptr()),
-                   "mmpl_cfg_unipc_step")
-        return sample
-
-    # -- device-resident step table: one hipGraph per denoise step, replayed with no host work in between --------------
-    def build_step_table(self, guidance: float, device) -> None:
-        """Upload the scalars of ALL remaining steps (they depend only on the step index, never on data) plus the timestep
-        of every step; `step_cfg_table` then reads entry *counter on the device.  The host-side step bookkeeping of THIS
-        object is not advanced (the scalars come from a copy): after the table's last step the device kernel does nothing
-        (the counter is clamped), `reset_step_table` rewinds it for another pass over the same schedule.  The rows are those of
-        the mode `_ensure_state` chose (bf16 unless it has been called with a float32 sample)."""
-        _table_rows(self, guidance, device)
-
-    def reset_step_table(self, timestep: torch.Tensor) -> None:
-        """Rewind the device step counter, the solver history and `timestep` to the first entry of the uploaded table."""
-        self._counter.zero_()
-        if self._state is not None:
-            for t in self._state:
-                t.zero_()
-        timestep.fill_(self._t_first)
-
-    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor,
-                       sample_bf16: Optional[torch.Tensor] = None) -> None:
-        """CFG combine + scheduler step with device-resident scalars (capturable: no host value enters the launch);
-        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous).  A float32
-        `sample` (the table was built for one) takes the float32 chain and writes its bf16 rounding to `sample_bf16`."""
-        _check_table_call(self, sample, timestep)
-        self._ensure_state(sample)
-        m0, m1, last = self._state
-        if sample.dtype == torch.float32:
-            _lib.check(_lib.load().mmpl_cfg_unipc_step_f32_table(
-                _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), _lib.ptr(last),
-                _shadow_ptr(sample, sample_bf16), sample.numel(), _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep),
-                _lib.ptr(self._t_table), timestep.numel(), self._table_n, _lib.stream_ptr()), "mmpl_cfg_unipc_step_f32_table")
-            return
-        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
-        _lib.check(_lib.load().mmpl_cfg_unipc_step_table(
-            _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), _lib.ptr(last), sample.numel(),
-            _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep), _lib.ptr(self._t_table), timestep.numel(), self._table_n,
-            _lib.stream_ptr()), "mmpl_cfg_unipc_step_table")
-
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
-        """Reference call shape (fm_solvers_unipc.py:655).  `timestep` is accepted and ignored like the reference's
-        internal step counter does after the first call."""
-        out = self.step_cfg(model_output.to(torch.bfloat16).contiguous(), None, 0.0, sample.contiguous().clone())   # (flows are bf16)
-        return (out,) if not return_dict else {"prev_sample": out}
-
 
 def get_sampling_sigmas(sampling_steps: int, shift: float) -> np.ndarray:
     """fm_solvers.py:22-26: the shifted sigmas of a `sampling_steps`-step schedule from 1 down (fp64, without the trailing 0)."""
@@ -281,7 +286,7 @@ def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, timeste
     return scheduler.timesteps, len(scheduler.timesteps)
 
 
-class FlowDPMSolverMultistepScheduler:
+class FlowDPMSolverMultistepScheduler(_DeviceSolver):
     """DPM-Solver++(2M) for flow matching: the reference's second sampler (MMPL_t2v/wan/utils/fm_solvers.py:69-797) in the one
     configuration its pipeline builds (pipeline/casual_fps_inference.py:512-521: order 2, dpmsolver++, midpoint, flow_prediction,
     final sigma 0, no thresholding, config shift 1 with the schedule's shift applied by `get_sampling_sigmas`).  Every other
@@ -291,8 +296,7 @@ class FlowDPMSolverMultistepScheduler:
     the reference's own torch fp32 0-dim tensor operations, the tensor update (CFG combine, x0 conversion, history rotation, first /
     second order update) is ONE fused HIP kernel (``mmpl_cfg_dpmpp_step``), and the device-facing interface is the UniPC class's, so
     the stage loop drives either object.  The solver state is two tensors of the sample's dtype (m0, m1); there is no corrector and no last sample."""
-    order = 1
-    latent_dtype = torch.bfloat16         # the mode: set by _ensure_state from the sample (see _solver_state)
+    _n_state, _stem = 2, "dpmpp"          # m0, m1
     _SUPPORTED = dict(solver_order=2, prediction_type="flow_prediction", shift=1.0, use_dynamic_shifting=False, thresholding=False,
                       algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, euler_at_final=False,
                       final_sigmas_type="zero", lambda_min_clipped=-float("inf"), variance_type=None, invert_sigmas=False)
@@ -311,16 +315,9 @@ class FlowDPMSolverMultistepScheduler:
             if v != self._SUPPORTED[k]:
                 raise NotImplementedError(f"FlowDPMSolverMultistepScheduler: {k}={v!r} is not supported (only {self._SUPPORTED[k]!r}: "
                                           "the configuration the pipeline builds)")
-        self.num_train_timesteps = num_train_timesteps
         self.solver_order = solver_order
-        alphas = np.linspace(1, 1 / num_train_timesteps, num_train_timesteps)[::-1].copy()
-        self.sigmas = torch.from_numpy(1.0 - alphas).to(dtype=torch.float32)         # shift 1: unchanged
-        self.sigma_min = self.sigmas[-1].item()
-        self.sigma_max = self.sigmas[0].item()
-        self.timesteps = self.sigmas * num_train_timesteps
-        self.num_inference_steps = None
+        self._train_sigmas(num_train_timesteps, 1.0)
         self.step_index = 0
-        self._state = None
 
     def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, sigmas=None, mu=None, shift: Optional[float] = None):
         """fm_solvers.py:226-287.  `sigmas` (fp64, from get_sampling_sigmas: already shifted) are taken as they are -- the config's
@@ -334,22 +331,9 @@ class FlowDPMSolverMultistepScheduler:
                 raise ValueError("set_timesteps: pass num_inference_steps or sigmas")
             sigmas = np.linspace(self.sigma_max, self.sigma_min, num_inference_steps + 1).copy()[:-1]
         sigmas = np.asarray(sigmas, dtype=np.float64)
-        if shift is None:
-            shift = 1.0
-        sigmas = shift * sigmas / (1 + (shift - 1) * sigmas)
-        timesteps = sigmas * self.num_train_timesteps
-        sigmas = np.concatenate([sigmas, [0]]).astype(np.float32)
-        self.sigmas = torch.from_numpy(sigmas)                       # stays on the host, like the reference
-        self.timesteps = torch.from_numpy(timesteps).to(dtype=torch.int64)      # truncated: the first one is 1000
-        self.num_inference_steps = len(timesteps)
-        self.step_index = 0
-        self._state = None
+        self._inference_sigmas(sigmas, 1.0 if shift is None else shift)
 
     # -- host scalars ------------------------------------------------------------------------------
-    @staticmethod
-    def _lam(sigma):
-        return torch.log(1 - sigma) - torch.log(sigma)
-
     def step_scalars(self, guidance: float) -> _lib.MmplDpmppStep:
         """Scalars of the step at the current step_index (fm_solvers.py:457-468, 529-553, 746-783), then step_index += 1.
         The reference's own fp32 0-dim tensor operations, so the values are its bits; its three infinities stay on the host:
@@ -380,70 +364,6 @@ class FlowDPMSolverMultistepScheduler:
                                      f"c1={st.c1} c2={st.c2} inv_r0={st.inv_r0}")
         self.step_index += 1
         return st
-
-    # -- device update -----------------------------------------------------------------------------
-    def _ensure_state(self, sample: torch.Tensor):
-        _solver_state(self, sample, 2)                                      # m0, m1
-
-    def step_cfg(self, flow_cond: torch.Tensor, flow_uncond: Optional[torch.Tensor], guidance: float,
-                 sample: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """CFG combine + scheduler step, fused; `sample` is updated in place and returned.  The flows are bf16.  A float32 `sample`
-        takes the float32 chain (the same scalars: the reference multiplies by 1.0 / r0 there too); `sample_bf16` (optional) then
-        receives the bf16 rounding of the new sample."""
-        assert sample.is_contiguous() and flow_cond.is_contiguous() and flow_cond.dtype == torch.bfloat16
-        self._ensure_state(sample)
-        st = self.step_scalars(guidance)
-        m0, m1 = self._state
-        if sample.dtype == torch.float32:
-            _lib.check(_lib.load().mmpl_cfg_dpmpp_step_f32(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
-                                                           _lib.ptr(m1), _shadow_ptr(sample, sample_bf16), sample.numel(), C.byref(st),
-                                                           _lib.stream_ptr()), "mmpl_cfg_dpmpp_step_f32")
-            return sample
-        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
-        _lib.check(_lib.load().mmpl_cfg_dpmpp_step(_lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0),
-                                                   _lib.ptr(m1), sample.numel(), C.byref(st), _lib.stream_ptr()),
-                   "mmpl_cfg_dpmpp_step")
-        return sample
-
-    # -- device-resident step table: the protocol of FlowUniPCMultistepScheduler.build_step_table ---------------------
-    def build_step_table(self, guidance: float, device) -> None:
-        """Upload the scalars and the timestep of every remaining step; `step_cfg_table` reads entry *counter on the device.  The
-        host-side step_index of THIS object is not advanced (the scalars come from a copy)."""
-        _table_rows(self, guidance, device)
-
-    def reset_step_table(self, timestep: torch.Tensor) -> None:
-        """Rewind the device step counter, the solver history and `timestep` to the first entry of the uploaded table."""
-        self._counter.zero_()
-        if self._state is not None:
-            for t in self._state:
-                t.zero_()
-        timestep.fill_(self._t_first)
-
-    def step_cfg_table(self, flow_cond: torch.Tensor, flow_uncond: torch.Tensor, sample: torch.Tensor, timestep: torch.Tensor,
-                       sample_bf16: Optional[torch.Tensor] = None) -> None:
-        """CFG combine + scheduler step with device-resident scalars (capturable: no host value enters the launch);
-        advances the device step counter and writes the next step's timestep into `timestep` (float32, contiguous).  A float32
-        `sample` (the table was built for one) takes the float32 chain and writes its bf16 rounding to `sample_bf16`."""
-        _check_table_call(self, sample, timestep)
-        self._ensure_state(sample)
-        m0, m1 = self._state
-        if sample.dtype == torch.float32:
-            _lib.check(_lib.load().mmpl_cfg_dpmpp_step_f32_table(
-                _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), _shadow_ptr(sample, sample_bf16),
-                sample.numel(), _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep), _lib.ptr(self._t_table),
-                timestep.numel(), self._table_n, _lib.stream_ptr()), "mmpl_cfg_dpmpp_step_f32_table")
-            return
-        assert sample_bf16 is None, "sample_bf16 is the shadow of a float32 sample"
-        _lib.check(_lib.load().mmpl_cfg_dpmpp_step_table(
-            _lib.ptr(flow_cond), _lib.ptr(flow_uncond), _lib.ptr(sample), _lib.ptr(m0), _lib.ptr(m1), sample.numel(),
-            _lib.ptr(self._table), _lib.ptr(self._counter), _lib.ptr(timestep), _lib.ptr(self._t_table), timestep.numel(), self._table_n,
-            _lib.stream_ptr()), "mmpl_cfg_dpmpp_step_table")
-
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = True):
-        """Reference call shape (fm_solvers.py:706).  `timestep` is accepted and ignored: the steps are counted, as the reference's
-        internal step counter does after the first call."""
-        out = self.step_cfg(model_output.to(torch.bfloat16).contiguous(), None, 0.0, sample.contiguous().clone())   # (flows are bf16)
-        return (out,) if not return_dict else {"prev_sample": out}
 
 
 class FlowMatchScheduler:

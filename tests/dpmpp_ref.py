@@ -1,4 +1,4 @@
-"""Host side of the exact tests of dpmpp_kernel / dpmpp_table_kernel (csrc/dpmpp.hip, through mmpl_cfg_dpmpp_step / _table): the
+"""Host side of the exact tests of the bf16 DPM-Solver++ step (csrc/sampler.hip, through mmpl_cfg_dpmpp_step / _table): the
 kernel's chain restated in numpy float32 and the operands the GPU test launches on.
 
 Every operation of the chain is ONE IEEE fp32 operation (numpy float32 arithmetic is IEEE, the kernel is compiled with
@@ -20,6 +20,9 @@ STEPS_50 = (0, 1, 2, 25, 49)                         # of the 50-step, shift-5 s
 STEPS_10 = (8, 9)                                    # of the 10-step, shift-5 schedule
 ORDERS = {(50, 0): 1, (50, 1): 2, (50, 2): 2, (50, 25): 2, (50, 49): 1, (10, 8): 2, (10, 9): 1}
 SIZES = (1, 255, 8192 * 256 + 257)                   # 2 097 409: a lone element-wise tail, a tail behind 31 vectors, 1025 blocks + a tail
+STRIDE_SIZE = 8192 * 256 * 8 + 2051                  # the grid is capped at 8192 blocks x 256 lanes x 8 elements: 2051 elements into the loop's second round
+STRIDE_PERIOD = 1_000_003                            # the chain is element-wise: at STRIDE_SIZE the operands are this many values, tiled (a prime: no stride
+                                                     # of the kernel is a multiple of it, so an element taken from the wrong place shows)
 MUTATIONS = ("scalar_rounded", "d1_unrounded", "m_swapped")
 FIELDS = ("guidance", "sigma_cur", "order", "c1", "c2", "inv_r0")
 MUTANT_SLICE = 4096                                  # the chain is element-wise: the mutants are evaluated on the first elements only
@@ -42,7 +45,7 @@ def operands(n, seed=0):
 
 
 def dpmpp_chain(st, fc, fu, x, m0, m1, mutation=None):
-    """dpmpp_one of csrc/dpmpp.hip in numpy float32 (st: any object with MmplDpmppStep's fields; fu None = fc is the combined flow;
+    """the bf16 DPM-Solver++ solver of csrc/sampler.hip in numpy float32 (st: any object with MmplDpmppStep's fields; fu None = fc is the combined flow;
     m0, m1: the history BEFORE the step; m1's values are not read: the rotation overwrites it).
     -> ([x, m0, m1] after the step as bf16 bits, the list of every fp32 intermediate that is rounded)."""
     q = (lambda v: rbf(F32(v))) if mutation == "scalar_rounded" else F32

@@ -1,4 +1,4 @@
-"""Host side of the exact tests of the float32 latent chain (csrc/fp32_chain.hip through mmpl_cfg_unipc_step_f32 /
+"""Host side of the exact tests of the float32 latent chain (csrc/sampler.hip through mmpl_cfg_unipc_step_f32 /
 mmpl_cfg_dpmpp_step_f32 and their _table forms): the two kernels restated per element in torch float32 operations, one torch
 operation per IEEE operation of the kernel, in the kernel's order (the formulas at the entries in include/mmpl_hip.h), and the
 operands the GPU test launches on.
@@ -30,7 +30,7 @@ def cfg_flow(fc, fu, guidance):
 
 
 def unipc_f32(st, fc, fu, x, m0, m1, last, mutation=None):
-    """UniPCF32 of csrc/fp32_chain.hip (st: any object with MmplUniPCStepF32's fields; the state BEFORE the step).
+    """the float32 UniPC solver of csrc/sampler.hip (st: any object with MmplUniPCStepF32's fields; the state BEFORE the step).
     -> (x, m0, m1, last) after the step, float32.  `mutation` = a plausible wrong kernel: 'inv_rk' multiplies by 1 / rk where the
     reference divides (the bf16 kernel's struct), 'bf16_rho' rounds the rhos to bf16 (`rhos_c.to(x.dtype)` of a bf16 sample)."""
     div = (lambda a, rk: a * (_s(1.0) / _s(rk))) if mutation == "inv_rk" else (lambda a, rk: a / _s(rk))
@@ -54,7 +54,7 @@ def unipc_f32(st, fc, fu, x, m0, m1, last, mutation=None):
 
 
 def dpmpp_f32(st, fc, fu, x, m0, m1):
-    """DpmppF32 of csrc/fp32_chain.hip (st: MmplDpmppStep's fields; m1's values are not read: the rotation overwrites it).
+    """the float32 DPM-Solver++ solver of csrc/sampler.hip (st: MmplDpmppStep's fields; m1's values are not read: the rotation overwrites it).
     -> (x, m0, m1) after the step, float32."""
     f = cfg_flow(fc, fu, st.guidance)
     mc = x - _s(st.sigma_cur) * f

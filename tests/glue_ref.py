@@ -1,5 +1,5 @@
 """Exact-input reference of the glue kernels of csrc/t5.hip (gather, softmax, transpose, gated GELU, zero-pad), of csrc/i2v.hip
-(gelu_erf, add) and of unipc_kernel / unipc_table_kernel (csrc/elementwise.hip), one launch at a time through mmpl_t5_gather,
+(gelu_erf, add) and of the bf16 UniPC step (csrc/sampler.hip), one launch at a time through mmpl_t5_gather,
 mmpl_t5_softmax, mmpl_t5_transpose, mmpl_t5_gated, mmpl_t5_zero_pad, mmpl_gelu_erf, mmpl_add and mmpl_cfg_unipc_step / _table: the
 case tables of tests/test_glue_exact_gpu.py, seeded generators, the buffer geometry (canaries), references in numpy float64 /
 float32, independent fp32 emulations with the value mutations the tests must catch, and the criteria.  numpy only: importable
@@ -16,7 +16,7 @@ Bit for bit, no allowance.
   zero-pad    rows under mask == 0 become +0, kept rows (arbitrary patterns, NaNs included) are untouched.
   add         ONE fp32 add of two bf16 values and one RNE: numpy float32 does exactly that.  The operands are finite and their sum is
               zero or at least 2^-126 in magnitude (`no_subnormal`: the project states no flush mode, so no bit-exact case may depend on one).
-  UniPC       every operation of unipc_body is one IEEE fp32 operation between two bf16 roundings, so the kernel equals the
+  UniPC       every operation of the bf16 UniPC solver is one IEEE fp32 operation between two bf16 roundings, so the kernel equals the
               emulation (tests/test_scheduler_host.py: emulate_kernel; restated here in numpy as `unipc_chain`, which also returns
               every intermediate for the subnormal check) in every bit of x, m0, m1 and last_sample, or it is wrong.
 
@@ -493,7 +493,7 @@ def softmax_needed_E(got, x, d, top=2.0 ** -12):
 # ------------------------------------------------------------------ UniPC
 UNIPC_STEPS = (0, 1, 2, 25, 49)                      # of the 50-step, shift-5 schedule at guidance 5
 UNIPC_ORDERS = {0: (0, 1, 1), 1: (1, 1, 2), 2: (1, 2, 2), 25: (1, 2, 2), 49: (1, 2, 1)}   # (use_corrector, corr_order, pred_order)
-UNIPC_SIZES = (1, 255, 8192 * 256 + 257)             # 2 097 409: past the grid cap of 8192 blocks
+UNIPC_SIZES = (1, 255, 8192 * 256 + 257)             # 2 097 409: a lone element-wise tail, a tail behind 31 vectors, 1025 blocks + a tail
 UNIPC_MUTATIONS = ("diff_unrounded", "pred_m_swapped", "half_d1_unrounded")   # the last is value-neutral (0.5 d1 is exact in bf16)
 UNIPC_FIELDS = ("guidance", "sigma_cur", "use_corrector", "corr_order", "c_c1", "c_c2", "c_c3", "c_inv_rk", "c_rho0", "c_rho_last",
                 "pred_order", "p_c1", "p_c2", "p_c3", "p_inv_rk")
@@ -506,7 +506,7 @@ def unipc_operands(n, seed=0):
 
 
 def unipc_chain(st, fc, fu, x, m0, m1, last, mutation=None):
-    """unipc_body in numpy float32 (st: any object with MmplUniPCStep's fields; fu None = fc is the combined flow).
+    """the bf16 UniPC solver of csrc/sampler.hip in numpy float32 (st: any object with MmplUniPCStep's fields; fu None = fc is the combined flow).
     -> (x, m0, m1, last_sample as bf16 bits, the list of every fp32 intermediate)."""
     s = lambda k: F32(getattr(st, k))
     mids = []

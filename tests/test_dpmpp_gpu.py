@@ -1,4 +1,4 @@
-"""The fused CFG + DPM-Solver++ step (csrc/dpmpp.hip through mmpl_cfg_dpmpp_step / _table) and the pipeline with
+"""The fused CFG + DPM-Solver++ step (csrc/sampler.hip through mmpl_cfg_dpmpp_step / _table) and the pipeline with
 sample_solver='dpm++' on the device (-m gpu).
 
   single steps   one launch per case on the operands of tests/dpmpp_ref.py: x, m0 and m1 equal `dpmpp_chain` in every bit (the chain is
@@ -99,6 +99,23 @@ def test_unaligned_operands_take_the_element_wise_path(lib):
     for b, w in zip(bufs[2:], want):
         g = host(b)
         assert g[0] == G.CANARY and np.array_equal(g[1:n + 1], w) and bool((g[n + 1:] == G.CANARY).all())
+
+
+def test_the_grid_stride_loop_past_the_block_cap(lib):
+    """n = dpmpp_ref.STRIDE_SIZE, step 25 of 50: the first lanes go round the loop a second time, the last of them into the ragged tail.
+    Every element against the emulation, evaluated on one period of the tiled operands."""
+    n, st = D.STRIDE_SIZE, _step_scalars(50)[25]
+    ops = D.operands(D.STRIDE_PERIOD, seed=3)
+    want, _ = D.dpmpp_chain(st, *ops)
+    bufs = [dev(G.with_canary(np.resize(o, n))) for o in ops]
+    _check(lib, lib.mmpl_cfg_dpmpp_step(*[_ptr(b) for b in bufs], n, C.byref(st), _stream()), "dpm++ past the block cap")
+    torch.cuda.synchronize()
+    for what, b, w in zip(("x", "m0", "m1"), bufs[2:], want):
+        g = host(b)
+        assert np.array_equal(g[:n], np.resize(w, n)), what
+        assert bool((g[n:] == G.CANARY).all()) and g.size == n + TAIL, what
+    for b, src in zip(bufs[:2], ops[:2]):                 # the flows are read only
+        assert np.array_equal(host(b), G.with_canary(np.resize(src, n)))
 
 
 def test_table_step_at_one_entry_equals_the_emulation(lib):

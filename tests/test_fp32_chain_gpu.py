@@ -1,4 +1,4 @@
-"""The float32 latent chain's kernels on the device (-m gpu): csrc/fp32_chain.hip through mmpl_cfg_unipc_step_f32 /
+"""The float32 latent chain's kernels on the device (-m gpu): csrc/sampler.hip through mmpl_cfg_unipc_step_f32 /
 mmpl_cfg_dpmpp_step_f32 and their _table forms, one launch each, against tests/fp32_chain_ref.py BIT FOR BIT (the restatement is
 one IEEE fp32 operation per kernel operation; tests/test_fp32_chain_host.py ties it to the REAL reference's schedulers).
 
@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from tests import fp32_chain_ref as R
+from tests.dpmpp_ref import STRIDE_PERIOD, STRIDE_SIZE
 from tests.test_fp32_chain_host import FX, f32_scheduler, recorded_rows
 from tests.test_rowpass_exact_gpu import _check, _ptr, _stream
 
@@ -118,6 +119,53 @@ def test_dpmpp_f32_single_steps_equal_the_restatement(lib, n, off):
         for with_u in (True, False):
             for with_shadow in (True, False):
                 _launch_and_compare(lib, "dpm++", step, n, off, with_u, with_shadow)
+
+
+def test_dpmpp_f32_strides_past_the_block_cap(lib):
+    """n = dpmpp_ref.STRIDE_SIZE, step 25 of 50: the first lanes go round the grid-stride loop a second time, the last of them into
+    the ragged tail.  Every element against the restatement, evaluated on one period of the tiled operands."""
+    n, st = STRIDE_SIZE, _scalars("dpm++")[25]
+    ops = R.operands(STRIDE_PERIOD, seed=25)[:5]
+    want = R.dpmpp_f32(st, *ops)
+    tile = lambda v: v.repeat(-(-n // STRIDE_PERIOD))[:n]
+    flows = [_padded(tile(v), 0, SENT_B) for v in ops[:2]]
+    state = [_padded(tile(v), 0, SENT_F) for v in ops[2:]]
+    shadow = _padded(torch.full([n], SENT_B, dtype=BF), 0, SENT_B)
+    _check(lib, lib.mmpl_cfg_dpmpp_step_f32(*[_ptr(v) for _, v in flows + state + [shadow]], n, C.byref(st), _stream()), "dpm++ f32 past the block cap")
+    torch.cuda.synchronize()
+    for what, (buf, v), w in zip(("x", "m0", "m1"), state, want):
+        assert torch.equal(_bits(v), _bits(tile(w))) and _intact(buf, 0, n, SENT_F), what
+    assert torch.equal(_bits(shadow[1]), _bits(tile(want[0].to(BF)))) and _intact(shadow[0], 0, n, SENT_B)
+    for (buf, v), src in zip(flows, ops[:2]):                              # the flows are read only
+        assert torch.equal(_bits(v), _bits(tile(src))) and _intact(buf, 0, n, SENT_B)
+
+
+@pytest.mark.parametrize("dtype", [BF, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("solver", ["unipc", "dpm++"])
+def test_a_negative_counter_is_a_no_op_in_every_table_form(lib, solver, dtype):
+    """counter = -1: x, the solver state, the shadow, the counter and `timestep` keep every bit.  table_dev is row 1 of a table whose
+    every row holds the valid coefficients of step 25, so a kernel without the guard applies row 0 and changes the tensors: it does
+    not read out of bounds."""
+    from mmpl_amd.pipeline._common import make_sample_scheduler
+    n = 255
+    fc, fu, *state = R.operands(n, seed=4)
+    state = [v.to(dtype).to(DEV) for v in state[:4 if solver == "unipc" else 3]]          # x, m0, m1 (, last_sample)
+    s, _ = make_sample_scheduler(solver, 1000, 50, 5.0, "cpu")
+    s._ensure_state(torch.zeros(1, dtype=dtype))                                          # the rows' struct is the storage type's
+    row = bytes([s.step_scalars(5.0) for _ in range(26)][25])
+    table = torch.frombuffer(bytearray(row * 3), dtype=torch.uint8).to(DEV)
+    counter = torch.full([1], -1, dtype=torch.int32, device=DEV)
+    t, t_table = torch.full([3], -1.0, dtype=F32, device=DEV), torch.full([2], 500.0, dtype=F32, device=DEV)
+    shadow = [torch.full([n], SENT_B, dtype=BF, device=DEV)] if dtype == F32 else []
+    fc, fu = fc.to(DEV), fu.to(DEV)
+    keep = [v.clone() for v in (*state, *shadow, counter, t)]
+    fn = getattr(lib, f"mmpl_cfg_{s._stem}_step{'_f32' if dtype == F32 else ''}_table")
+    _check(lib, fn(*[_ptr(v) for v in (fc, fu, *state, *shadow)], n, _ptr(table, len(row)), _ptr(counter), _ptr(t), _ptr(t_table), 3, 2,
+                   _stream()), f"{solver} {dtype} counter -1")
+    torch.cuda.synchronize()
+    assert int(counter.item()) == -1
+    for a, b in zip((*state, *shadow, counter, t), keep):
+        assert torch.equal(_bits(a), _bits(b))
 
 
 def test_a_contracted_or_reciprocal_kernel_would_show(lib):

@@ -1,6 +1,6 @@
 """Host tests of upstream Wan2.1's float32 latent chain (no GPU):
 
-  restatement    tests/fp32_chain_ref.py (the two kernels of csrc/fp32_chain.hip per element, one torch float32 operation per IEEE
+  restatement    tests/fp32_chain_ref.py (the two float32 solvers of csrc/sampler.hip per element, one torch float32 operation per IEEE
                  operation), driven by the float32 scalars of mmpl_amd/scheduler.py, reproduces the REAL reference's schedulers
                  (tests/golden/fp32_chain.pt, make_golden_fp32_chain.py) bit for bit at EVERY step, for both solvers and both
                  schedules.  The scalars the replay carries are the fixture's record of them (`rows`): the reference's 0-dim

@@ -1,7 +1,7 @@
-"""The glue kernels of csrc/t5.hip and csrc/i2v.hip and the UniPC step of csrc/elementwise.hip one launch at a time on exact inputs
+"""The glue kernels of csrc/t5.hip and csrc/i2v.hip and the bf16 UniPC step of csrc/sampler.hip one launch at a time on exact inputs
 (-m gpu): t5_gather_kernel, t5_softmax_kernel, t5_transpose_kernel, t5_gated_kernel, t5_zero_pad_kernel, gelu_erf_kernel and
-add_kernel through their entry points (the launchers mmpl_t5_encode, mmpl_i2v_* and mmpl_clip_visual call), unipc_kernel and
-unipc_table_kernel through mmpl_cfg_unipc_step / _table.
+add_kernel through their entry points (the launchers mmpl_t5_encode, mmpl_i2v_* and mmpl_clip_visual call), the UniPC step and its
+table form through mmpl_cfg_unipc_step / _table.
 
 Every case of tests/glue_ref.py's tables makes one launch and asserts
   - ZERO elements outside their candidates (glue_ref's docstring derives them; tests/test_glue_ref.py proves on the CPU that the
@@ -179,17 +179,45 @@ def _unipc_compare(name, n, st, ops, with_u, bufs):
         assert np.array_equal(host(t), G.with_canary(src))
 
 
-@pytest.mark.parametrize("with_u", [True, False], ids=["cfg", "combined"])
-@pytest.mark.parametrize("n", G.UNIPC_SIZES)
-def test_unipc_equals_emulation(lib, n, with_u):
+def _unipc_steps(lib, n, with_u, steps):
     ops = G.unipc_operands(n)
-    for step in G.UNIPC_STEPS:
+    for step in steps:
         st = _step_scalars()[step]
         assert (st.use_corrector, st.corr_order, st.pred_order) == G.UNIPC_ORDERS[step]
         bufs = [dev(G.with_canary(o)) for o in ops]
         _check(lib, lib.mmpl_cfg_unipc_step(_ptr(bufs[0]), _ptr(bufs[1]) if with_u else None, *[_ptr(b) for b in bufs[2:]], n,
                                             C.byref(st), _stream()), f"unipc step {step}")
         _unipc_compare(f"unipc n={n} step {step} {'cfg' if with_u else 'combined'}", n, st, ops, with_u, bufs)
+
+
+@pytest.mark.parametrize("with_u", [True, False], ids=["cfg", "combined"])
+@pytest.mark.parametrize("n", G.UNIPC_SIZES)
+def test_unipc_equals_emulation(lib, n, with_u):
+    _unipc_steps(lib, n, with_u, G.UNIPC_STEPS)
+
+
+@pytest.mark.parametrize("with_u", [True, False], ids=["cfg", "combined"])
+@pytest.mark.parametrize("n", [7, 8, 9])
+def test_unipc_around_the_vector_width(lib, n, with_u):
+    """One lane's 8 elements: an element-wise tail alone, exactly one 16-byte access, one access and a tail of one; at step 2 (corrector
+    and predictor of order 2) and step 0 (no corrector, order 1)."""
+    _unipc_steps(lib, n, with_u, (2, 0))
+
+
+def test_unipc_unaligned_operands_take_the_element_wise_path(lib):
+    """every pointer 2 bytes past a 16-byte boundary: the same bits, the element in front of each buffer and the canaries intact."""
+    n, st = 255, _step_scalars()[25]
+    ops = G.unipc_operands(n, seed=2)
+    bufs = [dev(np.concatenate([np.full(1, G.CANARY, dtype=np.uint16), G.with_canary(o)])) for o in ops]
+    _check(lib, lib.mmpl_cfg_unipc_step(*[_ptr(b, 2) for b in bufs], n, C.byref(st), _stream()), "unipc unaligned")
+    torch.cuda.synchronize()
+    want = emulate_kernel(st, *[_bf(o) for o in ops])
+    for b, w in zip(bufs[2:], want):
+        g = host(b)
+        assert g[0] == G.CANARY and np.array_equal(g[1:n + 1], w.view(torch.int16).numpy().view(np.uint16))
+        assert bool((g[n + 1:] == G.CANARY).all()) and g.size == n + 1 + TAIL
+    for b, src in zip(bufs[:2], ops[:2]):                 # the flows are read only
+        assert np.array_equal(host(b)[1:], G.with_canary(src))
 
 
 def test_unipc_table_equals_emulation(lib):

@@ -12,7 +12,7 @@ rbf = lambda t: t.to(BF).float()  # noqa: E731
 
 
 def emulate_kernel(st, fc, fu, x, m0, m1, last):
-    """mmpl_amd/csrc/elementwise.hip: unipc_kernel, in torch."""
+    """mmpl_amd/csrc/sampler.hip: the bf16 UniPC step, in torch."""
     fc, fu, x, m0, m1, last = [t.float() for t in (fc, fu, x, m0, m1, last)]
     flow = rbf(fu + rbf(st.guidance * rbf(fc - fu)))
     m_conv = rbf(x - rbf(st.sigma_cur * flow))
