@@ -197,6 +197,52 @@ int mmpl_dit_rope_tables(const MmplDit* h, float* cos_out, float* sin_out, mmpl_
  * from their share_out forward's; synchronises `stream` and resets the count.  0 when the switch is off. */
 int mmpl_dit_share_check_failures(MmplDit* h, long long* count, mmpl_stream_t stream);
 
+/* ---- step caching (TeaCache) of the 50-step samplers.  A denoise step whose timestep embedding has barely moved since the last
+ * computed step skips the transformer blocks: it adds the residual that step left (x after the last block - x after the patch
+ * embedding) to its own patch embedding and runs only the head.  Which steps skip depends on the timesteps and the weights alone
+ * (mmpl_dit_time_embed + mmpl_rel_l1_rows below), so the host knows it before sampling starts.
+ * mmpl_dit_forward_at_cached / mmpl_dit_forward_full_cached: every argument of mmpl_dit_forward_at / mmpl_dit_forward_full (y_in NULL)
+ * or mmpl_dit_forward_full_i2v (y_in non-NULL) under its contract there, plus
+ *   residual   : dev [n_frames * S, dim] bf16, mmpl_dit_step_cache_bytes(h, n_frames) bytes, 256-byte aligned, owned by the caller: one per
+ *                (CFG branch, stage shape)
+ *   cache_mode : 0 OFF    -- `residual` is ignored; the launches of the uncached entry, bit for bit.
+ *                1 RECORD -- the launches of the uncached entry (out, the cache writes, share_out / share_in and attn_history are what
+ *                            they are there, bit for bit), then after the last block the patch-embedding GEMM once more into the
+ *                            LayerNorm buffer (dead there; its input patches are still in the workspace, so x_0 has the bits the
+ *                            first run gave) and residual[r,c] = bf16(float(x_L[r,c]) - float(x_0[r,c])): one fp32 subtraction, one
+ *                            rounding.  The workspace sizes do not change.
+ *                2 REUSE  -- patchify (patchify2 with y_in), the patch-embedding GEMM with `residual` as its residual operand
+ *                            (epilogue 4: x = bf16(acc + bias + residual), one rounding), the timestep embedding and the head
+ *                            modulation, the head, unpatchify.  No block runs and no K / V is written: write_slots and
+ *                            visible_slots are validated but nothing is persisted; cross_k, cross_v, share_out, share_in and
+ *                            attn_history may be NULL and are ignored.
+ * Rejected before the first launch, each with its own message: a cache_mode outside 0 .. 2; in mode 1 or 2 a NULL residual or one
+ * that is not 256-byte aligned; and everything the uncached entry rejects.  mmpl_dit_forward_groups has no cached form. */
+size_t mmpl_dit_step_cache_bytes(const MmplDit* h, int n_frames);
+int mmpl_dit_forward_at_cached(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const int* frame_ids,
+                               const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
+                               int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
+                               void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                               mmpl_stream_t stream, int cache_mode, void* residual);
+int mmpl_dit_forward_full_cached(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const void* cross_k, const void* cross_v,
+                                 int cross_rows, void* share_out, const void* share_in, void* attn_history, void* out, void* workspace,
+                                 size_t workspace_bytes, mmpl_stream_t stream, const void* y_in, int cache_mode, void* residual);
+/* The timestep embedding of n_t timesteps at once: the sinusoid, time_embedding.0 (+ SiLU), time_embedding.2 -> e_out [n_t, dim] bf16,
+ * and SiLU + time_projection.1 -> e0_out [n_t, 6 * dim] bf16 (NULL = not wanted): the launches a forward makes for its own
+ * timesteps.  Row i of those GEMMs depends on row i of their input alone, so row i has the bits a forward computes for t_dev[i].
+ *   t_dev      : dev float32 [n_t], 1 <= n_t <= 4096
+ *   workspace  : dev, 256-byte aligned, at least mmpl_dit_time_embed_workspace_bytes(h, n_t) bytes */
+size_t mmpl_dit_time_embed_workspace_bytes(const MmplDit* h, int n_t);
+int mmpl_dit_time_embed(MmplDit* h, const float* t_dev, int n_t, void* e_out, void* e0_out, void* workspace, size_t workspace_bytes,
+                        mmpl_stream_t stream);
+/* out_dev[i] = (sum_c |x[i+1,c] - x[i,c]|) / (sum_c |x[i,c]|), i < rows - 1: the relative L1 distance of consecutive rows of the bf16
+ * matrix x [rows, d] (row stride ld elements), in float32 -- the step-cache indicator over the rows of mmpl_dit_time_embed.
+ * Deterministic, no float atomics.  Summation order of both sums: one 256-thread block per i; thread t adds the terms of columns
+ * t, t + 256, t + 512, ... in increasing order; the 64 partials of a wave combine by a butterfly (partner lane ^ 32, then ^ 16, ^ 8,
+ * ^ 4, ^ 2, ^ 1); the four wave sums are added in wave order 0, 1, 2, 3; then ONE IEEE division.  A zero row i gives inf or nan as
+ * that division does.  rows >= 2, d >= 1, ld >= d. */
+int mmpl_rel_l1_rows(const void* x, int ld, int rows, int d, float* out_dev, mmpl_stream_t stream);
+
 /* attention() seam (wan/modules/attention.py:139-185) over paged K/V.  q/o: row r, head h at base + r*ld + h*128; every base
  * 16-byte aligned, every leading dimension a multiple of 8 elements (rows are read and written 16 bytes per lane).
  * k_pages/v_pages: host arrays of n_pages dev pointers, each page = page_rows rows of stride ldk/ldv.

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmmpl_hip.so")
-SOURCES = ["device_state.hip", "gemm.hip", "attention.hip", "attn_w64.hip", "attn_w64_groups.hip", "elementwise.hip", "vae_kernels.hip", "vae.hip", "taehv_kernels.hip", "taehv.hip", "taehv_enc_kernels.hip", "taehv_enc.hip","kernel_entry.hip", "t5.hip", "i2v.hip", "fewstep.hip", "sampler.hip", "probe.hip", "api.hip"]
+SOURCES = ["device_state.hip", "gemm.hip", "attention.hip", "attn_w64.hip", "attn_w64_groups.hip", "elementwise.hip", "vae_kernels.hip", "vae.hip", "taehv_kernels.hip", "taehv.hip", "taehv_enc_kernels.hip", "taehv_enc.hip","kernel_entry.hip", "t5.hip", "i2v.hip", "fewstep.hip", "sampler.hip", "step_cache.hip", "probe.hip", "api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed"] + os.environ.get("MMPL_EXTRA_HIPCC_FLAGS", "").split()
 
 

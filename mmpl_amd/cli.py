@@ -247,6 +247,55 @@ def extend_refusal(args, fewstep: bool):
     return None
 
 
+def step_cache_coefficients(text: str):
+    """--teacache_coefficients a,b,...: the rescaling polynomial, highest power first."""
+    return tuple(float(c) for c in text.split(","))
+
+
+def step_cache_policy(args):
+    """The StepCachePolicy of --teacache_thresh / --teacache_coefficients / --teacache_ret_steps; None without --teacache_thresh
+    (step caching off: the pipelines as they are).  --teacache_ret_steps is upstream TeaCache's use_ret_steps: the first 5 steps
+    and nothing at the end forced, the indicator e0."""
+    thresh = getattr(args, "teacache_thresh", None)
+    if thresh is None:
+        return None
+    from .step_cache import StepCachePolicy
+    coeff = getattr(args, "teacache_coefficients", None)
+    kw = dict(coefficients=step_cache_coefficients(coeff)) if coeff else {}
+    if getattr(args, "teacache_ret_steps", False):
+        kw.update(ret_steps=5, cutoff=int(args.sampling_steps), indicator="e0")
+    return StepCachePolicy(float(thresh), **kw)
+
+
+def step_cache_refusal(args, world: int, fewstep: bool):
+    """Why --teacache_thresh cannot run this command line (None = it can, or it was not asked for): step caching skips steps of
+    the 50-step multistep samplers of one process."""
+    if getattr(args, "teacache_thresh", None) is None:
+        for flag in ("teacache_coefficients", "teacache_ret_steps"):
+            if getattr(args, flag, None):
+                return f"--{flag}: only with --teacache_thresh X"
+        return None
+    if args.teacache_thresh < 0:
+        return f"--teacache_thresh {args.teacache_thresh}: at least 0 (0 computes every step)"
+    if int(getattr(args, "num_samples", 1)) > 1:
+        return "--teacache_thresh: batched generation (--num_samples) runs the grouped forward, which has no cached form"
+    if fewstep:
+        return ("--teacache_thresh: the few-step pipeline (config with denoising_step_list) runs 4 steps that all differ; step "
+                "caching belongs to the 50-step samplers")
+    if world > 1 or getattr(args, "cfg_split", False):
+        return ("--teacache_thresh: step caching is single-process (the two CFG branches' residuals live on one GPU); run without "
+                "torchrun / --cfg_split")
+    coeff = getattr(args, "teacache_coefficients", None)
+    if coeff:
+        try:
+            ok = len(step_cache_coefficients(coeff)) >= 1
+        except ValueError:
+            ok = False
+        if not ok:
+            return f"--teacache_coefficients {coeff}: comma-separated numbers, highest power first (numpy.poly1d order)"
+    return None
+
+
 def first_refusal(args, world: int, fewstep: bool):
     """The first reason this command line cannot run, asked in ``main``'s order (None = it can).  ``main`` has put fewstep,
     num_frame_per_block, kv_window and pixel_hw on ``args``."""
@@ -254,7 +303,8 @@ def first_refusal(args, world: int, fewstep: bool):
               lambda: rolling_refusal(args, fewstep), lambda: solver_refusal(args, fewstep),
               lambda: fp32_refusal(args, fewstep),
               lambda: fewstep_refusal(args, world) if fewstep and not args.bidirectional else None,
-              lambda: extend_refusal(args, fewstep), lambda: samples_refusal(args, fewstep))
+              lambda: extend_refusal(args, fewstep), lambda: samples_refusal(args, fewstep),
+              lambda: step_cache_refusal(args, world, fewstep))
     return next((why for why in (check() for check in checks) if why is not None), None)
 
 
@@ -432,6 +482,16 @@ def main(argv=None):
                          "that many")
     ap.add_argument("--extend_context", type=int, default=None, metavar="N",
                     help="with --extend: latent frames of context (the clip's last 4 N frames); default num_frame_per_block, a multiple of it")
+    ap.add_argument("--teacache_thresh", type=float, default=None, metavar="X",
+                    help="50-step pipelines, one process: step caching (TeaCache) -- a denoise step whose timestep embedding moved less "
+                         "than X (accumulated relative L1, rescaled by --teacache_coefficients) since the last computed step reuses that "
+                         "step's residual and runs only the head; 0 computes every step (bit-identical to no flag)")
+    ap.add_argument("--teacache_coefficients", type=str, default=None, metavar="a,b,...",
+                    help="with --teacache_thresh: the rescaling polynomial, highest power first (the TeaCache project's per-model fit; "
+                         "none is built in: the default is the identity)")
+    ap.add_argument("--teacache_ret_steps", action="store_true",
+                    help="with --teacache_thresh: upstream TeaCache's use_ret_steps -- the first 5 steps always computed, no forced "
+                         "last step, the indicator e0 (the projected embedding) instead of e")
     args = ap.parse_args(argv)
     i2v_clip = bool(args.bidirectional and args.i2v_model)               # the whole-clip Wan-I2V model type: WanI2V.generate's defaults
     if args.sampling_steps is None:
@@ -485,6 +545,7 @@ def main(argv=None):
     mode = "i2v" if args.i2v else "t2v"
     pipe = CausalFPSInferencePipeline(config, dev, generator=gen, text_encoder=enc, vae=vae, device_cond=dev, device_uncond=dev, save=None,
                                       mode=mode, geometry=geo)
+    pipe.step_cache = step_cache_policy(args)
     image_latent, first_px = None, None
     if args.i2v:                                 # I2V/Wan_fps_inference_1gpu.py:100-104: the image -> vae.encode_to_latent
         first_px = _load_image(args.image, geo, dev)
@@ -622,6 +683,7 @@ def build_bidirectional_pipeline(config, args, dev, geo, mcfg):
             pipe.latent_dtype = torch.float32
         if getattr(args, "sample_shift", None) is not None:
             pipe.shift = float(args.sample_shift)
+        pipe.step_cache = step_cache_policy(args)
     return pipe
 
 

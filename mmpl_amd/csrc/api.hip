@@ -382,11 +382,20 @@ struct FwdCall {
   // visible_slots holds n_groups lists of n_visible; group_cross_k / _v the samples' text K / V (cross_k / cross_v are then sample 0's)
   int n_groups;
   const void *const *group_cross_k, *const *group_cross_v;
+  // step caching (the *_cached entries; 0 / NULL = every other entry): 1 RECORD leaves x_L - x_0 in `residual`, 2 REUSE adds it to
+  // the patch embedding and runs no block
+  int cache_mode;
+  void* residual;
   int run() const;
 };
 
 int FwdCall::run() const {
   if (!h || h->w.empty()) return fail(me, "weights not bound");
+  if (cache_mode < 0 || cache_mode > 2) return fail(me, "cache_mode outside 0 .. 2 (OFF, RECORD, REUSE)");
+  if (cache_mode && !residual) return fail(me, "cache_mode RECORD / REUSE needs a residual buffer (mmpl_dit_step_cache_bytes)");
+  if (cache_mode && reinterpret_cast<uintptr_t>(residual) % 256) return fail(me, "residual must be 256-byte aligned");
+  if (cache_mode && n_groups > 1) return fail(me, "a grouped forward has no cached form");
+  const bool reuse = cache_mode == 2;
   const MmplDitConfig& c = h->cfg;
   if (nF < 1 || nF > (full ? MMPL_MAX_PAGES : c.max_frames)) return fail(me, "n_frames out of range");
   int n_write = 0;
@@ -417,15 +426,19 @@ int FwdCall::run() const {
                                   c.lat_w, s), "patchify (x, y)");
   else
     MMPL_HIP_TRY(mmpl_launch_patchify((const bf16_t*)x_in, w.patch, h->pe_k, nF, c.in_dim, c.lat_h, c.lat_w, s), "patchify");
-  TRY(gemm(w.patch, h->pe_k, h->G(G_PE_W), h->pe_k, h->G(G_PE_B), w.x, d, Lq, d, h->pe_k, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
+  // REUSE: x = bf16(patch embedding + the residual the last computed step left), one rounding
+  TRY(gemm(w.patch, h->pe_k, h->G(G_PE_W), h->pe_k, h->G(G_PE_B), w.x, d, Lq, d, h->pe_k, reuse ? EPI_RES : EPI_BIAS,
+           reuse ? (const bf16_t*)residual : nullptr, reuse ? d : 0, nullptr, 0, 1, s));
   MMPL_HIP_TRY(mmpl_launch_sinusoid(t_dev, w.sinu, nT, c.freq_dim, s), "sinusoid");
   TRY(gemm(w.sinu, c.freq_dim, h->G(G_TE0_W), c.freq_dim, h->G(G_TE0_B), w.t1, d, nT, d, c.freq_dim, EPI_BIAS_SILU, nullptr,
            0, nullptr, 0, 1, s));
   TRY(gemm(w.t1, d, h->G(G_TE2_W), d, h->G(G_TE2_B), w.e, d, nT, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-  MMPL_HIP_TRY(mmpl_launch_silu(w.e, w.se, (size_t)nT * d, s), "silu");
-  TRY(gemm(w.se, d, h->G(G_TP_W), d, h->G(G_TP_B), w.e0, 6 * d, nT, 6 * d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
-  // e = bf16(modulation + e0) for every layer and for the head (causal_fps_model.py:338, 393)
-  MMPL_HIP_TRY(mmpl_launch_modulation(h->G(G_BLOCK_MOD), (size_t)6 * d, w.e0, 6 * d, 0, w.emod, c.num_layers, nT, 6, d, s), "modulation");
+  if (!reuse) {                                              // (the blocks' modulation vectors: no block runs in a reused step)
+    MMPL_HIP_TRY(mmpl_launch_silu(w.e, w.se, (size_t)nT * d, s), "silu");
+    TRY(gemm(w.se, d, h->G(G_TP_W), d, h->G(G_TP_B), w.e0, 6 * d, nT, 6 * d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
+    // e = bf16(modulation + e0) for every layer and for the head (causal_fps_model.py:338, 393)
+    MMPL_HIP_TRY(mmpl_launch_modulation(h->G(G_BLOCK_MOD), (size_t)6 * d, w.e0, 6 * d, 0, w.emod, c.num_layers, nT, 6, d, s), "modulation");
+  }
   MMPL_HIP_TRY(mmpl_launch_modulation(h->G(G_HEAD_MOD), 0, w.e, d, 1, w.emod_head, 1, nT, 2, d, s), "head modulation");
 
   const float scale = 1.0f / sqrtf(128.0f);
@@ -455,7 +468,7 @@ int FwdCall::run() const {
     if (which == 1) MMPL_HIP_TRY(mmpl_launch_share_check_compare(h->share_chk, s), "share check (compare)");
     return 0;
   };
-  for (int l = 0; l < c.num_layers; ++l) {
+  for (int l = 0; l < (reuse ? 0 : c.num_layers); ++l) {
     const bf16_t* em = w.emod + (size_t)l * nT * 6 * d;  // [nT][6][d]
     bf16_t* kc = (bf16_t*)k_cache + (size_t)l * layer_stride;
     bf16_t* vc = (bf16_t*)v_cache + (size_t)l * layer_stride;
@@ -613,6 +626,12 @@ int FwdCall::run() const {
     TRY(gemm(w.xn, d, h->Lw(l, L_F0_W), d, h->Lw(l, L_F0_B), w.big, f, Lq, f, d, EPI_BIAS_GELU, nullptr, 0, nullptr, 0, 1, s, tc, w.splitk));
     TRY(gemm(w.big, f, h->Lw(l, L_F2_W), f, h->Lw(l, L_F2_B), w.x, d, Lq, d, f, EPI_GATE_RES, w.x, d, em + 5 * d, mfs, S, s, tc, w.splitk));
   }
+  if (cache_mode == 1) {
+    // RECORD: x_0 once more (the patches are still in the workspace; the LayerNorm buffer is dead until the head norm), then x_L - x_0
+    TRY(gemm(w.patch, h->pe_k, h->G(G_PE_W), h->pe_k, h->G(G_PE_B), w.xn, d, Lq, d, h->pe_k, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
+    ProfScope ps(K_ELEMENTWISE, 0, s);
+    MMPL_HIP_TRY(mmpl_launch_residual_sub(w.x, w.xn, (bf16_t*)residual, (size_t)Lq * d, s), "step-cache residual");
+  }
   // ---- head + unpatchify (causal_fps_model.py:384-395, 1007-1030)
   {
     LnArgs a = ln_args(w.x, d, w.xn, d, Lq, d, c.eps);
@@ -640,7 +659,8 @@ int run_whole_clip(const FwdCall& a, bool i2v) {
   const char* me = a.me;
   MmplDit* h = a.h;
   if (!h) return fail(me, "null handle");
-  if (!a.x_in || (i2v && !a.y_in) || !a.t_dev || !a.cross_k || !a.cross_v || !a.out || !a.workspace) return fail(me, "null argument");
+  const bool need_cross = a.cache_mode != 2;                 // (a reused step runs no block)
+  if (!a.x_in || (i2v && !a.y_in) || !a.t_dev || (need_cross && (!a.cross_k || !a.cross_v)) || !a.out || !a.workspace) return fail(me, "null argument");
   if (i2v) {
     if (h->cfg.in_dim != 36 || h->cfg.out_dim != 16) return fail(me, "not an i2v handle (in_dim must be 36: 16 latent + 20 conditioning channels)");
     if (!h->img_k) return fail(me, "no image K / V attached (mmpl_dit_set_image_kv first)");
@@ -730,6 +750,77 @@ int mmpl_dit_forward_full_i2v(MmplDit* h, const void* x_in, const void* y_in, co
   a.cross_rows = cross_rows; a.share_out = share_out; a.share_in = share_in; a.attn_history = attn_history; a.out = out;
   a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = stream;
   return run_whole_clip(a, true);
+}
+
+size_t mmpl_dit_step_cache_bytes(const MmplDit* h, int n_frames) {
+  return (h && n_frames >= 1) ? round256((size_t)n_frames * h->S * h->cfg.dim * sizeof(bf16_t)) : 0;
+}
+
+// a reused step ignores what only the blocks read
+static void drop_block_operands(FwdCall& a) {
+  if (a.cache_mode == 2) { a.share_out = nullptr; a.share_in = nullptr; a.attn_history = nullptr; }
+}
+
+int mmpl_dit_forward_at_cached(MmplDit* h, const void* x_in, const float* t_dev, int nF, const int* frame_ids,
+                               const int* write_slots, const int* visible_slots, int n_visible, void* k_cache, void* v_cache,
+                               int n_slots, const void* cross_k, const void* cross_v, int cross_rows, void* share_out, const void* share_in,
+                               void* attn_history, void* out, void* workspace, size_t workspace_bytes, const int* frame_base_dev,
+                               mmpl_stream_t stream, int cache_mode, void* residual) {
+  FwdCall a = {};
+  a.me = "mmpl_dit_forward_at_cached"; a.h = h; a.x_in = x_in; a.t_dev = t_dev; a.nF = nF; a.frame_ids = frame_ids; a.write_slots = write_slots;
+  a.visible_slots = visible_slots; a.n_visible = n_visible; a.k_cache = k_cache; a.v_cache = v_cache; a.n_slots = n_slots;
+  a.cross_k = cross_k; a.cross_v = cross_v; a.cross_rows = cross_rows; a.share_out = share_out; a.share_in = share_in;
+  a.attn_history = attn_history; a.out = out; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  a.frame_base_dev = frame_base_dev; a.stream = stream; a.cache_mode = cache_mode; a.residual = residual;
+  drop_block_operands(a);
+  return a.run();
+}
+
+int mmpl_dit_forward_full_cached(MmplDit* h, const void* x_in, const float* t_dev, int n_frames, const void* cross_k, const void* cross_v,
+                                 int cross_rows, void* share_out, const void* share_in, void* attn_history, void* out, void* workspace,
+                                 size_t workspace_bytes, mmpl_stream_t stream, const void* y_in, int cache_mode, void* residual) {
+  FwdCall a = {};
+  a.me = "mmpl_dit_forward_full_cached"; a.full = true;
+  a.h = h; a.x_in = x_in; a.y_in = y_in; a.t_dev = t_dev; a.nF = n_frames; a.cross_k = cross_k; a.cross_v = cross_v;
+  a.cross_rows = cross_rows; a.share_out = share_out; a.share_in = share_in; a.attn_history = attn_history; a.out = out;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.stream = stream; a.cache_mode = cache_mode; a.residual = residual;
+  drop_block_operands(a);
+  return run_whole_clip(a, y_in != nullptr);
+}
+
+size_t mmpl_dit_time_embed_workspace_bytes(const MmplDit* h, int n_t) {
+  if (!h || n_t < 1 || n_t > 4096) return 0;
+  Carver k(nullptr);
+  k.take<bf16_t>((size_t)n_t * h->cfg.freq_dim);
+  k.take<bf16_t>((size_t)n_t * h->cfg.dim);
+  k.take<bf16_t>((size_t)n_t * h->cfg.dim);
+  return k.off;
+}
+
+int mmpl_dit_time_embed(MmplDit* h, const float* t_dev, int n_t, void* e_out, void* e0_out, void* workspace, size_t workspace_bytes,
+                        mmpl_stream_t stream) {
+  const char* me = "mmpl_dit_time_embed";
+  if (!h || !t_dev || !e_out || !workspace) return fail(me, "null argument");
+  if (h->w.empty()) return fail(me, "weights not bound");
+  if (n_t < 1 || n_t > 4096) return fail(me, "n_t out of range (1 .. 4096)");
+  if (workspace_bytes < mmpl_dit_time_embed_workspace_bytes(h, n_t)) return fail(me, "workspace too small");
+  if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(me, "workspace must be 256-byte aligned");
+  const MmplDitConfig& c = h->cfg;
+  const int d = c.dim;
+  hipStream_t s = (hipStream_t)stream;
+  Carver k(workspace);
+  bf16_t* sinu = k.take<bf16_t>((size_t)n_t * c.freq_dim);
+  bf16_t* t1 = k.take<bf16_t>((size_t)n_t * d);
+  bf16_t* se = k.take<bf16_t>((size_t)n_t * d);
+  // the launches of FwdCall::run() for its own timesteps
+  MMPL_HIP_TRY(mmpl_launch_sinusoid(t_dev, sinu, n_t, c.freq_dim, s), "sinusoid");
+  TRY(gemm(sinu, c.freq_dim, h->G(G_TE0_W), c.freq_dim, h->G(G_TE0_B), t1, d, n_t, d, c.freq_dim, EPI_BIAS_SILU, nullptr, 0, nullptr, 0, 1, s));
+  TRY(gemm(t1, d, h->G(G_TE2_W), d, h->G(G_TE2_B), (bf16_t*)e_out, d, n_t, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
+  if (e0_out) {
+    MMPL_HIP_TRY(mmpl_launch_silu((const bf16_t*)e_out, se, (size_t)n_t * d, s), "silu");
+    TRY(gemm(se, d, h->G(G_TP_W), d, h->G(G_TP_B), (bf16_t*)e0_out, 6 * d, n_t, 6 * d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s));
+  }
+  return 0;
 }
 
 int mmpl_dit_share_check_failures(MmplDit* h, long long* count, mmpl_stream_t stream) {

@@ -278,6 +278,10 @@ hipError_t mmpl_launch_share_check_compare(unsigned long long* chk, hipStream_t 
 hipError_t mmpl_launch_rows_equal_last(const bf16_t* x, int ld, int rows, int d, int* flags, hipStream_t s);
 hipError_t mmpl_launch_sinusoid(const float* t, bf16_t* out, int F, int freq_dim, hipStream_t s);
 hipError_t mmpl_launch_silu(const bf16_t* x, bf16_t* y, size_t n, hipStream_t s);
+// step caching (step_cache.hip).  r = bf16(float(xl) - float(x0)), n elements: 16 bytes per lane where all three are 16-byte aligned
+hipError_t mmpl_launch_residual_sub(const bf16_t* xl, const bf16_t* x0, bf16_t* r, size_t n, hipStream_t s);
+// out[i] = sum_c |x[i+1,c] - x[i,c]| / sum_c |x[i,c]| for i < rows - 1 (fp32, fixed order: mmpl_rel_l1_rows in the public header)
+hipError_t mmpl_launch_rel_l1_rows(const bf16_t* x, int ld, int rows, int d, float* out, hipStream_t s);
 
 // The samplers (sampler.hip): CFG combine + one UniPC / DPM-Solver++ step on x / m0 / m1 / last of storage type T (bf16_t or float)
 // with bf16 flows; the formulas are in sampler.hip's header and at the entries in include/mmpl_hip.h.  Defined for the four pairs

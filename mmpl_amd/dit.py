@@ -54,6 +54,10 @@ def slot_tensors(lib, g, num_layers: int, dim: int, in_dim: int) -> List[torch.T
     return [slot(n) for n in weight_slot_names(lib, 0)] + [slot(n, f"blocks.{i}.") for i in range(num_layers) for n in per_layer]
 
 
+# DitEngine.forward(cache_mode=...): the step-cache modes of mmpl_dit_forward_*_cached (include/mmpl_hip.h)
+CACHE_OFF, CACHE_RECORD, CACHE_REUSE = 0, 1, 2
+
+
 class CrossKV(tuple):
     """(cross_k, cross_v) of one prompt, each [num_layers, text_len, dim], plus `rows`: rows `rows .. text_len-1` of every layer are
     copies of row `rows` (the zero-padded tail of the text context after the text embedding; `text_len` = no repeated tail).
@@ -279,7 +283,8 @@ class DitEngine:
                 cross_v: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                 cross_rows: Optional[int] = None, share_out: Optional[torch.Tensor] = None,
                 share_in: Optional[torch.Tensor] = None, attn_history: Optional[torch.Tensor] = None,
-                frame_base: Optional[torch.Tensor] = None) -> torch.Tensor:
+                frame_base: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF,
+                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x: [nF, in_dim, lat_h, lat_w] bf16 (i2v: x and y concatenated on the channel axis); t: [nF] float32 (device).
         Returns the flow prediction [nF, 16, lat_h, lat_w].
         `cross_rows`: the `CrossKV.rows` that belongs to the CONTENTS of cross_k / cross_v (rows cross_rows .. text_len-1 repeat one
@@ -294,7 +299,11 @@ class DitEngine:
         one on a different stream (cond / uncond); default: the engine's own.
         `frame_base`: an int32 device scalar; `frame_ids` are then relative to it (RoPE position = frame_ids[i] + its value WHEN THE
         KERNELS RUN, clamped to the tables' 0..1023): a forward captured into a hipGraph is replayed at another position in time by
-        writing the scalar in stream order before the replay (mmpl_dit_forward_at).  None = absolute frame_ids."""
+        writing the scalar in stream order before the replay (mmpl_dit_forward_at).  None = absolute frame_ids.
+        `cache_mode` / `residual` (`new_step_cache(nF)`): step caching, mmpl_dit_forward_at_cached -- CACHE_RECORD: this forward
+        plus x after the last block minus x after the patch embedding left in `residual`; CACHE_REUSE: the patch embedding plus
+        `residual`, then the head: no block runs, no K / V is written, the caches and cross K / V may be None.  CACHE_OFF (the
+        default) is the uncached entry."""
         nF = x.shape[0]
         assert x.is_contiguous() and x.dtype == torch.bfloat16 and x.shape[1:] == (self.in_dim, self.lat_h, self.lat_w)
         assert t.dtype == torch.float32 and t.numel() == nF and t.is_cuda
@@ -306,12 +315,16 @@ class DitEngine:
         ws = self.workspace(nF) if workspace is None else workspace
         n_slots = k_cache.shape[1] // self.S
         ia = lambda v: (C.c_int * len(v))(*[int(i) for i in v])
+        self._check_residual(cache_mode, residual, nF, x.device)
         with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
-            _lib.check(self._lib.mmpl_dit_forward_at(
-                self._h, _lib.ptr(x), _lib.ptr(t), nF, ia(frame_ids), ia(write_slots), ia(visible_slots), len(visible_slots),
-                _lib.ptr(k_cache), _lib.ptr(v_cache), n_slots, _lib.ptr(cross_k), _lib.ptr(cross_v),
-                self.text_len if cross_rows is None else int(cross_rows), _lib.ptr(share_out), _lib.ptr(share_in),
-                _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base), _lib.stream_ptr()), "mmpl_dit_forward")
+            args = (self._h, _lib.ptr(x), _lib.ptr(t), nF, ia(frame_ids), ia(write_slots), ia(visible_slots), len(visible_slots),
+                    _lib.ptr(k_cache), _lib.ptr(v_cache), n_slots, _lib.ptr(cross_k), _lib.ptr(cross_v),
+                    self.text_len if cross_rows is None else int(cross_rows), _lib.ptr(share_out), _lib.ptr(share_in),
+                    _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.ptr(frame_base), _lib.stream_ptr())
+            if cache_mode == CACHE_OFF:
+                _lib.check(self._lib.mmpl_dit_forward_at(*args), "mmpl_dit_forward")
+            else:
+                _lib.check(self._lib.mmpl_dit_forward_at_cached(*args, int(cache_mode), _lib.ptr(residual)), "mmpl_dit_forward_at_cached")
         return out
 
     def forward_groups(self, x: torch.Tensor, t: torch.Tensor, n_groups: int, frame_ids: Sequence[int], write_slots: Sequence[int],
@@ -360,6 +373,43 @@ class DitEngine:
             out = torch.empty(nF, 16, self.lat_h, self.lat_w, dtype=torch.bfloat16, device=x.device)
         return out
 
+    # ------------------------------------------------------------------ step caching
+    def new_step_cache(self, n_frames: int) -> torch.Tensor:
+        """[n_frames * S, dim] bf16 for `forward(..., cache_mode=, residual=)` / `forward_full`: what a CACHE_RECORD forward leaves and
+        a CACHE_REUSE forward adds (mmpl_dit_step_cache_bytes).  One per (CFG branch, stage shape)."""
+        n = self._lib.mmpl_dit_step_cache_bytes(self._h, n_frames)
+        return torch.empty(n // 2, dtype=torch.bfloat16, device=self.device)
+
+    def _check_residual(self, cache_mode: int, residual: Optional[torch.Tensor], nF: int, device) -> None:
+        if cache_mode != CACHE_OFF and residual is not None:
+            assert residual.dtype == torch.bfloat16 and residual.is_contiguous() and residual.device == device
+            assert residual.numel() >= nF * self.S * self.dim, (residual.numel(), nF * self.S * self.dim)
+
+    def time_embed(self, t: torch.Tensor, want_e0: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """t: [n] float32 on the device -> (e [n, dim], e0 [n, 6 * dim] or None) bf16: the timestep embedding and its projection as a
+        forward at timestep t[i] computes them (mmpl_dit_time_embed: the same launches, row for row)."""
+        assert t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous() and t.device == self.device
+        n = t.numel()
+        e = torch.empty(n, self.dim, dtype=torch.bfloat16, device=self.device)
+        e0 = torch.empty(n, 6 * self.dim, dtype=torch.bfloat16, device=self.device) if want_e0 else None
+        nbytes = self._lib.mmpl_dit_time_embed_workspace_bytes(self._h, n)
+        if nbytes == 0:
+            raise ValueError(f"DitEngine.time_embed: {n} timesteps is outside 1 .. 4096")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mmpl_dit_time_embed(self._h, _lib.ptr(t), n, _lib.ptr(e), _lib.ptr(e0), _lib.ptr(ws), ws.numel(),
+                                                     _lib.stream_ptr()), "mmpl_dit_time_embed")
+        return e, e0
+
+    def rel_l1_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """x: [rows >= 2, d] bf16 (row stride x.stride(0)) -> float32 [rows - 1]: sum |x[i+1] - x[i]| / sum |x[i]| (mmpl_rel_l1_rows)."""
+        assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= 2 and x.is_cuda
+        out = torch.empty(x.shape[0] - 1, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(self._lib.mmpl_rel_l1_rows(_lib.ptr(x), x.stride(0), x.shape[0], x.shape[1], _lib.ptr(out), _lib.stream_ptr()),
+                       "mmpl_rel_l1_rows")
+        return out
+
     # ------------------------------------------------------------------ whole-clip (bidirectional) forward
     def full_workspace(self, n_frames: int, second: bool = False) -> torch.Tensor:
         """Scratch of `forward_full` at `n_frames` frames: one buffer per frame count, allocated on first use (outside any capture).
@@ -376,14 +426,16 @@ class DitEngine:
     def forward_full(self, x: torch.Tensor, t: torch.Tensor, cross_k: torch.Tensor, cross_v: torch.Tensor,
                      cross_rows: Optional[int] = None, out: Optional[torch.Tensor] = None, share_out: Optional[torch.Tensor] = None,
                      share_in: Optional[torch.Tensor] = None, attn_history: Optional[torch.Tensor] = None,
-                     workspace: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     workspace: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF,
+                     residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The non-causal forward over a whole clip (mmpl_dit_forward_full): x [nF, 16, lat_h, lat_w] bf16 with nF up to 24
         whatever `max_frames`; t: ONE float32 on the device, the clip's timestep.  Frame i is rotated at temporal position i, every
         frame attends to every frame, and there is no KV cache: the layer's K / V live in the workspace.  Returns the flow
         prediction [nF, 16, lat_h, lat_w].  `cross_rows`, `share_out`, `share_in`, `attn_history` as in `forward`; `workspace`: a
         private scratch (`full_workspace(nF, second=True)`) for a forward that runs concurrently with another one.
         `y`: the i2v model type's conditioning video, [nF, in_dim - 16, lat_h, lat_w] bf16, frame-major like x and read next to it
-        (mmpl_dit_forward_full_i2v: x and y are never concatenated); required there -- with `set_image_kv` done --, None for t2v."""
+        (mmpl_dit_forward_full_i2v: x and y are never concatenated); required there -- with `set_image_kv` done --, None for t2v.
+        `cache_mode` / `residual`: step caching as in `forward` (mmpl_dit_forward_full_cached)."""
         nF = x.shape[0]
         i2v = self.model_type == "i2v"
         if i2v and y is None:
@@ -401,8 +453,12 @@ class DitEngine:
         assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.shape == (nF, 16, self.lat_h, self.lat_w)
         tail = (nF, _lib.ptr(cross_k), _lib.ptr(cross_v), self.text_len if cross_rows is None else int(cross_rows), _lib.ptr(share_out),
                 _lib.ptr(share_in), _lib.ptr(attn_history), _lib.ptr(out), _lib.ptr(ws), ws.numel())
+        self._check_residual(cache_mode, residual, nF, x.device)
         with torch.cuda.device(self.device):          # the stream handed to the library is this device's current stream
-            if i2v:
+            if cache_mode != CACHE_OFF:
+                _lib.check(self._lib.mmpl_dit_forward_full_cached(self._h, _lib.ptr(x), _lib.ptr(t), *tail, _lib.stream_ptr(), _lib.ptr(y),
+                                                                  int(cache_mode), _lib.ptr(residual)), "mmpl_dit_forward_full_cached")
+            elif i2v:
                 _lib.check(self._lib.mmpl_dit_forward_full_i2v(self._h, _lib.ptr(x), _lib.ptr(y), _lib.ptr(t), *tail, _lib.stream_ptr()),
                            "mmpl_dit_forward_full_i2v")
             else:
@@ -413,7 +469,8 @@ class DitEngine:
     # ------------------------------------------------------------------ hipGraph
     def capture(self, x: torch.Tensor, t: torch.Tensor, frame_ids, write_slots, visible_slots, k_cache, v_cache, cross_k, cross_v,
                 out: torch.Tensor, pre=None, cross_rows: Optional[int] = None,
-                attn_history: Optional[torch.Tensor] = None) -> "torch.cuda.CUDAGraph":
+                attn_history: Optional[torch.Tensor] = None, cache_mode: int = CACHE_OFF,
+                residual: Optional[torch.Tensor] = None) -> "torch.cuda.CUDAGraph":
         """Capture one forward (fixed stage shape, slot table and buffers) into a hipGraph.  The forward is a pure launch
         sequence -- no host sync, no allocation -- so replaying it costs one graph launch instead of ~13 launches per
         layer.  `x`, `t`, `out` and the caches are captured BY ADDRESS: update their contents in place between replays
@@ -423,7 +480,8 @@ class DitEngine:
         The first capture of a stage shape on this engine runs the forward once eagerly, ahead of the capture (see below), on the
         caller's own buffers: it writes `out` and the caches' write slots, and it runs with the caller's `attn_history`, so it
         ADVANCES that history by one forward before any replay does.  A caller whose bits must not depend on whether the shape was
-        warm zeroes the history after capture() (the pipeline does, at every stage boundary)."""
+        warm zeroes the history after capture() (the pipeline does, at every stage boundary).
+        `cache_mode` / `residual`: the captured forward's step-cache mode and buffer (`forward`)."""
         self.workspace(x.shape[0])                      # allocate outside the capture
         if x.shape[0] not in self._warm:                # one eager call per (engine, stage shape): the kernels a shape selects (pipelined
             # LayerNorm from 16 384 rows, the v8 GEMM variants, attn_cross_kernel<NT>, the split-KV tail) set their dynamic-LDS
@@ -431,7 +489,7 @@ class DitEngine:
             if pre is not None:
                 pre()
             self.forward(x, t, frame_ids, write_slots, visible_slots, k_cache, v_cache, cross_k, cross_v, out=out, cross_rows=cross_rows,
-                         attn_history=attn_history)
+                         attn_history=attn_history, cache_mode=cache_mode, residual=residual)
             self._warm.add(x.shape[0])
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
@@ -439,6 +497,6 @@ class DitEngine:
             if pre is not None:
                 pre()
             self.forward(x, t, frame_ids, write_slots, visible_slots, k_cache, v_cache, cross_k, cross_v, out=out, cross_rows=cross_rows,
-                         attn_history=attn_history)
+                         attn_history=attn_history, cache_mode=cache_mode, residual=residual)
         return g
 

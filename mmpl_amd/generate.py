@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from .pipeline import BidirectionalDiffusionInferencePipeline
+from .step_cache import StepCachePolicy
 
 VAE_STRIDE = (4, 8, 8)            # wan/configs/shared_config.py / wan_*_14B.py: the same for every released model
 PATCH_SIZE = (1, 2, 2)
@@ -145,12 +146,20 @@ class _WanGenerate:
             raise ValueError(f"noise: float32 {list(shape)} (upstream's layout, channels first); got {noise.dtype} {list(noise.shape)}")
         return noise.to(self.device).permute(1, 0, 2, 3).unsqueeze(0).contiguous()
 
-    def _generate(self, input_prompt, noise, shift, sample_solver, sampling_steps, guide_scale, n_prompt, image_condition=None):
+    def _generate(self, input_prompt, noise, shift, sample_solver, sampling_steps, guide_scale, n_prompt, image_condition=None,
+                  teacache_thresh=0.0, teacache_coefficients=None, use_ret_steps=False):
         if sample_solver not in ("unipc", "dpm++"):
             raise NotImplementedError("Unsupported solver.")
         if int(sampling_steps) < 1:
             raise ValueError(f"sampling_steps {sampling_steps}: at least 1")
         p = self.pipeline
+        # TeaCache4Wan2.1's arguments: 0 = every step computed -- the sampler as it is (no policy, nothing allocated)
+        p.step_cache = None
+        if teacache_thresh and float(teacache_thresh) > 0:
+            kw = {} if teacache_coefficients is None else {"coefficients": tuple(teacache_coefficients)}
+            if use_ret_steps:                                # upstream: the first 5 steps computed, no forced last step, e0 the indicator
+                kw.update(ret_steps=5, cutoff=int(sampling_steps), indicator="e0")
+            p.step_cache = StepCachePolicy(float(teacache_thresh), **kw)
         p.shift, p.sampling_steps, p.sample_solver = float(shift), int(sampling_steps), sample_solver
         p.args.guidance_scale = float(guide_scale)
         p.args.negative_prompt = self.sample_neg_prompt if n_prompt == "" else n_prompt
@@ -170,11 +179,15 @@ class WanT2V(_WanGenerate):
 
     def generate(self, input_prompt, size=(1280, 720), frame_num=81, shift=5.0, sample_solver='unipc', sampling_steps=50,
                  guide_scale=5.0, n_prompt="", seed=-1, offload_model=True, *, noise: Optional[torch.Tensor] = None,
-                 return_latents: bool = False):
-        """-> float32 [3, frame_num, H, W] in [-1, 1] (with `return_latents` also the float32 latents [1, F, 16, h, w])."""
+                 return_latents: bool = False, teacache_thresh: float = 0.0, teacache_coefficients=None, use_ret_steps: bool = False):
+        """-> float32 [3, frame_num, H, W] in [-1, 1] (with `return_latents` also the float32 latents [1, F, 16, h, w]).
+        `teacache_thresh` > 0: step caching (mmpl_amd/step_cache.py) with the polynomial `teacache_coefficients` (highest power
+        first; None = identity); `use_ret_steps`: the first 5 steps computed, no forced last step, the indicator e0."""
         n = latent_frames(frame_num)
         self._check_geometry(*t2v_latent_hw(size), asked=f"size={tuple(size)}")
-        video, latents = self._generate(input_prompt, self._noise(noise, n, seed), shift, sample_solver, sampling_steps, guide_scale, n_prompt)
+        video, latents = self._generate(input_prompt, self._noise(noise, n, seed), shift, sample_solver, sampling_steps, guide_scale, n_prompt,
+                                        teacache_thresh=teacache_thresh, teacache_coefficients=teacache_coefficients,
+                                        use_ret_steps=use_ret_steps)
         return (video, latents) if return_latents else video
 
 
@@ -191,8 +204,9 @@ class WanI2V(_WanGenerate):
 
     def generate(self, input_prompt, img, max_area=720 * 1280, frame_num=81, shift=5.0, sample_solver='unipc', sampling_steps=40,
                  guide_scale=5.0, n_prompt="", seed=-1, offload_model=True, *, noise: Optional[torch.Tensor] = None,
-                 return_latents: bool = False):
-        """-> float32 [3, frame_num, H, W] in [-1, 1] (with `return_latents` also the float32 latents [1, F, 16, h, w])."""
+                 return_latents: bool = False, teacache_thresh: float = 0.0, teacache_coefficients=None, use_ret_steps: bool = False):
+        """-> float32 [3, frame_num, H, W] in [-1, 1] (with `return_latents` also the float32 latents [1, F, 16, h, w]).
+        `teacache_thresh`, `teacache_coefficients`, `use_ret_steps`: step caching, as in `WanT2V.generate`."""
         from .i2v_condition import build_image_condition
         n = latent_frames(frame_num)
         image = _image_tensor(img)
@@ -202,5 +216,6 @@ class WanI2V(_WanGenerate):
             image = torch.nn.functional.interpolate(image[None], size=(8 * lat_h, 8 * lat_w), mode="bicubic")[0]
         condition = build_image_condition(self.vae, self.clip, image.to(self.device), n)
         video, latents = self._generate(input_prompt, self._noise(noise, n, seed), shift, sample_solver, sampling_steps, guide_scale, n_prompt,
-                                        image_condition=condition)
+                                        image_condition=condition, teacache_thresh=teacache_thresh,
+                                        teacache_coefficients=teacache_coefficients, use_ret_steps=use_ret_steps)
         return (video, latents) if return_latents else video

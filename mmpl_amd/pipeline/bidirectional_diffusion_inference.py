@@ -17,7 +17,13 @@ is not read --, ``args``) and the same semantics.  What changed underneath:
   * block 0's self-attention is the same computation in both CFG branches, so the uncond forward takes x after it from the cond
     forward (share_out / share_in) where the two run back to back; where ``concurrent_cfg_pays`` says so they run as parallel
     branches of the graph instead (second stream, private workspace);
-  * the frame count is ``noise.shape[1]`` where the reference writes the literal 21; batch size 1.
+  * the frame count is ``noise.shape[1]`` where the reference writes the literal 21; batch size 1;
+  * ``step_cache`` (a ``mmpl_amd.step_cache.StepCachePolicy``; None = off: nothing of this exists) runs fewer forwards (TeaCache):
+    the steps the policy skips reuse the residual the last computed step left and run only the head.  The indicator is the timestep
+    embedding, so the schedule is computed once per step shape before sampling (one ``time_embed`` over the timestep table, one
+    ``rel_l1_rows``, one read-back).  Each step kind is its own graph, captured on first use -- two RECORD forwards + the solver
+    kernel, two REUSE forwards + the same solver kernel --, and the host replays the one the schedule names.
+    ``computed_steps`` / ``skipped_steps`` count the last call's.
 
 Over a ``model_type='i2v'`` generator (the released Wan2.1-I2V-14B-480P / -720P weights) this is upstream ``WanI2V.generate``'s
 forward and conditioning (wan/image2video.py): ``inference(..., image_condition={"clip_fea": [257, 1280], "y": [20, F, h, w]})`` from
@@ -36,6 +42,8 @@ from typing import Dict, List, Optional
 
 import torch
 
+from ..dit import CACHE_OFF, CACHE_RECORD, CACHE_REUSE
+from ..step_cache import StepCachePolicy, step_schedule
 from ._common import (GeneratorPipeline, cfg_concurrent, cfg_step, cfg_step_buffers, decode_video, eager_then_capture,
                       make_sample_scheduler)
 
@@ -63,6 +71,9 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
         self.concurrent_cfg: Optional[bool] = None    # None = where concurrent_cfg_pays says so; True / False = always / never
         self.share_block0 = True          # sequential branches: the uncond forward takes block 0's self-attention from the cond one
         self.graph_captures = 0           # hipGraphs constructed so far (tests: none after the first call)
+        self.step_cache: Optional[StepCachePolicy] = None    # TeaCache: which steps reuse the last computed step's residual (None = off)
+        self.computed_steps = 0           # the last call's steps that ran the blocks / that reused a residual
+        self.skipped_steps = 0
         self._steps: Dict[tuple, dict] = {}     # (frames, solver, steps, guidance, concurrent, share, latent dtype, shift) -> static buffers, scheduler, graph
         self._stores = (self._steps,)
         self._side_stream = None
@@ -84,6 +95,8 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
             raise ValueError(f"latent_dtype {self.latent_dtype}: torch.bfloat16 (the reference pipeline's chain) or torch.float32 (upstream's)")
         key = (F, self.sample_solver, int(self.sampling_steps), float(self.args.guidance_scale), concurrent,
                bool(self.share_block0 and not concurrent), self.latent_dtype, float(self.shift))
+        if self.step_cache is not None:                                   # its own buffers, schedule and graphs; off: the key as it was
+            key += (self.step_cache.key(),)
         st = self._steps.get(key)
         if st is None:
             g = self.geometry
@@ -101,15 +114,22 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
                       y=torch.empty((F, engine.in_dim - 16, g.lat_h, g.lat_w), dtype=torch.bfloat16, device=dev) if self.i2v else None)
             engine.full_workspace(F)                                      # allocations and the stream: outside any capture
             st["share"], st["ws2"] = cfg_step_buffers(self, engine, F, concurrent, lambda n: engine.full_workspace(n, second=True), dev)
+            if self.step_cache is not None:
+                # per step True = compute; one residual per CFG branch; one graph per step kind, captured on first use
+                st["schedule"] = step_schedule(engine, self.step_cache, sched._t_table)
+                st["residual"] = (engine.new_step_cache(F), engine.new_step_cache(F))
+                st["graphs"] = {}
             self._steps[key] = st
         return st
 
-    def _step(self, st: dict) -> None:
-        """One denoise step's launches (bidirectional_diffusion_inference.py:62-76): eager, or recorded into the step graph."""
+    def _step(self, st: dict, cache_mode: int = CACHE_OFF) -> None:
+        """One denoise step's launches (bidirectional_diffusion_inference.py:62-76): eager, or recorded into the step graph.
+        `cache_mode`: CACHE_RECORD / CACHE_REUSE for a computed / a reused step under `step_cache`."""
         caches = (self.crossattn_cache_pos, self.crossattn_cache_neg)
         kw = {} if st["y"] is None else {"y": st["y"]}                    # i2v: both branches see the image (image2video.py arg_null)
         x_in = st["latents"] if st["latents_bf16"] is None else st["latents_bf16"]
-        cfg_step(lambda bi, out, **k: self.generator.flow_full(x_in, st["t"], caches[bi], out=out, **k, **kw),
+        cache = (lambda bi: {}) if cache_mode == CACHE_OFF else (lambda bi: {"cache_mode": cache_mode, "residual": st["residual"][bi]})
+        cfg_step(lambda bi, out, **k: self.generator.flow_full(x_in, st["t"], caches[bi], out=out, **k, **kw, **cache(bi)),
                  st["sched"], st["flow"], st["latents"], st["t"], self.device, self._side_stream if st["concurrent"] else None,
                  st["share"], st["ws2"], latents_bf16=st["latents_bf16"])
 
@@ -160,7 +180,18 @@ class BidirectionalDiffusionInferencePipeline(GeneratorPipeline):
                 self.generator.set_image(image_condition["clip_fea"])
             st["sched"].reset_step_table(st["t"])
             n = st["n"]
-            if st["graph"] is not None:
+            self.computed_steps, self.skipped_steps = n, 0
+            if "schedule" in st:
+                self.computed_steps = sum(st["schedule"])
+                self.skipped_steps = n - self.computed_steps
+                for compute in st["schedule"]:
+                    g = st["graphs"].get(compute)
+                    if g is not None:
+                        g.replay()
+                    else:                                                 # first use of this step kind (without graphs: every use)
+                        mode = CACHE_RECORD if compute else CACHE_REUSE
+                        st["graphs"][compute] = eager_then_capture(self, lambda: self._step(st, mode))
+            elif st["graph"] is not None:
                 for _ in range(n):
                     st["graph"].replay()
             else:                                                         # first use: step 1 eagerly, then into the step's graph

@@ -16,7 +16,11 @@ underneath, MI355X-first:
   * the reference's ``device_cond`` / ``device_uncond`` seam (two GPUs per pipeline, :42-43,346-367) is ``self.cfg_pair``
     in the one-process-per-GPU world: the two ranks of a ``CfgPair`` each own ONE branch (cond or uncond: its KV cache,
     cross-attention cache and forward), exchange the two flow predictions per step (one 2-rank all-gather of <= 3.2 MB)
-    and both apply the fused CFG + UniPC update, so their latents stay bit-identical without a second exchange.
+    and both apply the fused CFG + UniPC update, so their latents stay bit-identical without a second exchange;
+  * ``step_cache`` (a ``mmpl_amd.step_cache.StepCachePolicy``; None = off) runs fewer forwards (TeaCache) on the single-process
+    path: the steps the policy skips reuse the residual the last computed step of their (branch, stage shape) left and run only
+    the head.  All stages use the same timesteps, so they share one schedule, known before sampling.  A skipped step writes no
+    K / V; the t = 0 refresh after the stage is always a plain forward and rewrites the stage's slots with clean context.
 """
 from __future__ import annotations
 
@@ -24,7 +28,9 @@ from typing import Callable, List, Optional
 
 import torch
 
+from ..dit import CACHE_OFF, CACHE_RECORD, CACHE_REUSE
 from ..geometry import Geometry
+from ..step_cache import StepCachePolicy, step_schedule
 from ..stage_plan import StagePlan
 from ..wan_wrapper import WanFPSWrapper
 from ._common import PipelineBase, cfg_concurrent, cfg_step, cfg_step_buffers, decode_video, make_sample_scheduler
@@ -86,6 +92,13 @@ class CausalFPSInferencePipeline(PipelineBase):
         # softmax either way; for such blocks the bits then depend on the steps before (include/mmpl_hip.h).  False = stateless.
         self.attn_history = True
         self.cfg_pair = None              # mmpl_amd.handoff.CfgPair: this rank runs only the cond (role 0) / uncond (role 1) branch
+        # TeaCache (mmpl_amd/step_cache.py): which denoise steps reuse the last computed step's residual; None = off.  Single process only.
+        self.step_cache: Optional[StepCachePolicy] = None
+        self.computed_steps = 0           # the last call's denoise steps (over all stages) that ran the blocks / that reused a residual
+        self.skipped_steps = 0
+        self._residuals = {}              # (branch, frames of the stage) -> the residual buffer
+        self._schedules = {}              # (policy, solver, steps, shift) -> per step, True = compute
+        self._reuse_warm = set()          # stage shapes whose REUSE forward ran eagerly once (ahead of its first capture)
 
         # ---- "add new noise on previous frames" schedule (casual_fps_inference.py:93-108); the randint keeps the
         # reference's RNG consumption order; the resulting timestep is >= 1000, i.e. pure noise
@@ -95,12 +108,25 @@ class CausalFPSInferencePipeline(PipelineBase):
         self.ddmp_timestep = self.ddpm_scheduler.timesteps.to(self.ddpm_index.device)[self.ddpm_index] + 1000
 
     # ------------------------------------------------------------------------------------------------------------
-    def _forward(self, latents, cond, timestep, kv, cross, frames, out=None, workspace=None, share_out=None, share_in=None):
+    def _forward(self, latents, cond, timestep, kv, cross, frames, out=None, workspace=None, share_out=None, share_in=None,
+                 cache_mode=CACHE_OFF, residual=None):
         S = self.frame_seq_length
         starts = [f * S for f in frames]
         return self.generator_cond(noisy_image_or_video=latents, conditional_dict=cond, timestep=timestep, kv_cache=kv,
                                    crossattn_cache=cross, current_start=starts, cache_start=starts, out=out, workspace=workspace,
-                                   share_out=share_out, share_in=share_in)[0]
+                                   share_out=share_out, share_in=share_in, cache_mode=cache_mode, residual=residual)[0]
+
+    def _step_schedule(self, sample_scheduler) -> List[bool]:
+        """The policy's schedule over the sampler's timesteps (every stage has the same): computed once, outside any capture."""
+        key = (self.step_cache.key(), self.sample_solver, int(self.sampling_steps), float(self.shift))
+        if key not in self._schedules:
+            self._schedules[key] = step_schedule(self.generator_cond.engine, self.step_cache, [float(t) for t in sample_scheduler.timesteps])
+        return self._schedules[key]
+
+    def _residual(self, branch: int, n_frames: int) -> torch.Tensor:
+        if (branch, n_frames) not in self._residuals:
+            self._residuals[(branch, n_frames)] = self.generator_cond.engine.new_step_cache(n_frames)
+        return self._residuals[(branch, n_frames)]
 
     def _branches(self, cond, uncond):
         """[(conditional_dict, kv_cache, crossattn_cache, index into the flow pair)] this rank computes."""
@@ -124,6 +150,11 @@ class CausalFPSInferencePipeline(PipelineBase):
         assert batch_size == 1 and num_frames == self.geometry.frames_per_chunk
         dev = noise.device
         pair = self.cfg_pair
+        policy = self.step_cache
+        if policy is not None and pair is not None:
+            raise ValueError("CausalFPSInferencePipeline: step_cache is single-process only; it is not available with a CfgPair "
+                             "(--cfg_split / more than one rank)")
+        self.computed_steps = self.skipped_steps = 0
         with torch.no_grad():
             if pair is not None:                                              # same noise on both ranks of the pair
                 noise = pair.broadcast(noise.contiguous())
@@ -217,11 +248,35 @@ class CausalFPSInferencePipeline(PipelineBase):
                 outs = [flow[i] for _, _, _, i in branches] if pair is None else [torch.empty_like(latents)]
                 timestep = torch.empty([1, len(frames)], device=dev, dtype=torch.float32)
                 graphs, step_graph = None, None
+                # step caching: per step True = compute (RECORD) / False = reuse; the kinds this stage needs; each branch's arguments
+                schedule = self._step_schedule(sample_scheduler) if policy is not None else None
+                kinds = sorted(set(schedule), reverse=True) if schedule is not None else []
+                mode_of = {True: CACHE_RECORD, False: CACHE_REUSE}
+                cache_kw = lambda compute, bi: {"cache_mode": mode_of[compute], "residual": self._residual(branches[bi][3], len(frames))}
+                kind_graphs, kind_step_graphs = {}, {}
+                if schedule is None:
+                    self.computed_steps += len(sample_scheduler.timesteps)
+                else:
+                    self.computed_steps += sum(schedule)
+                    self.skipped_steps += len(schedule) - sum(schedule)
+                    for bi in range(len(branches)):
+                        cache_kw(True, bi)                                    # allocate outside any capture
+                    if False in kinds and self.use_graphs and len(frames) not in self._reuse_warm:
+                        # once per stage shape, ahead of its first capture: the kernels a shape selects settle on first launch
+                        # (DitEngine.capture).  A REUSE forward writes `out` and the workspace only.
+                        timestep.fill_(float(sample_scheduler.timesteps[0]))
+                        for bi, ((d, kv, cross, _), o) in enumerate(zip(branches, outs)):
+                            self._forward(latents, d, timestep, kv, cross, frames, o, **cache_kw(False, bi))
+                        self._reuse_warm.add(len(frames))
                 if self.use_graphs:
                     starts = [f * S for f in frames]
                     timestep.fill_(float(sample_scheduler.timesteps[0]))
                     graphs = [self.generator_cond.capture(latents, d, timestep, kv, cross, starts, o)
                               for (d, kv, cross, _), o in zip(branches, outs)]
+                    if schedule is not None and not self.step_graphs:         # one forward graph per (step kind, branch)
+                        for compute in kinds:
+                            kind_graphs[compute] = [self.generator_cond.capture(latents, d, timestep, kv, cross, starts, o, **cache_kw(compute, bi))
+                                                    for bi, ((d, kv, cross, _), o) in enumerate(zip(branches, outs))]
                     if pair is None and self.step_graphs:
                         # ONE hipGraph per denoise step: both forwards + the fused CFG / UniPC update, whose scalars and
                         # the next timestep live in device tables -- 50 replays with no host work in between
@@ -239,25 +294,40 @@ class CausalFPSInferencePipeline(PipelineBase):
                             d, kv, cross, _ = branches[bi]
                             self._forward(latents, d, timestep, kv, cross, frames, out, **kw)
 
-                        step_graph = torch.cuda.CUDAGraph()                   # (no eager run of its own: the forward graphs above had theirs)
-                        with torch.cuda.graph(step_graph):
-                            cfg_step(forward, sample_scheduler, flow, latents, timestep, dev, self._side_stream if concurrent else None,
-                                     share, ws2)
+                        def capture_step(fwd):
+                            g = torch.cuda.CUDAGraph()                        # (no eager run of its own: the forward graphs above had theirs)
+                            with torch.cuda.graph(g):
+                                cfg_step(fwd, sample_scheduler, flow, latents, timestep, dev, self._side_stream if concurrent else None,
+                                         share, ws2)
+                            return g
+
+                        if schedule is None:
+                            step_graph = capture_step(forward)
+                        for compute in kinds:                                 # a computed step's graph, a reused step's graph
+                            kind_step_graphs[compute] = capture_step(lambda bi, out, c=compute, **kw: forward(bi, out, **kw, **cache_kw(c, bi)))
                 for kv in live_kv:                                            # a new stage: other shapes, other blocks
                     kv.reset_attn_history()
                 if step_graph is not None:
                     timestep.fill_(float(sample_scheduler.timesteps[0]))
                     for _ in sample_scheduler.timesteps:
                         step_graph.replay()
+                elif kind_step_graphs:
+                    timestep.fill_(float(sample_scheduler.timesteps[0]))
+                    for compute in schedule:
+                        kind_step_graphs[compute].replay()
                 else:
-                    for t in sample_scheduler.timesteps:
+                    for i, t in enumerate(sample_scheduler.timesteps):
                         timestep.fill_(float(t))
-                        if graphs is not None:
+                        if schedule is not None and graphs is not None:
+                            for g in kind_graphs[schedule[i]]:
+                                g.replay()
+                        elif graphs is not None:
                             for g in graphs:
                                 g.replay()
                         else:
-                            for (d, kv, cross, _), o in zip(branches, outs):
-                                self._forward(latents, d, timestep, kv, cross, frames, o)
+                            for bi, ((d, kv, cross, _), o) in enumerate(zip(branches, outs)):
+                                self._forward(latents, d, timestep, kv, cross, frames, o,
+                                              **({} if schedule is None else cache_kw(schedule[i], bi)))
                         if pair is not None:
                             pair.exchange(outs[0], flow)
                         # flow = uncond + g (cond - uncond); latents = scheduler.step(flow)  -- one fused kernel (:366-374)

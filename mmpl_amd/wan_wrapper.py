@@ -245,9 +245,10 @@ class WanFPSWrapper(_GeneratorBase):
         return x, frames, [slot_of(o // S) for o in vis], self._image_stream(frames, conditional_dict, clip_fea, y)
 
     def capture(self, noisy_image_or_video, conditional_dict, timestep, kv_cache, crossattn_cache, current_start, out,
-                clip_fea=None, y=None):
+                clip_fea=None, y=None, cache_mode: int = 0, residual: Optional[torch.Tensor] = None):
         """hipGraph of this exact forward (fixed buffers / stage shape); returns the graph, replay() re-runs it on the
-        current contents of `noisy_image_or_video`, `timestep` and the caches."""
+        current contents of `noisy_image_or_video`, `timestep` and the caches.  `cache_mode` / `residual`: step caching
+        (DitEngine.forward)."""
         assert noisy_image_or_video.is_contiguous() and noisy_image_or_video.dtype == torch.bfloat16
         assert timestep.dtype == torch.float32 and timestep.is_contiguous() and out.is_contiguous()
         x, frames, visible, ys = self._stage(noisy_image_or_video[0], conditional_dict, kv_cache, crossattn_cache, current_start,
@@ -258,7 +259,7 @@ class WanFPSWrapper(_GeneratorBase):
             pre = lambda: x[:, :16].copy_(lat)
         g = self.engine.capture(x, timestep.view(-1), frames, StagePlan.write_slots(frames), visible, kv_cache.k_all, kv_cache.v_all,
                                 crossattn_cache.k_all, crossattn_cache.v_all, out[0], pre=pre, cross_rows=crossattn_cache.rows,
-                                attn_history=kv_cache.attn_history)
+                                attn_history=kv_cache.attn_history, cache_mode=cache_mode, residual=residual)
         return g if ys is None else _HeldGraph(g, x)
 
     def forward(self, noisy_image_or_video: torch.Tensor, conditional_dict: dict, timestep: torch.Tensor,
@@ -266,7 +267,7 @@ class WanFPSWrapper(_GeneratorBase):
                 current_start=None, classify_mode=False, concat_time_embeddings=False, clean_x=None, aug_t=None,
                 cache_start=None, out: Optional[torch.Tensor] = None, return_x0: bool = False, clip_fea=None, y=None,
                 workspace: Optional[torch.Tensor] = None, share_out: Optional[torch.Tensor] = None,
-                share_in: Optional[torch.Tensor] = None):
+                share_in: Optional[torch.Tensor] = None, cache_mode: int = 0, residual: Optional[torch.Tensor] = None):
         assert kv_cache is not None and crossattn_cache is not None, "the FPS path always runs with caches"
         assert noisy_image_or_video.shape[0] == 1, "batch size 1 (as every reference entry point)"
         lat, frames, visible, ys = self._stage(noisy_image_or_video[0], conditional_dict, kv_cache, crossattn_cache, current_start,
@@ -276,7 +277,8 @@ class WanFPSWrapper(_GeneratorBase):
         flow = self.engine.forward(x, t, frames, StagePlan.write_slots(frames), visible,
                                    kv_cache.k_all, kv_cache.v_all, crossattn_cache.k_all, crossattn_cache.v_all,
                                    out=None if out is None else out[0], cross_rows=crossattn_cache.rows, workspace=workspace,
-                                   share_out=share_out, share_in=share_in, attn_history=kv_cache.attn_history)
+                                   share_out=share_out, share_in=share_in, attn_history=kv_cache.attn_history,
+                                   cache_mode=cache_mode, residual=residual)
         flow_pred = flow.unsqueeze(0)
         pred_x0 = None
         if return_x0:                                                     # wan_wrapper.py:373-397 (unused by the pipeline)
@@ -640,20 +642,23 @@ class WanDiffusionWrapper(_GeneratorBase):
 
     def flow(self, x: torch.Tensor, t: torch.Tensor, start_frame: int, write_slots, visible_slots, kv_cache: KVCache,
              crossattn_cache: CrossAttnCache, out: Optional[torch.Tensor] = None,
-             frame_base: Optional[torch.Tensor] = None) -> torch.Tensor:
+             frame_base: Optional[torch.Tensor] = None, cache_mode: int = 0, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One CausalWanModel._forward_inference on explicit slots: x [F, 16, h, w] bf16, t [F] float32 on the device.  Stateless
         attention; the text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch).
         ``frame_base`` (int32 device scalar): `start_frame` is then relative to its value at execution time (DitEngine.forward).
         A ``KVCache(..., batch=G)``: x [G*F, 16, h, w] and t [G*F] sample-major, slots as ``slots(..., batch=G)`` gives them, every
-        sample at `start_frame` (DitEngine.forward_groups)."""
+        sample at `start_frame` (DitEngine.forward_groups).  `cache_mode` / `residual`: step caching (DitEngine.forward); a batched
+        cache has no cached form."""
         G = getattr(kv_cache, "batch", 1)
         if G > 1:
+            if cache_mode:
+                raise ValueError("WanDiffusionWrapper.flow: step caching is not available to a batched (grouped) forward")
             frames = [start_frame + i for _ in range(G) for i in range(x.shape[0] // G)]
             return self.engine.forward_groups(x, t, G, frames, write_slots, visible_slots, kv_cache.k_all, kv_cache.v_all,
                                               crossattn_cache.pairs(), out=out, frame_base=frame_base)
         frames = [start_frame + i for i in range(x.shape[0])]
         return self.engine.forward(x, t, frames, write_slots, visible_slots, kv_cache.k_all, kv_cache.v_all, crossattn_cache.k_all,
-                                   crossattn_cache.v_all, out=out, frame_base=frame_base)
+                                   crossattn_cache.v_all, out=out, frame_base=frame_base, cache_mode=cache_mode, residual=residual)
 
     @staticmethod
     def fewstep_update(flow: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], x0_out: torch.Tensor, sigma_t: float,
@@ -668,14 +673,15 @@ class WanDiffusionWrapper(_GeneratorBase):
     # -- is_causal=False: WanModel.forward over the whole clip (wan/modules/model.py, utils/wan_wrapper.py:277-281) ------------------
     def flow_full(self, x: torch.Tensor, t: torch.Tensor, crossattn_cache: CrossAttnCache, out: Optional[torch.Tensor] = None,
                   share_out: Optional[torch.Tensor] = None, share_in: Optional[torch.Tensor] = None,
-                  workspace: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  workspace: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, cache_mode: int = 0,
+                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One whole-clip forward: x [F, 16, h, w] bf16, t ONE float32 on the device (uniform_timestep).  Stateless attention; the
         text cross-attention runs over all text_len rows (no prompt-dependent host value enters the launch: a captured graph
         serves every later prompt).  share_out / share_in / workspace as in DitEngine.forward_full.  i2v model type: `y`
         [F, 20, h, w] bf16 (frame-major) is required and `set_image` must have run; the image K / V it fills keep their address, so
-        a captured graph serves every later image too."""
+        a captured graph serves every later image too.  `cache_mode` / `residual`: step caching (DitEngine.forward_full)."""
         return self.engine.forward_full(x, t, crossattn_cache.k_all, crossattn_cache.v_all, out=out, share_out=share_out,
-                                        share_in=share_in, workspace=workspace, y=y)
+                                        share_in=share_in, workspace=workspace, y=y, cache_mode=cache_mode, residual=residual)
 
     def set_image(self, clip_fea: torch.Tensor) -> None:
         """i2v model type: (re)build the per-layer image K / V of `clip_fea` ([257, 1280] or [1, 257, 1280]) into the wrapper's one
