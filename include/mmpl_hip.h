@@ -445,7 +445,10 @@ int mmpl_fewstep_update(const void* flow, void* x, const void* noise, void* x0_o
  * i.e. per (32-channel chunk, tap, 16-row group) the 64 lanes' 16 bytes back to back, lane = 16 * (8-channel k chunk) + row
  * (mmpl_amd/vae.py VaeEngine._frag_pack is the reference packer).  bind_weights rejects any other count: a caller that binds
  * by state-dict name must produce the .frag entries too.
- * mode 0 = decode, 1 = encode.  mean / inv_std: host float[16] (bf16-rounded values of the wrapper's scale tensors). */
+ * mode 0 = decode, 1 = encode.  mean / inv_std: host float[16] (bf16-rounded values of the wrapper's scale tensors).
+ * Geometry: any lat_h, lat_w >= 2.  The attention of the middle blocks runs over lat_h * lat_w tokens; where that is no multiple
+ * of 4 (3 x 5) the scores GEMM, which stores four columns at a time, runs over the token count rounded up to 4 against zero key
+ * rows whose scores the softmax does not read. */
 typedef struct MmplVae MmplVae;
 int mmpl_vae_num_weights(void);
 const char* mmpl_vae_weight_name(int i);
@@ -598,7 +601,7 @@ int mmpl_clip_visual(const void* patches, int n_patch, int pk, int dim, int mlp_
  * One launch of vae_kernels.hip / taehv_kernels.hip on plain arguments, as mmpl_gemm / mmpl_layernorm are for the DiT kernels.  The
  * product never calls them (mmpl_vae_* / mmpl_taehv_* drive the same launchers); they add no arithmetic.  All pointers are device
  * bf16 unless stated.  Every argument check runs before the first HIP call and a rejected call launches nothing: null pointers,
- * non-positive sizes, more than 2^31 - 1 pixels in one launch (mmpl_vae_conv / _norm / _upsample / _zprep / _mu_out; mmpl_taehv_prep: 2^25 - 1),
+ * non-positive sizes, more than 2^31 - 1 pixels in one launch (mmpl_vae_conv / _norm / _upsample / _zprep / _mu_out / _px_in / _px_out / _px_out_u8; mmpl_taehv_prep: 2^25 - 1),
  * misaligned pointers (the kernels move 8 / 16 bytes per access), more than 8 ring or norm frames, and whatever the launcher itself
  * rejects.  The checks bound what a kernel reaches by the sizes stated in the call; "reach" below is how large
  * each buffer must then be.
@@ -645,6 +648,17 @@ int mmpl_vae_zprep(const void* z, int F, int h, int w, const float* mean, const 
  * out dev float32 [>= f_out + F, 16, h, w] at frame f + f_out.  mean / inv_std: host float[16]. */
 int mmpl_vae_mu_out(const void* enc, const void* w1, const void* b1, const float* mean, const float* inv_std, void* out, int F,
                     int f_out, int h, int w, mmpl_stream_t stream);
+/* px_in_kernel: px [3, Ttot, H, W] (t0 + T <= Ttot) -> channels [0, 3) of the interior of dst [>= dt0 + T, H + 2, W + 2, 32]: frame
+ * t0 + t goes to frame dt0 + t.  Three channels per pixel are written and nothing else: border, channels [3, 32) and the frames in
+ * front of dt0 keep what they held.  2-byte accesses. */
+int mmpl_vae_px_in(const void* px, void* dst, int Ttot, int t0, int T, int H, int W, int dt0, mmpl_stream_t stream);
+/* px_out_kernel: src [T, H, W, 4] (8-byte aligned; the fourth channel is the decoder head's padding and is dropped) ->
+ * out dev float32 [>= t_out + T, 3, H, W] at frame t + t_out, clamp(-1, 1) of the bf16 value. */
+int mmpl_vae_px_out(const void* src, void* out, int T, int H, int W, int t_out, mmpl_stream_t stream);
+/* px_out_u8_kernel: src [T, H, W, 4] (16-byte aligned) -> out dev uint8 [>= t_out + T, H, W, 3] (4-byte aligned) at frame t + t_out:
+ * (x.clamp(-1, 1) * 0.5 + 0.5).clamp(0, 1), then (v * 255.0).clamp(0, 255) truncated, in float32.  A lane converts 4 consecutive
+ * pixels: W % 8 == 0 and T * H * W % 4 == 0 are required. */
+int mmpl_vae_px_out_u8(const void* src, void* out, int T, int H, int W, int t_out, mmpl_stream_t stream);
 /* taehv_conv_kernel, TaehvConvArgs (taehv_kernels.h) field for field: a 3x3 (ntaps 9) or 1x1 (ntaps 1) conv over padded frames
  * [Ho + 2, Wo + 2, C] with a zero border, out = bf16(relu?(acc + bias? + skip?)).
  *   src0 / src1  output frame f reads src0 + f * fs0 (C0 channels) and, when C1 > 0, src1 + f * fs1 (C1 channels) as one K axis

@@ -158,6 +158,36 @@ int mmpl_vae_mu_out(const void* enc, const void* w1, const void* b1, const float
   LAUNCH(vae_launch_mu_out(a, (hipStream_t)stream), me);
 }
 
+int mmpl_vae_px_in(const void* px, void* dst, int Ttot, int t0, int T, int H, int W, int dt0, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_px_in";
+  REJECT(!px || !dst, me, "null argument");
+  REJECT(Ttot < 1 || T < 1 || H < 1 || W < 1 || t0 < 0 || dt0 < 0, me, "non-positive size");
+  REJECT((long)t0 + T > Ttot, me, "t0 + T > Ttot");
+  REJECT(too_many(T, H, W), me, "too many pixels");
+  REJECT(misaligned(px, 2) || misaligned(dst, 2), me, "misaligned pointer");
+  LAUNCH(vae_launch_px_in((const bf16_t*)px, (bf16_t*)dst, Ttot, t0, T, H, W, dt0, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_px_out(const void* src, void* out, int T, int H, int W, int t_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_px_out";
+  REJECT(!src || !out, me, "null argument");
+  REJECT(T < 1 || H < 1 || W < 1 || t_out < 0, me, "non-positive size");
+  REJECT(too_many(T, H, W), me, "too many pixels");
+  REJECT(misaligned(src, 8) || misaligned(out, 4), me, "misaligned pointer");
+  LAUNCH(vae_launch_px_out((const bf16_t*)src, (float*)out, T, H, W, t_out, (hipStream_t)stream), me);
+}
+
+int mmpl_vae_px_out_u8(const void* src, void* out, int T, int H, int W, int t_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_vae_px_out_u8";
+  REJECT(!src || !out, me, "null argument");
+  REJECT(T < 1 || H < 1 || W < 1 || t_out < 0, me, "non-positive size");
+  REJECT(too_many(T, H, W), me, "too many pixels");
+  REJECT(W % 8, me, "W % 8 (a lane's 4 pixels stay within a row)");
+  REJECT(((long)T * H * W) % 4, me, "T * H * W % 4");          // (follows from W % 8; stated because the kernel counts groups of 4 pixels)
+  REJECT(misaligned(src, 16) || misaligned(out, 4), me, "misaligned pointer");
+  LAUNCH(vae_launch_px_out_u8((const bf16_t*)src, (unsigned char*)out, T, H, W, t_out, (hipStream_t)stream), me);
+}
+
 // One launch of mmpl_launch_gemm in any of the forms the forwards use (include/mmpl_hip.h).  The plan is the launcher's own
 // (mmpl_gemm_plan, which mmpl_launch_gemm consults for every choice); it is computed after the checks, because the 256 x 256
 // kernels' plan asks the device for its CU count.

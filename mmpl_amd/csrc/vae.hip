@@ -263,9 +263,12 @@ void res_block(Ctx& c, const std::string& pre, const bf16_t* x, bf16_t* out, bf1
 
 // AttentionBlock (vae.py:223-262), per frame, single head of dim C over H*W tokens
 void attn_block(Ctx& c, const std::string& pre, const bf16_t* x, bf16_t* out, int T, int H, int W, int C) {
-  const int HW = H * W, HWp = (HW + 63) / 64 * 64;
+  // HW4: the GEMM stores four columns at a time, so the scores are computed for HW rounded up to 4 keys; the up to three extra key
+  // rows of qkv are never written (zero since the workspace was cleared) and their score columns lie inside the row's padding
+  // [HW, HWp), which the softmax does not read.  HW % 4 == 0 (every production geometry): nothing changes.
+  const int HW = H * W, HWp = (HW + 63) / 64 * 64, HW4 = (HW + 3) / 4 * 4;
   bf16_t* xn = c.ar.get(pre + "xn", (size_t)HW * C);
-  bf16_t* qkv = c.ar.get(pre + "qkv", (size_t)HW * 3 * C);
+  bf16_t* qkv = c.ar.get(pre + "qkv", (size_t)HW4 * 3 * C);
   float* sc = (float*)c.ar.get(pre + "scores", (size_t)HW * HWp, 4);
   bf16_t* p = c.ar.get(pre + "p", (size_t)HW * HWp);
   bf16_t* vt = c.ar.get(pre + "vt", (size_t)C * HWp);
@@ -274,7 +277,7 @@ void attn_block(Ctx& c, const std::string& pre, const bf16_t* x, bf16_t* out, in
     const bf16_t* xt = x + (size_t)t * HW * C;
     norm_into(c, xt, 1, H, W, C, c.v->W(pre + "norm.gamma"), false, xn, H, W, C, 0, 0, 0);
     gemm(c, xn, C, c.v->W(pre + "to_qkv.weight"), C, c.v->W(pre + "to_qkv.bias"), qkv, 3 * C, HW, 3 * C, C, EPI_BIAS, nullptr, 0);
-    gemm(c, qkv, 3 * C, qkv + C, 3 * C, nullptr, sc, HWp, HW, HW, C, EPI_F32_SCALE, nullptr, 0, 1.0f / sqrtf((float)C));
+    gemm(c, qkv, 3 * C, qkv + C, 3 * C, nullptr, sc, HWp, HW, HW4, C, EPI_F32_SCALE, nullptr, 0, 1.0f / sqrtf((float)C));
     if (!c.dry) {
       c.chk(vae_launch_softmax(sc, HWp, p, HWp, HW, HW, c.s), "softmax");
       c.chk(vae_launch_transpose(qkv + 2 * C, 3 * C, vt, HWp, HW, C, c.s), "transpose");

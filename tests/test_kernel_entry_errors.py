@@ -92,6 +92,34 @@ def test_vae_pass_entry_points_reject():
     assert "null argument" in e(lib.mmpl_vae_mu_out(P, P, None, f16, f16, P, 1, 0, 4, 4, None))
     assert "non-positive" in e(lib.mmpl_vae_mu_out(P, P, P, f16, f16, P, 0, 0, 4, 4, None))
     assert "too many pixels" in e(lib.mmpl_vae_mu_out(P, P, P, f16, f16, P, 2, 0, 1 << 16, 1 << 14, None))
+    # px_in(px, dst, Ttot, t0, T, H, W, dt0)
+    assert "null argument" in e(lib.mmpl_vae_px_in(None, P, 5, 0, 1, 8, 8, 2, None))
+    assert "null argument" in e(lib.mmpl_vae_px_in(P, None, 5, 0, 1, 8, 8, 2, None))
+    assert "non-positive" in e(lib.mmpl_vae_px_in(P, P, 5, 0, 0, 8, 8, 2, None))
+    assert "non-positive" in e(lib.mmpl_vae_px_in(P, P, 5, -1, 1, 8, 8, 2, None))
+    assert "non-positive" in e(lib.mmpl_vae_px_in(P, P, 5, 0, 1, 8, 8, -1, None))
+    assert "t0 + T > Ttot" in e(lib.mmpl_vae_px_in(P, P, 5, 2, 4, 8, 8, 2, None))
+    assert "t0 + T > Ttot" in e(lib.mmpl_vae_px_in(P, P, 0x7fffffff, 0x7fffffff, 1, 8, 8, 2, None))
+    assert "too many pixels" in e(lib.mmpl_vae_px_in(P, P, 5, 0, 2, 1 << 16, 1 << 14, 2, None))
+    assert "misaligned" in e(lib.mmpl_vae_px_in(P + 1, P, 5, 0, 1, 8, 8, 2, None))
+    # px_out(src, out, T, H, W, t_out)
+    assert "null argument" in e(lib.mmpl_vae_px_out(None, P, 1, 8, 8, 0, None))
+    assert "null argument" in e(lib.mmpl_vae_px_out(P, None, 1, 8, 8, 0, None))
+    assert "non-positive" in e(lib.mmpl_vae_px_out(P, P, 1, 0, 8, 0, None))
+    assert "non-positive" in e(lib.mmpl_vae_px_out(P, P, 1, 8, 8, -1, None))
+    assert "too many pixels" in e(lib.mmpl_vae_px_out(P, P, 2, 1 << 16, 1 << 14, 0, None))
+    assert "misaligned" in e(lib.mmpl_vae_px_out(P + 4, P, 1, 8, 8, 0, None))          # the [.., 4] bf16 source: 8 bytes per pixel
+    assert "misaligned" in e(lib.mmpl_vae_px_out(P, P + 2, 1, 8, 8, 0, None))
+    # px_out_u8(src, out, T, H, W, t_out)
+    assert "null argument" in e(lib.mmpl_vae_px_out_u8(None, P, 1, 8, 8, 0, None))
+    assert "null argument" in e(lib.mmpl_vae_px_out_u8(P, None, 1, 8, 8, 0, None))
+    assert "non-positive" in e(lib.mmpl_vae_px_out_u8(P, P, 0, 8, 8, 0, None))
+    assert "non-positive" in e(lib.mmpl_vae_px_out_u8(P, P, 1, 8, 8, -1, None))
+    assert "too many pixels" in e(lib.mmpl_vae_px_out_u8(P, P, 2, 1 << 16, 1 << 14, 0, None))
+    assert "W % 8" in e(lib.mmpl_vae_px_out_u8(P, P, 1, 8, 12, 0, None))
+    assert "W % 8" in e(lib.mmpl_vae_px_out_u8(P, P, 1, 3, 5, 0, None))
+    assert "misaligned" in e(lib.mmpl_vae_px_out_u8(P + 8, P, 1, 8, 8, 0, None))       # two 16-byte loads per lane
+    assert "misaligned" in e(lib.mmpl_vae_px_out_u8(P, P + 2, 1, 8, 8, 0, None))       # three dword stores per lane
     assert "null argument" in e(lib.mmpl_taehv_prep(None, P, 4, 4, None))
     assert "non-positive" in e(lib.mmpl_taehv_prep(P, P, 0, 4, None))
     assert "misaligned" in e(lib.mmpl_taehv_prep(P, P + 8, 4, 4, None))

@@ -5,7 +5,9 @@ torch conv3d in float64 (tests/vae_kernel_ref.py).  In the exact regime (integer
 result must be bit-identical; everything a launch does not own -- borders, channels [N, ldd), frames and slots it was not given,
 pixels outside its window -- must still hold the sentinel it was filled with.  Each case asserts the kernel the launcher reported.
 The division / exponential passes follow the near-tie rule, the softmax and the Gaussian cases derived bounds (see the reference
-module's docstring and the tests below).  Whole-network accuracy stays in tests/test_vae_gpu.py."""
+module's docstring and the tests below).  The pixel passes (px_in, px_out, px_out_u8) are pure data movement and clamping and must
+match exactly, px_out_u8 on every bf16 bit pattern.  Whole-network accuracy stays in tests/test_vae_gpu.py; the compositions are held
+to a chain of these launches in tests/test_vae_chain_gpu.py."""
 import ctypes as C
 import math
 
@@ -253,3 +255,119 @@ def test_mu_out(lib):
     assert torch.equal(got.to(torch.bfloat16).float(), got), "mu_out stores bf16-rounded values"
     R.check_near_tie(got.to(torch.bfloat16), R.bf16_exact(b["ref"]), b["amb"], "mu_out")
     assert bool((out[:f_out] == R.SENTINEL).all()) and bool((out[f_out + F_:] == R.SENTINEL).all())
+
+
+# ------------------------------------------------------------------------------------------------ pixel in / out
+CANARY_TAIL = 256                  # elements behind every buffer of the pixel cases that no launch may touch
+
+
+def _tailed(shape, dtype, fill):
+    """A buffer of `shape` filled with `fill` with CANARY_TAIL more elements of it behind: (view of the buffer, the whole)."""
+    n = math.prod(shape)
+    whole = torch.full((n + CANARY_TAIL,), fill, dtype=dtype, device=DEV)
+    return whole[:n].view(shape), whole
+
+
+def _tail_intact(whole, fill):
+    return bool((whole[-CANARY_TAIL:].cpu().double() == fill).all())
+
+
+@pytest.mark.parametrize("H,W", [(16, 24), (8, 8)])
+@pytest.mark.parametrize("dt0", [0, 2])
+@pytest.mark.parametrize("t0,T", [(0, 1), (1, 4)])
+def test_px_in(lib, t0, T, dt0, H, W):
+    """px_in_kernel: frames t0 .. t0 + T - 1 of px [3, 5, H, W] -> channels 0..2 of the interior of frames dt0.. of a padded
+    32-channel volume, an exact copy; the border, channels 3..31 and the frames in front of dt0 keep the prefill."""
+    Ttot = 5
+    px = R._ints(R._rng(f"pxin{H}"), (3, Ttot, H, W), 255)
+    pxd, px_whole = _tailed((3, Ttot, H, W), torch.bfloat16, R.SENTINEL)
+    pxd.copy_(R.bf16_exact(px))
+    dst, whole = _tailed((dt0 + T, H + 2, W + 2, 32), torch.bfloat16, R.SENTINEL)
+    _lib.check(lib.mmpl_vae_px_in(_lib.ptr(pxd), _lib.ptr(dst), Ttot, t0, T, H, W, dt0, _lib.stream_ptr()), "mmpl_vae_px_in")
+    torch.cuda.synchronize()
+    vol = dst.cpu()
+    assert torch.equal(R.extract(vol, T, H, W, 3, dt0, 1, 1).double(), R.px_in_ref(px, t0, T))
+    assert R.outside_is(vol, T, H, W, 3, dt0, 1, 1), "px_in wrote more than three channels of the interior of its frames"
+    assert _tail_intact(whole, R.SENTINEL) and _tail_intact(px_whole, R.SENTINEL)
+
+
+def _px_out_src(name, T, H, W):
+    """[T, H, W, 4] bf16: Gaussian values of std 1.5 (a third of them outside [-1, 1]) with, in front, +-1, their bf16 neighbours on
+    both sides, +-0, and values far outside; channel 3 holds 0.5, which no other element holds."""
+    src = R._gauss_bf16(R._rng(name), (T, H, W, 4), 1.5).to(torch.float32)
+    src[src == 0.5] = 0.25
+    edge = [1.0, 1.0 + 2.0 ** -7, 1.0 - 2.0 ** -8, -1.0, -1.0 - 2.0 ** -7, -1.0 + 2.0 ** -8, 0.0, -0.0, 100.0, -100.0, 2.0 ** 127, -2.0 ** 127,
+            float("inf"), float("-inf"), 2.0 ** -126, -2.0 ** -133]
+    flat = src[..., :3].reshape(-1)
+    flat[:len(edge)] = torch.tensor(edge)
+    flat[-len(edge):] = torch.tensor(edge)
+    src[..., :3] = flat.view(T, H, W, 3)
+    src[..., 3] = 0.5
+    out = src.to(torch.bfloat16)
+    assert torch.equal(out.to(torch.float32), src)
+    return out
+
+
+@pytest.mark.parametrize("t_out", [0, 1])
+@pytest.mark.parametrize("T", [1, 4])
+def test_px_out(lib, T, t_out):
+    """px_out_kernel: float32 [t_out + T, 3, H, W] = clamp(-1, 1) of the bf16 value, bit for bit (the sign of zero included); the
+    fourth channel never appears, the frames in front of t_out and the tail keep the prefill."""
+    H, W = 16, 24
+    src = _px_out_src(f"pxout{T}", T, H, W)
+    srcd, src_whole = _tailed((T, H, W, 4), torch.bfloat16, R.SENTINEL)
+    srcd.copy_(src)
+    out, whole = _tailed((t_out + T, 3, H, W), torch.float32, R.SENTINEL)
+    _lib.check(lib.mmpl_vae_px_out(_lib.ptr(srcd), _lib.ptr(out), T, H, W, t_out, _lib.stream_ptr()), "mmpl_vae_px_out")
+    torch.cuda.synchronize()
+    got = out.cpu()
+    ref = R.px_out_ref(src)
+    assert torch.equal(got[t_out:].view(torch.int32), ref.view(torch.int32))
+    assert not bool((got == 0.5).any()), "the padding channel reached the output"
+    assert bool((got[:t_out] == R.SENTINEL).all()) and _tail_intact(whole, R.SENTINEL) and _tail_intact(src_whole, R.SENTINEL)
+
+
+def test_px_out_u8_every_bf16(lib):
+    """px_out_u8_kernel over all 65 536 bf16 bit patterns in every channel (three different orders), one launch of 4 frames of
+    64 x 256: bit-equal to PyTorch's float32 (x.clamp(-1, 1) * 0.5 + 0.5).clamp(0, 1) -> (v * 255.0).clamp(0, 255).to(uint8) on the CPU.
+    NaN patterns are excluded from that comparison (torch's clamp propagates a NaN, whose uint8 is undefined) and pinned instead:
+    the kernel's fmaxf(-1, NaN) returns -1, so every NaN, quiet or signalling, of either sign, becomes byte 0."""
+    T, H, W = 4, 64, 256
+    src = torch.empty(T * H * W, 4, dtype=torch.bfloat16)
+    src[:, 0] = R.all_bf16_patterns()
+    src[:, 1] = R.all_bf16_patterns(40503, 1)
+    src[:, 2] = R.all_bf16_patterns(-1 & 0xffff, 0)
+    src[:, 3] = 0.5
+    src = src.view(T, H, W, 4)
+    srcd, src_whole = _tailed((T, H, W, 4), torch.bfloat16, R.SENTINEL)
+    srcd.copy_(src)
+    out, whole = _tailed((T, H, W, 3), torch.uint8, 0xA5)
+    _lib.check(lib.mmpl_vae_px_out_u8(_lib.ptr(srcd), _lib.ptr(out), T, H, W, 0, _lib.stream_ptr()), "mmpl_vae_px_out_u8")
+    torch.cuda.synchronize()
+    got = out.cpu()
+    nan = torch.isnan(src[..., :3].float())
+    assert int(nan.sum()) == 3 * 2 * 127                           # exponent 0xff, mantissa != 0, both signs
+    ref = R.px_out_u8_ref(src)
+    nbad = int(((got != ref) & ~nan).sum())
+    print(f"px_out_u8: {nbad} of {int((~nan).sum())} non-NaN elements differ; NaN inputs give bytes {sorted(set(got[nan].tolist()))}")
+    assert nbad == 0
+    assert bool((got[nan] == 0).all()), "a NaN input must give byte 0"
+    assert set(got[~nan].tolist()) == set(range(256))              # the inputs reach every byte value
+    assert _tail_intact(whole, 0xA5) and _tail_intact(src_whole, R.SENTINEL)
+
+
+def test_px_out_u8_byte_order(lib):
+    """[T, H, W, 3] uint8 at frame t_out = 1, RGB within a pixel and pixels in row-major order: independent values per channel, so a
+    swapped byte or pixel inside a lane's group of 4 shows; frame 0 and the tail keep the prefill."""
+    T, H, W, t_out = 2, 16, 24, 1
+    src = (torch.rand((T, H, W, 4), generator=R._rng("pxu8")) * 2.5 - 1.25).to(torch.bfloat16)
+    srcd, _ = _tailed((T, H, W, 4), torch.bfloat16, R.SENTINEL)
+    srcd.copy_(src)
+    out, whole = _tailed((t_out + T, H, W, 3), torch.uint8, 0xA5)
+    _lib.check(lib.mmpl_vae_px_out_u8(_lib.ptr(srcd), _lib.ptr(out), T, H, W, t_out, _lib.stream_ptr()), "mmpl_vae_px_out_u8")
+    torch.cuda.synchronize()
+    got = out.cpu()
+    ref = R.px_out_u8_ref(src)
+    assert len(set(ref.reshape(-1).tolist())) > 200
+    assert torch.equal(got[t_out:], ref)
+    assert bool((got[:t_out] == 0xA5).all()) and _tail_intact(whole, 0xA5)

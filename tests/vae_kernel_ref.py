@@ -243,6 +243,32 @@ def mu_out_ref(enc, w1, b1, mean, inv_std):
     return rbf(d * inv_std).permute(0, 3, 1, 2).contiguous(), amb.permute(0, 3, 1, 2).contiguous()
 
 
+def px_in_ref(px: torch.Tensor, t0: int, T: int) -> torch.Tensor:
+    """px_in_kernel: px [3, Ttot, H, W] -> channels-last [T, H, W, 3], frames t0 .. t0 + T - 1, a copy."""
+    return px[:, t0:t0 + T].permute(1, 2, 3, 0).contiguous()
+
+
+def px_out_ref(src: torch.Tensor) -> torch.Tensor:
+    """px_out_kernel: src bf16 [T, H, W, 4] -> float32 [T, 3, H, W], clamp(-1, 1) of the bf16 value; channel 3 is dropped."""
+    return src[..., :3].to(torch.float32).clamp(-1.0, 1.0).permute(0, 3, 1, 2).contiguous()
+
+
+def px_out_u8_ref(src: torch.Tensor) -> torch.Tensor:
+    """px_out_u8_kernel: src bf16 [T, H, W, 4] -> uint8 [T, H, W, 3]: PyTorch's own float32 evaluation, on the CPU, of what the
+    pipeline and the CLI do to a decoded frame (the expression the kernel's comment cites).  NaN inputs have no defined uint8 here:
+    the caller masks them (nan_bf16)."""
+    x = src[..., :3].to(torch.float32)
+    v = (x.clamp(-1, 1) * 0.5 + 0.5).clamp(0, 1)
+    return (v * 255.0).clamp(0, 255).to(torch.uint8)
+
+
+def all_bf16_patterns(mult: int = 1, add: int = 0) -> torch.Tensor:
+    """All 65 536 bf16 bit patterns as a bf16 tensor, pattern (i * mult + add) mod 2^16 at index i (mult odd: a permutation)."""
+    assert mult % 2 == 1
+    i = (torch.arange(65536, dtype=torch.int64) * mult + add) & 0xffff
+    return torch.where(i >= 0x8000, i - 0x10000, i).to(torch.int16).view(torch.bfloat16)
+
+
 def taehv_prep_ref(z):
     """z [16, h, w] -> ([h, w, 16], ambiguous)."""
     v = torch.tanh(z / 3.0) * 3.0
