@@ -601,7 +601,7 @@ int mmpl_clip_visual(const void* patches, int n_patch, int pk, int dim, int mlp_
  * One launch of vae_kernels.hip / taehv_kernels.hip on plain arguments, as mmpl_gemm / mmpl_layernorm are for the DiT kernels.  The
  * product never calls them (mmpl_vae_* / mmpl_taehv_* drive the same launchers); they add no arithmetic.  All pointers are device
  * bf16 unless stated.  Every argument check runs before the first HIP call and a rejected call launches nothing: null pointers,
- * non-positive sizes, more than 2^31 - 1 pixels in one launch (mmpl_vae_conv / _norm / _upsample / _zprep / _mu_out / _px_in / _px_out / _px_out_u8; mmpl_taehv_prep: 2^25 - 1),
+ * non-positive sizes, more than 2^31 - 1 pixels in one launch (mmpl_vae_conv / _norm / _upsample / _zprep / _mu_out / _px_in / _px_out / _px_out_u8, mmpl_taehv_px_out; mmpl_taehv_prep: 2^25 - 1),
  * misaligned pointers (the kernels move 8 / 16 bytes per access), more than 8 ring or norm frames, and whatever the launcher itself
  * rejects.  The checks bound what a kernel reaches by the sizes stated in the call; "reach" below is how large
  * each buffer must then be.
@@ -674,6 +674,11 @@ int mmpl_taehv_conv(const void* src0, const void* src1, long long fs0, long long
                     int Nsplit, int relu, const void* skip, long long fss, void* keep, mmpl_stream_t stream);
 /* taehv_prep_kernel: z [16, h, w] -> bf16(tanh(z / 3) * 3) -> channels [0, 16) of the interior of dst [h + 2, w + 2, 32] (16-byte aligned). */
 int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream);
+/* taehv_px_out_kernel: head frames src [T, H + 2, W + 2, 4] (8-byte aligned; interiors are read, the fourth channel is the head's
+ * padding and is dropped) -> out at frame t + t_out.  out_format 0: dev float32 [>= t_out + T, 3, H, W] (4-byte aligned), the bf16
+ * value as it is (no clamp; NaN and inf pass through); 1: dev uint8 [>= t_out + T, H, W, 3] = (x.clamp(0, 1) * 255) truncated, in
+ * float32 from the same bf16 value.  One thread per pixel, 1- and 4-byte stores: no condition on W.  At most 2^31 - 1 pixels. */
+int mmpl_taehv_px_out(const void* src, void* out, int out_format, int T, int H, int W, int t_out, mmpl_stream_t stream);
 /* taehv_conv_in_kernel (taehv_enc_kernels.hip), the encoder's input layer: conv 3->64 3x3 (zero padding 1) + bias + ReLU straight
  * from the caller's pixels.  px: in_format 0 dev float32 [T, 3, H, W] (4-byte aligned); 1 dev uint8 [T, H, W, 3], read as
  * bf16(u / 255).  Wfrag: the packed [64, 32] matrix (k = (3 ky + kx) * 3 + c, k >= 27 zero) fragment-major, 2048 elements; bias [64].

@@ -426,6 +426,16 @@ int mmpl_taehv_prep(const void* z, void* dst, int h, int w, mmpl_stream_t stream
   LAUNCH(taehv_launch_prep((const bf16_t*)z, (bf16_t*)dst, h, w, (hipStream_t)stream), me);
 }
 
+int mmpl_taehv_px_out(const void* src, void* out, int out_format, int T, int H, int W, int t_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_taehv_px_out";
+  REJECT(!src || !out, me, "null argument");
+  REJECT(out_format != 0 && out_format != 1, me, "unknown out_format");
+  REJECT(T < 1 || H < 1 || W < 1 || t_out < 0, me, "non-positive size");
+  REJECT(too_many(T, H + 2L, W + 2L), me, "too many pixels");
+  REJECT(misaligned(src, 8) || misaligned(out, out_format == 0 ? 4 : 1), me, "misaligned pointer");
+  LAUNCH(taehv_launch_px_out((const bf16_t*)src, out, out_format, T, H, W, t_out, (hipStream_t)stream), me);
+}
+
 int mmpl_taehv_conv_in(const void* px, int in_format, const void* Wfrag, const void* bias, int T, int H, int W, void* dst,
                        long long fsd, mmpl_stream_t stream) {
   const char* me = "mmpl_taehv_conv_in";

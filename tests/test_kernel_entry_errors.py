@@ -123,6 +123,20 @@ def test_vae_pass_entry_points_reject():
     assert "null argument" in e(lib.mmpl_taehv_prep(None, P, 4, 4, None))
     assert "non-positive" in e(lib.mmpl_taehv_prep(P, P, 0, 4, None))
     assert "misaligned" in e(lib.mmpl_taehv_prep(P, P + 8, 4, 4, None))
+    # taehv px_out(src, out, out_format, T, H, W, t_out)
+    assert "null argument" in e(lib.mmpl_taehv_px_out(None, P, 0, 1, 8, 8, 0, None))
+    assert "null argument" in e(lib.mmpl_taehv_px_out(P, None, 1, 1, 8, 8, 0, None))
+    assert "unknown out_format" in e(lib.mmpl_taehv_px_out(P, P, 2, 1, 8, 8, 0, None))
+    assert "unknown out_format" in e(lib.mmpl_taehv_px_out(P, P, -1, 1, 8, 8, 0, None))
+    assert "non-positive" in e(lib.mmpl_taehv_px_out(P, P, 0, 0, 8, 8, 0, None))
+    assert "non-positive" in e(lib.mmpl_taehv_px_out(P, P, 0, 1, 0, 8, 0, None))
+    assert "non-positive" in e(lib.mmpl_taehv_px_out(P, P, 1, 1, 8, -3, 0, None))
+    assert "non-positive" in e(lib.mmpl_taehv_px_out(P, P, 0, 1, 8, 8, -1, None))
+    assert "too many pixels" in e(lib.mmpl_taehv_px_out(P, P, 0, 2, 1 << 16, 1 << 14, 0, None))
+    assert "too many pixels" in e(lib.mmpl_taehv_px_out(P, P, 1, 1 << 30, 1 << 30, 1 << 30, 0, None))
+    assert "misaligned" in e(lib.mmpl_taehv_px_out(P + 4, P, 0, 1, 8, 8, 0, None))      # the [.., 4] bf16 source: 8 bytes per pixel
+    assert "misaligned" in e(lib.mmpl_taehv_px_out(P, P + 2, 0, 1, 8, 8, 0, None))      # float32 stores
+    assert e(lib.mmpl_taehv_px_out(P, P + 2, 0, 1, 8, 8, 0, None)).startswith("mmpl_taehv_px_out:")
 
 
 def _taehv(**kw):

@@ -4,6 +4,7 @@ One launch per case on operands made from plain tensors by TaehvEngine._repack, 
 explicitly up-sampled and zero-padded input (tests/vae_kernel_ref.py): bf16(relu(acc + bias + skip)).  In the exact regime the
 result must be bit-identical; the one-pixel borders, the channels [N, ldd), frames the launch does not address and the border of
 `keep` must still hold the sentinel.  Nw % 64 == 0 runs taehv_conv_kernel<4>, the head (Nw = 16) taehv_conv_kernel<1>.
+taehv_px_out_kernel (mmpl_taehv_px_out) does no rounding at all: both output formats are compared exactly over every bf16 pattern.
 Whole-network accuracy stays in tests/test_taehv_gpu.py."""
 import pytest
 import torch
@@ -145,3 +146,81 @@ def test_taehv_prep(lib, h, w):
     dst = dst.cpu()
     R.check_near_tie(R.extract(dst, 1, h, w, 16, 0, 1, 1)[0], R.bf16_exact(b["ref"]), b["amb"], "taehv_prep")
     assert R.outside_is(dst, 1, h, w, 16, 0, 1, 1)
+
+
+# ---------------------------------------------------------------------------------------------------- taehv_px_out_kernel
+PX_OUT_CANARY = 0x7FA5
+PX_OUT_TAIL = 128
+PX_OUT_CASES = [(3, 150, 147, 2), (1, 9, 13, 0)]           # T, H, W (ragged: no multiple of 4), t_out; 3 * 150 * 147 >= 65536
+
+
+def _bf16_bits(t):
+    return t.contiguous().view(torch.int16).to(torch.int32) & 0xffff
+
+
+def _px_out_frames(T, H, W, with_nan):
+    """Head frames [T, H + 2, W + 2, 4]: live channel c holds the bf16 patterns in a permutation of its own (all 65 536 of them when
+    T * H * W allows: every finite value, +-0, +-inf and, with_nan, every NaN); the fourth channel and the border hold the sentinel.
+    Without NaN the NaN patterns are replaced by 0.5."""
+    n = T * H * W
+    src = torch.full((T, H + 2, W + 2, 4), R.SENTINEL, dtype=torch.bfloat16)
+    for c, (mult, add) in enumerate([(1, 0), (257, 12345), (40503, 777)]):
+        v = R.all_bf16_patterns(mult, add).repeat((n + 65535) // 65536)[:n].clone()
+        if not with_nan:
+            v[torch.isnan(v)] = 0.5
+        src[:, 1:-1, 1:-1, c] = v.view(T, H, W)
+    return src
+
+
+def _run_px_out(lib, src, fmt, t_out):
+    T, H, W = src.shape[0], src.shape[1] - 2, src.shape[2] - 2
+    per = 3 * H * W * (4 if fmt == 0 else 1)                          # bytes of one output frame
+    nbytes = (t_out + T) * per
+    pad = -nbytes % 2
+    raw = torch.full(((nbytes + pad) // 2 + PX_OUT_TAIL,), PX_OUT_CANARY, dtype=torch.int16, device=DEV)
+    before = raw.cpu().view(torch.uint8).clone()
+    sd = src.to(DEV)
+    _lib.check(lib.mmpl_taehv_px_out(_lib.ptr(sd), _lib.ptr(raw), fmt, T, H, W, t_out, _lib.stream_ptr()), "mmpl_taehv_px_out")
+    torch.cuda.synchronize()
+    got = raw.cpu().view(torch.uint8)
+    assert torch.equal(got[:t_out * per], before[:t_out * per]), "frames in front of t_out were written"
+    assert torch.equal(got[nbytes:], before[nbytes:]), "bytes behind the last frame were written"
+    return got[t_out * per:nbytes]
+
+
+@pytest.mark.parametrize("T,H,W,t_out", PX_OUT_CASES)
+def test_taehv_px_out_float_is_the_bf16_bits(lib, T, H, W, t_out):
+    """Format 0: planar float32 whose bits are the bf16 pattern shifted up -- no clamp, NaN payloads and infinities kept."""
+    src = _px_out_frames(T, H, W, with_nan=True)
+    got = _run_px_out(lib, src, 0, t_out).view(torch.int32).view(T, 3, H, W)
+    want = (_bf16_bits(src[:, 1:-1, 1:-1, :3]) << 16).permute(0, 3, 1, 2)
+    nbad = int((got != want).sum())
+    print(f"px_out float {T} x {H} x {W} at frame {t_out}: {nbad} of {got.numel()} elements differ")
+    assert nbad == 0
+
+
+@pytest.mark.parametrize("T,H,W,t_out", PX_OUT_CASES)
+def test_taehv_px_out_uint8_truncates(lib, T, H, W, t_out):
+    """Format 1: (x.clamp(0, 1) * 255) truncated, in float32 from the bf16 value.  A bf16 value has 8 significant bits and so has 255:
+    the float32 product is exact, so the expected byte is floor(clamp(x) * 255) in exact arithmetic, and PyTorch's float32
+    evaluation of the header's expression gives the same."""
+    src = _px_out_frames(T, H, W, with_nan=False)
+    got = _run_px_out(lib, src, 1, t_out).view(T, H, W, 3)
+    x = src[:, 1:-1, 1:-1, :3]
+    want = (x.to(torch.float32).clamp(0, 1) * 255).to(torch.uint8)
+    assert torch.equal(want, torch.floor(x.to(torch.float64).clamp(0, 1) * 255).to(torch.uint8))
+    nbad = int((got != want).sum())
+    print(f"px_out uint8 {T} x {H} x {W} at frame {t_out}: {nbad} of {got.numel()} elements differ")
+    assert nbad == 0
+    if T * H * W < 65536:
+        return
+    # the 256 boundaries k / 255: the smallest bf16 value >= k / 255 gives k, the bf16 value just below it k - 1
+    line = R.bf16_line(R.all_bf16_patterns())
+    vals = R.all_bf16_patterns().to(torch.float64)
+    for c in range(3):
+        xc, gc = x[..., c].reshape(-1), got[..., c].reshape(-1).to(torch.int64)
+        lc = R.bf16_line(xc)
+        for k in range(1, 256):
+            at = int(line[(vals * 255 >= k) & torch.isfinite(vals)].min())       # on the monotone line of bf16 values
+            assert bool((gc[lc == at] == k).all()) and int((lc == at).sum()) > 0, (c, k)
+            assert bool((gc[lc == at - 1] == k - 1).all()) and int((lc == at - 1).sum()) > 0, (c, k)
