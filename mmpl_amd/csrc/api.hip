@@ -266,16 +266,11 @@ int gemm_check_epilogue(int epi, const void* res, const void* gate) {
   return 0;
 }
 
-// The argument list mmpl_attn_fwd_variant and mmpl_attn_fwd_history share (n_pages already checked against MMPL_MAX_PAGES).
-AttnArgs attn_entry_args(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages, int ldk,
-                         int ldv, int n_pages, int page_rows, int Lq, int num_heads, float softmax_scale, void* workspace,
-                         size_t workspace_bytes) {
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv; a.n_pages = n_pages;
-  a.page_rows = page_rows; a.Lq = Lq; a.H = num_heads; a.scale = softmax_scale;
+// The pages and the workspace of mmpl_attn_fwd_variant and mmpl_attn_fwd_history (n_pages already checked against MMPL_MAX_PAGES).
+void attn_entry_pages(AttnArgs& a, const void* const* k_pages, const void* const* v_pages, int n_pages, void* workspace, size_t workspace_bytes) {
+  a.n_pages = n_pages;
   a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
   for (int i = 0; i < n_pages; ++i) { a.k_pages[i] = (const bf16_t*)k_pages[i]; a.v_pages[i] = (const bf16_t*)v_pages[i]; }
-  return a;
 }
 }  // namespace
 
@@ -509,7 +504,7 @@ int FwdCall::run() const {
         QkNormArgs a = {};
         a.q = w.big; a.ldq = 3 * d; a.k = w.big + d; a.ldk = 3 * d; a.v = nullptr; a.ldv = 3 * d;
         a.wq = h->Lw(l, L_NQ); a.wk = h->Lw(l, L_NK); a.rows = Lq; a.d = d; a.eps = c.eps; a.rope = 1;
-        a.q_scale = prescale_q ? scale * 1.4426950408889634f : 0.f;
+        a.q_scale = prescale_q ? scale * ATTN_LOG2E : 0.f;
         a.cos_tab = h->cos_tab; a.sin_tab = h->sin_tab; a.rows_per_frame = S; a.grid_w = h->gw;
         static_assert(sizeof(a.frame_ids) / sizeof(a.frame_ids[0]) >= MMPL_MAX_PAGES, "a whole clip's frames");
         for (int i = 0; i < nF; ++i) {
@@ -527,8 +522,7 @@ int FwdCall::run() const {
       MMPL_HIP_TRY(hipMemcpyAsync(w.x, share_in, (size_t)Lq * d * sizeof(bf16_t), hipMemcpyDeviceToDevice, s), "shared block-0 x");
     } else {
     {
-        AttnArgs a = {};
-        a.q = w.big; a.ldq = 3 * d; a.o = w.attn; a.ldo = d; a.ldk = d; a.ldv = d; a.page_rows = S; a.Lq = Lq / G; a.H = H; a.scale = scale;
+        AttnArgs a = attn_args(w.big, 3 * d, w.attn, d, d, d, S, Lq / G, H, scale);
         // sample g (the only one unless this is mmpl_dit_forward_groups): its visible slots, then its own frames' scratch pages
         AttnGroupPages pages[MMPL_MAX_GROUPS] = {};
         int np = 0;
@@ -572,11 +566,10 @@ int FwdCall::run() const {
     TRY(gemm(w.xn, d, h->Lw(l, L_CQ_W), d, h->Lw(l, L_CQ_B), w.big, d, Lq, d, d, EPI_BIAS, nullptr, 0, nullptr, 0, 1, s, tc, w.splitk));
     {
       ProfScope ps(K_QKNORM, 0, s);
-      MMPL_HIP_TRY(mmpl_launch_rmsnorm(w.big, d, h->Lw(l, L_CNQ), Lq, d, c.eps, s, cross_w64 ? scale * 1.4426950408889634f : 0.f), "cross q norm");
+      MMPL_HIP_TRY(mmpl_launch_rmsnorm(w.big, d, h->Lw(l, L_CNQ), Lq, d, c.eps, s, cross_w64 ? scale * ATTN_LOG2E : 0.f), "cross q norm");
     }
     {
-      AttnArgs a = {};
-      a.q = w.big; a.ldq = d; a.o = w.attn; a.ldo = d; a.ldk = d; a.ldv = d; a.page_rows = T; a.Lq = Lq; a.H = H; a.scale = scale;
+      AttnArgs a = attn_args(w.big, d, w.attn, d, d, d, T, Lq, H, scale);
       a.n_pages = 1;
       a.cross = 1;
       if (cross_w64) { a.variant = ATTN_W64; a.q_prescaled = true; }
@@ -854,8 +847,8 @@ int mmpl_attn_fwd_history(const void* q, int ldq, void* o, int ldo, const void* 
                           void* workspace, size_t workspace_bytes, void* history, void* stats_dev, mmpl_stream_t stream) {
   if (n_pages < 1 || n_pages > MMPL_MAX_PAGES) return fail("mmpl_attn_fwd_history", "n_pages out of range");
   if (reinterpret_cast<uintptr_t>(stats_dev) % 8) return fail("mmpl_attn_fwd_history", "stats must be 8-byte aligned");
-  AttnArgs a = attn_entry_args(q, ldq, o, ldo, k_pages, v_pages, ldk, ldv, n_pages, page_rows, Lq, num_heads, softmax_scale, workspace,
-                               workspace_bytes);
+  AttnArgs a = attn_args((const bf16_t*)q, ldq, (bf16_t*)o, ldo, ldk, ldv, page_rows, Lq, num_heads, softmax_scale);
+  attn_entry_pages(a, k_pages, v_pages, n_pages, workspace, workspace_bytes);
   a.variant = ATTN_W64;
   a.q_prescaled = 1;
   a.history = (unsigned char*)history;
@@ -873,8 +866,8 @@ int mmpl_attn_fwd_variant(const void* q, int ldq, void* o, int ldo, const void* 
   if (n_pages < 1 || n_pages > MMPL_MAX_PAGES) return fail("mmpl_attn_fwd", "n_pages out of range");
   if (variant != ATTN_AUTO && variant != ATTN_LOCKSTEP && variant != ATTN_W64 && variant != ATTN_W64 + 1)
     return fail("mmpl_attn_fwd", "unknown kernel variant");
-  AttnArgs a = attn_entry_args(q, ldq, o, ldo, k_pages, v_pages, ldk, ldv, n_pages, page_rows, Lq, num_heads, softmax_scale, workspace,
-                               workspace_bytes);
+  AttnArgs a = attn_args((const bf16_t*)q, ldq, (bf16_t*)o, ldo, ldk, ldv, page_rows, Lq, num_heads, softmax_scale);
+  attn_entry_pages(a, k_pages, v_pages, n_pages, workspace, workspace_bytes);
   a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
   a.q_prescaled = variant == ATTN_W64 + 1;
   a.cross = cross != 0;

@@ -21,6 +21,12 @@
 // "Swapped" formulation: S^T = K.Q^T and O^T = V^T.P^T with v_mfma_f32_32x32x16_bf16, so each lane owns one
 // query column: softmax statistics are lane-local (one cross-half shuffle per tile) and the P^T fragment for
 // the PV MFMA is just 8 consecutive accumulator registers packed to bf16 (no LDS round trip for P).
+//
+// attn_fwd_kernel and attn_cross_kernel are one block body in two loop shapes.  Shared: attn_lane (the lane's constants),
+// attn_block_map (block -> head, part), attn_load_q, attn_stage_load / attn_stage_store (a thread's share of a K / V tile),
+// attn_state_reset, attn_tile and attn_store_o (the epilogue).  Each kernel keeps only its loop.
+// The host side (plans and launches of all three kernels) follows the kernels; what the split-KV tail of a w64 launch leaves in
+// its workspace is AttnPartial (kernels.h).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -31,11 +37,12 @@
 
 namespace {
 
-constexpr int NW = 8, QW = 32, QB = NW * QW, KVB = 64;
+constexpr int NW = 8, QW = 32;              // waves per block, query rows per wave
+static_assert(NW * QW == ATTN_QB, "a block is one query block");
 constexpr int K_STRIDE = 272;               // bytes per K row in LDS (256 + 16 pad)
 constexpr int V_STRIDE = 320;               // bytes per V row in LDS (256 + 64 pad): 4 rows -> 4 bank windows
-constexpr int K_TILE = KVB * K_STRIDE;      // 17408
-constexpr int V_TILE = KVB * V_STRIDE;      // 20480
+constexpr int K_TILE = ATTN_KVB * K_STRIDE; // 17408
+constexpr int V_TILE = ATTN_KVB * V_STRIDE; // 20480
 constexpr int BUF = K_TILE + V_TILE;        // 37888
 constexpr int SMEM = 2 * BUF;               // 75776
 
@@ -47,12 +54,31 @@ MMPL_DEV bf16x8 tr_pair(const char* p0, const char* p1) {
   return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
+// Per-lane constants of a block: the lane's place in the 32x32 MFMA tiles and its LDS read offsets.
+struct AttnLane {
+  int hi, l31;             // lane = 32 hi + l31: query column l31 of the wave's 32, kv rows 4 hi .. of every 8
+  int k_off, v_off;        // K fragment: + 32*c bytes, + 32 rows for half 1; V fragment: + kv / d block offsets
+  float c, last_bias;      // scale * log2(e): p = exp2(s*c - m*c); the page's-last-row bias (attn_tile)
+};
+MMPL_DEV AttnLane attn_lane(const AttnArgs& a, int lane) {
+  AttnLane ln;
+  ln.hi = lane >> 5;
+  ln.l31 = lane & 31;
+  ln.k_off = ln.l31 * K_STRIDE + 16 * ln.hi;
+  const int i16 = lane & 15, g16 = (lane >> 4) & 1;
+  ln.v_off = (4 * ln.hi + (i16 >> 2)) * V_STRIDE + (16 * g16 + 4 * (i16 & 3)) * 2;
+  ln.c = a.scale * ATTN_LOG2E;
+  ln.last_bias = a.last_row_copies > 1 ? __logf((float)a.last_row_copies) / a.scale : 0.f;
+  return ln;
+}
+
 // One KV tile of 64 rows (kb / vb: its K and V in LDS) against the wave's 32 query rows (qf): S^T = K.Q^T, online softmax,
 // O^T += V^T.P^T.  `valid` = rows of the tile that exist; last_bias: see the page's-last-row comment below.
 struct AttnState { f32x16 o[4]; float m_run, l_run; };
-MMPL_DEV void attn_tile(const char* kb, const char* vb, const bf16x8 (&qf)[8], int valid, float last_bias, float c, int k_off, int v_off,
-                        int hi, AttnState& st) {
+MMPL_DEV void attn_tile(const char* kb, const char* vb, const bf16x8 (&qf)[8], int valid, const AttnLane& ln, AttnState& st) {
 #pragma clang fp contract(off)          // the one fma (the exponent's argument) is written out: the same bits whatever this is inlined into
+  const int hi = ln.hi, k_off = ln.k_off, v_off = ln.v_off;
+  const float c = ln.c, last_bias = ln.last_bias;
   f32x16 (&o)[4] = st.o;
   float& m_run = st.m_run;
   float& l_run = st.l_run;
@@ -92,7 +118,7 @@ MMPL_DEV void attn_tile(const char* kb, const char* vb, const bf16x8 (&qf)[8], i
     __builtin_amdgcn_s_setprio(0);
   }
   // lane holds kv_local = 32*half + 8*(r>>2) + 4*hi + (r&3) for its query column
-  if (valid < KVB) {
+  if (valid < ATTN_KVB) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int kv = 8 * (r >> 2) + 4 * hi + (r & 3);
@@ -102,7 +128,7 @@ MMPL_DEV void attn_tile(const char* kb, const char* vb, const bf16x8 (&qf)[8], i
   }
   // the page's last row stands for `last_row_copies` identical keys (the zero-padded tail of the text context, api.hip):
   // copies * exp(scale * s) = exp(scale * (s + ln(copies) / scale))
-  if (last_bias != 0.f && valid <= KVB) {
+  if (last_bias != 0.f && valid <= ATTN_KVB) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int kv = 8 * (r >> 2) + 4 * hi + (r & 3);
@@ -171,103 +197,64 @@ MMPL_DEV void attn_tile(const char* kb, const char* vb, const bf16x8 (&qf)[8], i
 
 }
 
-// CROSS only tags the symbol (attn_fwd_kernel<0> = self-attention over cache pages, <1> = text cross-attention) so that
-// profiles report the two launch populations separately; the code is identical.
-template <int CROSS>
-__global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int hi = lane >> 5, l31 = lane & 31;
-
-  // block -> (head, q block): keep a head's blocks on one XCD so its K/V stream is shared in that L2
-  const int n_qb = (a.Lq + QB - 1) / QB;
-  int head, qb;
-  if ((a.H & 7) == 0) {
+// ---- what the two lock-step kernels share besides attn_lane and attn_tile
+// block -> (head, part) with per_head blocks to a head: keep a head's blocks on one XCD so its K/V stream is shared in that L2
+MMPL_DEV void attn_block_map(int H, int per_head, int& head, int& part) {
+  if ((H & 7) == 0) {
     const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    head = xcd + 8 * (local / n_qb);
-    qb = local % n_qb;
+    head = xcd + 8 * (local / per_head);
+    part = local % per_head;
   } else {
-    head = blockIdx.x / n_qb;
-    qb = blockIdx.x % n_qb;
+    head = blockIdx.x / per_head;
+    part = blockIdx.x % per_head;
   }
-
-  // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q = l31][16c + 8*hi .. +8]
-  const int qrow = min(qb * QB + wave * QW + l31, a.Lq - 1);
-  bf16x8 qf[8];
-  {
-    const bf16_t* qp = a.q + (size_t)qrow * a.ldq + head * 128 + 8 * hi;
+}
+// Q fragments of query block qb (B operand of S^T = K.Q^T): lane holds Q[q = l31][16c + 8*hi .. +8]
+MMPL_DEV void attn_load_q(const AttnArgs& a, int head, int qb, int wave, int lane, bf16x8 (&f)[8]) {
+  const int qrow = min(qb * ATTN_QB + wave * QW + (lane & 31), a.Lq - 1);
+  const bf16_t* qp = a.q + (size_t)qrow * a.ldq + head * 128 + 8 * (lane >> 5);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) qf[c] = *reinterpret_cast<const bf16x8*>(qp + 16 * c);
-  }
-
-  const int tiles_pp = (a.page_rows + KVB - 1) / KVB;
-  const int total = a.n_pages * tiles_pp;
-
-  // ---- staging roles: thread moves 2x16 B of K and 2x16 B of V per tile
+  for (int c = 0; c < 8; ++c) f[c] = *reinterpret_cast<const bf16x8*>(qp + 16 * c);
+}
+// Staging roles: a thread moves 2x16 B of K and 2x16 B of V per tile (rows tid >> 4 and + 32, 16-byte chunk tid & 15), global ->
+// registers -> the padded LDS rows of the tile at `buf`
+struct AttnStage { u32x4 k[2], v[2]; };
+MMPL_DEV void attn_stage_load(AttnStage& g, const AttnArgs& a, const bf16_t* k_page, const bf16_t* v_page, int head, int row0, int tid) {
   const int srow = tid >> 4, schunk = tid & 15;
-  u32x4 rk[2], rv[2];
-  auto stage_load = [&](int t) {
-    const int p = t / tiles_pp, row0 = (t - p * tiles_pp) * KVB;
-    const bf16_t* kp = a.k_pages[p] + head * 128 + schunk * 8;
-    const bf16_t* vp = a.v_pages[p] + head * 128 + schunk * 8;
+  const bf16_t* kp = k_page + head * 128 + schunk * 8;
+  const bf16_t* vp = v_page + head * 128 + schunk * 8;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int r = min(row0 + srow + 32 * j, a.page_rows - 1);
-      rk[j] = *reinterpret_cast<const u32x4*>(kp + (size_t)r * a.ldk);
-      rv[j] = *reinterpret_cast<const u32x4*>(vp + (size_t)r * a.ldv);
-    }
-  };
-  auto stage_write = [&](int buf) {
-    char* kb = smem + buf * BUF;
-    char* vb = kb + K_TILE;
+  for (int j = 0; j < 2; ++j) {
+    const int r = min(row0 + srow + 32 * j, a.page_rows - 1);
+    g.k[j] = *reinterpret_cast<const u32x4*>(kp + (size_t)r * a.ldk);
+    g.v[j] = *reinterpret_cast<const u32x4*>(vp + (size_t)r * a.ldv);
+  }
+}
+MMPL_DEV void attn_stage_store(const AttnStage& g, char* buf, int tid) {
+  const int srow = tid >> 4, schunk = tid & 15;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      *reinterpret_cast<u32x4*>(kb + (srow + 32 * j) * K_STRIDE + schunk * 16) = rk[j];
-      *reinterpret_cast<u32x4*>(vb + (srow + 32 * j) * V_STRIDE + schunk * 16) = rv[j];
-    }
-  };
-
-  AttnState st;
+  for (int j = 0; j < 2; ++j) {
+    *reinterpret_cast<u32x4*>(buf + (srow + 32 * j) * K_STRIDE + schunk * 16) = g.k[j];
+    *reinterpret_cast<u32x4*>(buf + K_TILE + (srow + 32 * j) * V_STRIDE + schunk * 16) = g.v[j];
+  }
+}
+MMPL_DEV void attn_state_reset(AttnState& st) {
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
     for (int r = 0; r < 16; ++r) st.o[nb][r] = 0.f;
   st.m_run = -INFINITY;
   st.l_run = 0.f;
-  const float c = a.scale * 1.4426950408889634f;  // fold log2(e): p = exp2(s*c - m*c)
-  const float last_bias = a.last_row_copies > 1 ? __logf((float)a.last_row_copies) / a.scale : 0.f;
-
-  // per-lane LDS read offsets
-  const int k_off = l31 * K_STRIDE + 16 * hi;                                          // + 32*c bytes, + 32 rows for half 1
-  const int i16 = lane & 15, g16 = (lane >> 4) & 1;
-  const int v_off = (4 * hi + (i16 >> 2)) * V_STRIDE + (16 * g16 + 4 * (i16 & 3)) * 2;  // + kv/d block offsets
-
-  stage_load(0);
-  stage_write(0);
-  __syncthreads();
-
-  for (int t = 0; t < total; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < total) stage_load(t + 1);
-    const char* kb = smem + cur * BUF;
-    const char* vb = kb + K_TILE;
-
-    const int pg = t / tiles_pp, row0 = (t - pg * tiles_pp) * KVB;
-    attn_tile(kb, vb, qf, a.page_rows - row0, last_bias, c, k_off, v_off, hi, st);
-
-    if (t + 1 < total) stage_write(cur ^ 1);
-    __syncthreads();
-  }
-
-  // ---- epilogue: lane (q = l31, hi) holds O[q][32*nb + 8*g + 4*hi + {0..3}] in o[nb][4g..4g+3].  Straight from there a store
-  // instruction would write 16 B per query row (32 rows x 2 lanes x 8 B): 16 partial-sector writes per row.  The wave's 32 x 128
-  // tile goes through its own 8 KiB of the (now free: the tile loop ended on a barrier) K/V buffers instead and leaves as full
-  // 256-byte rows, 16 B per lane.  Row pitch 264 B: the 8-byte writes of lanes 0..31 fall on 64 different banks.
+}
+// Epilogue: lane (q = l31, hi) holds O[q][32*nb + 8*g + 4*hi + {0..3}] in o[nb][4g..4g+3].  Straight from there a store
+// instruction would write 16 B per query row (32 rows x 2 lanes x 8 B): 16 partial-sector writes per row.  The wave's 32 x 128
+// tile goes through its own 8 KiB of LDS at `ob` instead (no other wave touches it: no barrier) and leaves as full 256-byte rows,
+// 16 B per lane.  Row pitch 264 B: the 8-byte writes of lanes 0..31 fall on 64 different banks.
+constexpr int O_PITCH = 264;
+constexpr int O_STAGE = NW * QW * O_PITCH;  // 67584: all eight waves' tiles
+MMPL_DEV void attn_store_o(const AttnArgs& a, const AttnState& st, char* ob, int head, int qb, int wave, int lane, const AttnLane& ln) {
   const float l_tot = st.l_run + __shfl_xor(st.l_run, 32, 64);
   const float inv = 1.0f / l_tot;
-  constexpr int O_PITCH = 264;
-  static_assert(NW * QW * O_PITCH <= SMEM, "output staging fits the K/V buffers");
-  char* ob = smem + wave * (QW * O_PITCH);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
@@ -275,16 +262,61 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs a) {
       uint2 w;
       w.x = pack2bf(st.o[nb][4 * g] * inv, st.o[nb][4 * g + 1] * inv);
       w.y = pack2bf(st.o[nb][4 * g + 2] * inv, st.o[nb][4 * g + 3] * inv);
-      *reinterpret_cast<uint2*>(ob + l31 * O_PITCH + (32 * nb + 8 * g + 4 * hi) * 2) = w;
+      *reinterpret_cast<uint2*>(ob + ln.l31 * O_PITCH + (32 * nb + 8 * g + 4 * ln.hi) * 2) = w;
     }
   const int orow = lane >> 4, ochunk = lane & 15;                 // 4 rows x 16 chunks of 16 B per instruction
+  bf16_t* op = a.o + head * 128 + ochunk * 8;
+  const int ldo = a.ldo;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const int r = orow + 4 * k, q_out = qb * QB + wave * QW + r;
+    const int r = orow + 4 * k, q_out = qb * ATTN_QB + wave * QW + r;
     const uint2 lo = *reinterpret_cast<const uint2*>(ob + r * O_PITCH + ochunk * 16);
     const uint2 hi2 = *reinterpret_cast<const uint2*>(ob + r * O_PITCH + ochunk * 16 + 8);
-    if (q_out < a.Lq) *reinterpret_cast<uint4*>(a.o + (size_t)q_out * a.ldo + head * 128 + ochunk * 8) = uint4{lo.x, lo.y, hi2.x, hi2.y};
+    if (q_out < a.Lq) *reinterpret_cast<uint4*>(op + (size_t)q_out * ldo) = uint4{lo.x, lo.y, hi2.x, hi2.y};
   }
+}
+
+// CROSS only tags the symbol (attn_fwd_kernel<0> = self-attention over cache pages, <1> = text cross-attention) so that
+// profiles report the two launch populations separately; the code is identical.
+template <int CROSS>
+__global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int head, qb;
+  attn_block_map(a.H, (a.Lq + ATTN_QB - 1) / ATTN_QB, head, qb);
+  bf16x8 qf[8];
+  attn_load_q(a, head, qb, wave, lane, qf);
+
+  const int tiles_pp = (a.page_rows + ATTN_KVB - 1) / ATTN_KVB;
+  const int total = a.n_pages * tiles_pp;
+  AttnStage g;
+  auto stage_load = [&](int t) {
+    const int p = t / tiles_pp, row0 = (t - p * tiles_pp) * ATTN_KVB;
+    attn_stage_load(g, a, a.k_pages[p], a.v_pages[p], head, row0, tid);
+  };
+  AttnState st;
+  attn_state_reset(st);
+  const AttnLane ln = attn_lane(a, lane);
+
+  stage_load(0);
+  attn_stage_store(g, smem, tid);
+  __syncthreads();
+
+  for (int t = 0; t < total; ++t) {
+    const int cur = t & 1;
+    if (t + 1 < total) stage_load(t + 1);
+    const char* kb = smem + cur * BUF;
+
+    const int pg = t / tiles_pp, row0 = (t - pg * tiles_pp) * ATTN_KVB;
+    attn_tile(kb, kb + K_TILE, qf, a.page_rows - row0, ln, st);
+
+    if (t + 1 < total) attn_stage_store(g, smem + (cur ^ 1) * BUF, tid);
+    __syncthreads();
+  }
+
+  // o leaves through the K/V buffers, free now: the tile loop ended on a barrier
+  static_assert(O_STAGE <= SMEM, "output staging fits the K/V buffers");
+  attn_store_o(a, st, smem + wave * (QW * O_PITCH), head, qb, wave, lane, ln);
 }
 
 
@@ -295,92 +327,39 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs a) {
 // Here a block keeps ITS head's K / V tiles in LDS for a whole run of query blocks and every wave has the next block's q
 // fragments in flight while it works on the current one (the prefetch of the row passes, elementwise.hip); o leaves through a
 // separate staging area, so the loop has no barrier at all.  Bit-identical to attn_fwd_kernel (same attn_tile, same order).
-constexpr int O_PITCH_X = 264;
-constexpr int SMEM_X = 2 * BUF + NW * QW * O_PITCH_X;            // 143360 B: one block per CU, as the registers dictate anyway
+constexpr int SMEM_X = 2 * BUF + O_STAGE;                        // 143360 B: one block per CU, as the registers dictate anyway
 
 template <int NT>
 __global__ __launch_bounds__(512, 2) void attn_cross_kernel(AttnArgs a, int qb_per_block, int blocks_per_head) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int n_qb = (a.Lq + QB - 1) / QB;
-  int head, part;                                                // a head's blocks on one XCD, as attn_fwd_kernel
-  if ((a.H & 7) == 0) {
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    head = xcd + 8 * (local / blocks_per_head);
-    part = local % blocks_per_head;
-  } else {
-    head = blockIdx.x / blocks_per_head;
-    part = blockIdx.x % blocks_per_head;
-  }
+  int head, part;
+  attn_block_map(a.H, blocks_per_head, head, part);
   int qb = part * qb_per_block;
-  const int qb_end = min(qb + qb_per_block, n_qb);
+  const int qb_end = min(qb + qb_per_block, (a.Lq + ATTN_QB - 1) / ATTN_QB);
   if (qb >= qb_end) return;
 
-  auto load_q = [&](bf16x8 (&f)[8], int qblock) {
-    const int qrow = min(qblock * QB + wave * QW + l31, a.Lq - 1);
-    const bf16_t* qp = a.q + (size_t)qrow * a.ldq + head * 128 + 8 * hi;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) f[c] = *reinterpret_cast<const bf16x8*>(qp + 16 * c);
-  };
   bf16x8 qf[8], qn[8];
-  load_q(qf, qb);
-  {  // the head's K / V, once
-    const int srow = tid >> 4, schunk = tid & 15;
-    const bf16_t* kp = a.k_pages[0] + head * 128 + schunk * 8;
-    const bf16_t* vp = a.v_pages[0] + head * 128 + schunk * 8;
+  attn_load_q(a, head, qb, wave, lane, qf);
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = min(t * KVB + srow + 32 * j, a.page_rows - 1);
-        const u32x4 rk = *reinterpret_cast<const u32x4*>(kp + (size_t)r * a.ldk);
-        const u32x4 rv = *reinterpret_cast<const u32x4*>(vp + (size_t)r * a.ldv);
-        *reinterpret_cast<u32x4*>(smem + t * BUF + (srow + 32 * j) * K_STRIDE + schunk * 16) = rk;
-        *reinterpret_cast<u32x4*>(smem + t * BUF + K_TILE + (srow + 32 * j) * V_STRIDE + schunk * 16) = rv;
-      }
+  for (int t = 0; t < NT; ++t) {  // the head's K / V, once
+    AttnStage g;
+    attn_stage_load(g, a, a.k_pages[0], a.v_pages[0], head, t * ATTN_KVB, tid);
+    attn_stage_store(g, smem + t * BUF, tid);
   }
   __syncthreads();
-  const float c = a.scale * 1.4426950408889634f;
-  const float last_bias = a.last_row_copies > 1 ? __logf((float)a.last_row_copies) / a.scale : 0.f;
-  const int k_off = l31 * K_STRIDE + 16 * hi;
-  const int i16 = lane & 15, g16 = (lane >> 4) & 1;
-  const int v_off = (4 * hi + (i16 >> 2)) * V_STRIDE + (16 * g16 + 4 * (i16 & 3)) * 2;
-  char* ob = smem + 2 * BUF + wave * (QW * O_PITCH_X);
-  const int orow = lane >> 4, ochunk = lane & 15;
+  const AttnLane ln = attn_lane(a, lane);
+  char* ob = smem + 2 * BUF + wave * (QW * O_PITCH);
 
   for (;; ++qb) {
     const bool more = qb + 1 < qb_end;                           // block-uniform
-    if (more) load_q(qn, qb + 1);
+    if (more) attn_load_q(a, head, qb + 1, wave, lane, qn);
     asm volatile("" ::: "memory");                               // the prefetch is issued here, not where it is consumed
     AttnState st;
+    attn_state_reset(st);
 #pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) st.o[nb][r] = 0.f;
-    st.m_run = -INFINITY;
-    st.l_run = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-      attn_tile(smem + t * BUF, smem + t * BUF + K_TILE, qf, a.page_rows - t * KVB, last_bias, c, k_off, v_off, hi, st);
-    const float l_tot = st.l_run + __shfl_xor(st.l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        uint2 w;
-        w.x = pack2bf(st.o[nb][4 * g] * inv, st.o[nb][4 * g + 1] * inv);
-        w.y = pack2bf(st.o[nb][4 * g + 2] * inv, st.o[nb][4 * g + 3] * inv);
-        *reinterpret_cast<uint2*>(ob + l31 * O_PITCH_X + (32 * nb + 8 * g + 4 * hi) * 2) = w;
-      }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int r = orow + 4 * k, q_out = qb * QB + wave * QW + r;
-      const uint2 lo = *reinterpret_cast<const uint2*>(ob + r * O_PITCH_X + ochunk * 16);
-      const uint2 hi2 = *reinterpret_cast<const uint2*>(ob + r * O_PITCH_X + ochunk * 16 + 8);
-      if (q_out < a.Lq) *reinterpret_cast<uint4*>(a.o + (size_t)q_out * a.ldo + head * 128 + ochunk * 8) = uint4{lo.x, lo.y, hi2.x, hi2.y};
-    }
+    for (int t = 0; t < NT; ++t) attn_tile(smem + t * BUF, smem + t * BUF + K_TILE, qf, a.page_rows - t * ATTN_KVB, ln, st);
+    attn_store_o(a, st, ob, head, qb, wave, lane, ln);
     if (!more) break;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -394,34 +373,34 @@ __global__ __launch_bounds__(512, 2) void attn_cross_kernel(AttnArgs a, int qb_p
 // Combine the `sp` KV-range partials of each tail query block: O = sum_p w_p O_p / sum_p w_p l_p, w_p = 2^((m_p - m) c).
 // (n_groups > 0: the tail of a grouped launch -- (group, head) is the virtual head, the group's rows of o start at group * Lq)
 MMPL_DEV void attn_merge_block(const AttnArgs& a, int n_groups, int local_base, int sp, int tb) {
-  __shared__ float wgt[QB][4];
+  __shared__ float wgt[ATTN_QB][4];
   const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-  const int n_qb = (a.Lq + QB - 1) / QB;
+  const int n_qb = (a.Lq + ATTN_QB - 1) / ATTN_QB;
   int head, qb;
   if (!mmpl_attn_item(n_groups ? n_groups * a.H : a.H, n_qb, xcd, local_base + k, head, qb)) return;
   const int grp = n_groups ? head / a.H : 0;
   head -= grp * a.H;
   bf16_t* o = a.o + (size_t)grp * a.Lq * a.ldo;
-  const float* base = a.split_ws + (size_t)(xcd * tb + k) * sp * (QB * 130);
-  const float c = a.scale * 1.4426950408889634f;
+  const float* base = a.split_ws + (size_t)(xcd * tb + k) * sp * AttnPartial::FLOATS;    // this block's `sp` partials
+  const float c = a.scale * ATTN_LOG2E;
   {
     const int r = threadIdx.x;
     float m = -INFINITY;
-    for (int p = 0; p < sp; ++p) m = fmaxf(m, base[(size_t)p * (QB * 130) + QB * 128 + r]);
+    for (int p = 0; p < sp; ++p) m = fmaxf(m, base[(size_t)p * AttnPartial::FLOATS + AttnPartial::m(r)]);
     float l = 0.f, w[4] = {0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < sp; ++p) {
-      w[p] = __builtin_amdgcn_exp2f((base[(size_t)p * (QB * 130) + QB * 128 + r] - m) * c);
-      l += w[p] * base[(size_t)p * (QB * 130) + QB * 129 + r];
+      w[p] = __builtin_amdgcn_exp2f((base[(size_t)p * AttnPartial::FLOATS + AttnPartial::m(r)] - m) * c);
+      l += w[p] * base[(size_t)p * AttnPartial::FLOATS + AttnPartial::l(r)];
     }
     const float inv = 1.0f / l;
     for (int p = 0; p < 4; ++p) wgt[r][p] = w[p] * inv;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < QB * 32; i += 256) {          // 16-byte chunks, coalesced
-    const int r = i >> 5, ch = i & 31, q_out = qb * QB + r;
+  for (int i = threadIdx.x; i < ATTN_QB * 32; i += 256) {          // 16-byte chunks, coalesced
+    const int r = i >> 5, ch = i & 31, q_out = qb * ATTN_QB + r;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < sp; ++p) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(base + (size_t)p * (QB * 130) + (size_t)r * 128 + ch * 4);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(base + (size_t)p * AttnPartial::FLOATS + AttnPartial::o(r) + ch * 4);
       const float w = wgt[r][p];
       acc[0] += w * v[0]; acc[1] += w * v[1]; acc[2] += w * v[2]; acc[3] += w * v[3];
     }
@@ -439,8 +418,6 @@ __global__ __launch_bounds__(256) void attn_merge_groups_kernel(AttnGroupArgs ga
 }
 
 }  // namespace
-
-size_t mmpl_attention_split_ws_bytes() { return (size_t)256 * QB * 130 * sizeof(float); }   // <= one block per CU in the tail round
 
 // MMPL_ATTN_V1=1: A/B runs of a whole forward on the lock-step kernel (mmpl_config.h)
 int mmpl_attention_self_variant() { return mmpl_config().attn_v1 ? ATTN_LOCKSTEP : ATTN_W64; }
@@ -477,6 +454,42 @@ AttnArgs merge_contiguous_pages(const AttnArgs& a) {
   }
   return m;
 }
+
+// Tail round of a w64 launch: with one block per CU and b = n_qb * heads / 8 work items per XCD (kernels.h: mmpl_attn_item; 32 CUs),
+// the last tb = b mod 32 blocks of every XCD would run alone for a whole block time.  They are launched instead as `sp` blocks each
+// over 1/sp of the KV tiles (fp32 partials in ws) followed by a small merge kernel, so the tail round lasts ~1/sp block times.
+// Only a tail that fits ONE round of parts is split (tb * sp <= CUs per XCD): tails of 3 shorter rounds (tb = 17 -> 3 parts,
+// 23-24 -> 4) and launches with fewer items than CUs measured 0.6-8 % SLOWER than leaving them alone (profiles/r03Q_*).  A part
+// gets at least 8 of `tiles` (a grouped launch: the shortest group's).  heads: virtual heads (a grouped launch: n_groups * H).
+// Sets p.sp, p.tail_items and p.main_blocks.
+void plan_tail(AttnPlan& p, int heads, int n_qb, int tiles, const float* ws, size_t ws_bytes, int per_xcd) {
+  const int total = n_qb * heads;
+  const int b = (heads & 7) == 0 ? total / 8 : (total + 7) / 8, tb = b % per_xcd;
+  int sp = 1;
+  if (!mmpl_config().attn_nosplit && ws && b > per_xcd && tb > 0 && per_xcd / tb >= 2) {
+    sp = per_xcd / tb > 4 ? 4 : per_xcd / tb;
+    if (tiles / sp < 8 || (size_t)8 * tb * sp * AttnPartial::BYTES > ws_bytes) sp = 1;
+  }
+  p.sp = sp;
+  p.tail_items = sp == 1 ? 0 : tb;
+  p.main_blocks = 8 * (b - p.tail_items);
+}
+
+// The launches of a w64 plan on its argument struct (AttnArgs | AttnGroupArgs): the full rounds, one block per work item; then
+// the tail round's items as sp parts each, and their merge
+template <class Args>
+hipError_t launch_w64(const AttnPlan& p, const Args& a, void (*merge)(Args, int, int, int), hipStream_t s) {
+  const AttnW64Kernels<Args> k = mmpl_attention_w64_kernels<Args>();
+  const int smem = mmpl_attention_w64_smem();
+  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(k.main), smem); e != hipSuccess) return e;
+  if (hipError_t e = mmpl_dyn_smem_once(reinterpret_cast<const void*>(k.split), smem); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k.main, dim3(p.main_blocks), dim3(256), smem, s, a, 0, 1);
+  if (p.sp > 1) {
+    hipLaunchKernelGGL(k.split, dim3(8 * p.tail_items * p.sp), dim3(256), smem, s, a, p.main_blocks / 8, p.sp);
+    hipLaunchKernelGGL(merge, dim3(8 * p.tail_items), dim3(256), 0, s, a, p.main_blocks / 8, p.sp, p.tail_items);
+  }
+  return hipGetLastError();
+}
 }  // namespace
 
 int mmpl_attn_resolve_variant(const AttnArgs& a) {
@@ -505,13 +518,13 @@ AttnPlan mmpl_attn_plan(const AttnArgs& a_in) {
     return invalid;
   if (a.q_prescaled && variant != ATTN_W64) return invalid;
   if (a.last_row_copies > 1 && (variant != ATTN_LOCKSTEP || a.n_pages != 1)) return invalid;
-  const int n_qb = (a.Lq + QB - 1) / QB;
+  const int n_qb = (a.Lq + ATTN_QB - 1) / ATTN_QB;
   p.n_pages = a.n_pages;
   p.sp = 1;
-  if (variant == ATTN_LOCKSTEP && a.cross && a.n_pages == 1 && a.page_rows <= 2 * KVB) {
+  if (variant == ATTN_LOCKSTEP && a.cross && a.n_pages == 1 && a.page_rows <= 2 * ATTN_KVB) {
     // <= 2 KV tiles: the head's K / V stay in LDS over a run of query blocks; every CU gets one block (the registers allow no more),
     // the blocks of a head share its query blocks evenly
-    p.kv_tiles = (a.page_rows + KVB - 1) / KVB;
+    p.kv_tiles = (a.page_rows + ATTN_KVB - 1) / ATTN_KVB;
     p.kernel = p.kv_tiles == 1 ? ATTN_KERNEL_CROSS1 : ATTN_KERNEL_CROSS2;
     const int cus = 8 * mmpl_cus_per_xcd();
     int bph = cus / a.H < 1 ? 1 : cus / a.H;                    // blocks per head (40 heads, 256 CUs: 6)
@@ -523,32 +536,14 @@ AttnPlan mmpl_attn_plan(const AttnArgs& a_in) {
   }
   if (variant == ATTN_LOCKSTEP) {
     p.kernel = ATTN_KERNEL_LOCKSTEP;
-    p.kv_tiles = a.n_pages * ((a.page_rows + KVB - 1) / KVB);
+    p.kv_tiles = a.n_pages * ((a.page_rows + ATTN_KVB - 1) / ATTN_KVB);
     p.main_blocks = n_qb * a.H;
     return p;
   }
   p.kernel = ATTN_KERNEL_W64;
   if (a.history) a.history_mem = reinterpret_cast<short*>(a.history + mmpl_attention_history_state_bytes(a.Lq, a.H));
-  // Tail round: with one block per CU and b = n_qb*H/8 query blocks per XCD (32 CUs), the last b mod 32 blocks of every
-  // XCD would run alone for a whole block time.  They are launched instead as `sp` blocks each over 1/sp of the KV tiles
-  // (fp32 partials in split_ws) followed by a small merge kernel, so the tail round lasts ~1/sp block times.
-  const int per_xcd = mmpl_cus_per_xcd();
-  int tiles = 0;
-  for (int i = 0; i < a.n_pages; ++i) tiles += (a.page_rows_each[i] + KVB - 1) / KVB;
-  p.kv_tiles = tiles;
-  // b = work items per XCD (kernels.h: mmpl_attn_item), tb = those of the partial last round.  Only a tail that fits ONE round of
-  // parts is split (tb * sp <= CUs per XCD): tails of 3 shorter rounds (tb = 17 -> 3 parts, 23-24 -> 4) and launches with fewer
-  // items than CUs measured 0.6-8 % SLOWER than leaving them alone (profiles/r03Q_*).
-  const int total = n_qb * a.H;
-  const int b = (a.H & 7) == 0 ? total / 8 : (total + 7) / 8, tb = b % per_xcd;
-  int sp = 1;
-  if (!mmpl_config().attn_nosplit && a.split_ws && b > per_xcd && tb > 0 && per_xcd / tb >= 2) {
-    sp = per_xcd / tb > 4 ? 4 : per_xcd / tb;
-    if (tiles / sp < 8 || (size_t)8 * tb * sp * QB * 130 * sizeof(float) > a.split_ws_bytes) sp = 1;
-  }
-  p.sp = sp;
-  p.tail_items = sp == 1 ? 0 : tb;
-  p.main_blocks = 8 * (b - p.tail_items);
+  for (int i = 0; i < a.n_pages; ++i) p.kv_tiles += (a.page_rows_each[i] + ATTN_KVB - 1) / ATTN_KVB;
+  plan_tail(p, a.H, n_qb, p.kv_tiles, a.split_ws, a.split_ws_bytes, mmpl_cus_per_xcd());
   return p;
 }
 
@@ -578,15 +573,7 @@ hipError_t mmpl_launch_attention(const AttnArgs& a_in, hipStream_t s) {
     default:
       break;
   }
-  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_symbol(0), mmpl_attention_w64_smem()); e != hipSuccess) return e;
-  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_symbol(1), mmpl_attention_w64_smem()); e != hipSuccess) return e;
-  // main launch: the full rounds, one block per work item; then the tail round's items as sp parts each, and their merge
-  mmpl_launch_attention_w64(a, p.main_blocks, 0, 1, false, s);
-  if (p.sp > 1) {
-    mmpl_launch_attention_w64(a, 8 * p.tail_items * p.sp, p.main_blocks / 8, p.sp, true, s);
-    hipLaunchKernelGGL(attn_merge_kernel, dim3(8 * p.tail_items), dim3(256), 0, s, a, p.main_blocks / 8, p.sp, p.tail_items);
-  }
-  return hipGetLastError();
+  return launch_w64(p, a, attn_merge_kernel, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -623,7 +610,7 @@ AttnGroupPlan mmpl_attn_groups_plan(const AttnArgs& common, int n_groups, const 
     tiles_min = g == 0 || p.kv_tiles < tiles_min ? p.kv_tiles : tiles_min;
     tiles_max = p.kv_tiles > tiles_max ? p.kv_tiles : tiles_max;
   }
-  const int n_qb = (common.Lq + QB - 1) / QB;
+  const int n_qb = (common.Lq + ATTN_QB - 1) / ATTN_QB;
   gp.invalid = 0;
   gp.n_groups = n_groups;
   gp.items = n_groups * common.H * n_qb;
@@ -635,17 +622,7 @@ AttnGroupPlan mmpl_attn_groups_plan(const AttnArgs& common, int n_groups, const 
   AttnPlan& p = gp.p;
   p.n_pages = pages;
   p.kv_tiles = tiles_max;
-  // the tail round, by mmpl_attn_plan's rule on the virtual heads' items (see there)
-  const int per_xcd = mmpl_cus_per_xcd(), hv = n_groups * common.H, total = gp.items;
-  const int b = (hv & 7) == 0 ? total / 8 : (total + 7) / 8, tb = b % per_xcd;
-  int sp = 1;
-  if (!mmpl_config().attn_nosplit && ga.a.split_ws && b > per_xcd && tb > 0 && per_xcd / tb >= 2) {
-    sp = per_xcd / tb > 4 ? 4 : per_xcd / tb;
-    if (tiles_min / sp < 8 || (size_t)8 * tb * sp * QB * 130 * sizeof(float) > ga.a.split_ws_bytes) sp = 1;
-  }
-  p.sp = sp;
-  p.tail_items = sp == 1 ? 0 : tb;
-  p.main_blocks = 8 * (b - p.tail_items);
+  plan_tail(p, n_groups * common.H, n_qb, tiles_min, ga.a.split_ws, ga.a.split_ws_bytes, mmpl_cus_per_xcd());
   return gp;
 }
 
@@ -657,13 +634,5 @@ hipError_t mmpl_launch_attention_groups(const AttnArgs& common, int n_groups, co
       if (hipError_t e = mmpl_launch_attention(gp.single[g], s); e != hipSuccess) return e;
     return hipSuccess;
   }
-  const AttnPlan& p = gp.p;
-  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_groups_symbol(0), mmpl_attention_w64_smem()); e != hipSuccess) return e;
-  if (hipError_t e = mmpl_dyn_smem_once(mmpl_attention_w64_groups_symbol(1), mmpl_attention_w64_smem()); e != hipSuccess) return e;
-  mmpl_launch_attention_w64_groups(gp.ga, p.main_blocks, 0, 1, false, s);
-  if (p.sp > 1) {
-    mmpl_launch_attention_w64_groups(gp.ga, 8 * p.tail_items * p.sp, p.main_blocks / 8, p.sp, true, s);
-    hipLaunchKernelGGL(attn_merge_groups_kernel, dim3(8 * p.tail_items), dim3(256), 0, s, gp.ga, p.main_blocks / 8, p.sp, p.tail_items);
-  }
-  return hipGetLastError();
+  return launch_w64(gp.p, gp.ga, attn_merge_groups_kernel, s);
 }

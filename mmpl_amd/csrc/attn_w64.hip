@@ -50,7 +50,7 @@
 
 namespace {
 
-constexpr int QB = 256, KVB = 64, TILE = KVB * 256, RING = 4;         // K ring [0, 64 KiB), V ring [64 KiB, 128 KiB)
+constexpr int TILE = ATTN_KVB * 256, RING = 4;                        // K ring [0, 64 KiB), V ring [64 KiB, 128 KiB)
 constexpr int W64_SMEM = 2 * RING * TILE + 64;     // + the block's redo flag
 constexpr float BOUND_GEN = 1073741824.f;                              // 2^30: a GENERAL tile's partial row sums
 constexpr float pow2f(int e) { return e == 0 ? 1.f : (e > 0 ? 2.f * pow2f(e - 1) : 0.5f * pow2f(e + 1)); }
@@ -184,11 +184,11 @@ struct Ctx {
   // differ in length: merged runs of cache slots; <= 24 pages, scalar code that runs between runs only)
   MMPL_DEV void locate(int at, int& pg, int& pos, int& tiles_pg) const {
     pg = 0;
-    int start = 0, tp = (rows_each[0] + KVB - 1) / KVB;
+    int start = 0, tp = (rows_each[0] + ATTN_KVB - 1) / ATTN_KVB;
     while (at >= start + tp) {
       start += tp;
       ++pg;
-      tp = (rows_each[pg] + KVB - 1) / KVB;
+      tp = (rows_each[pg] + ATTN_KVB - 1) / ATTN_KVB;
     }
     pos = at - start;
     tiles_pg = tp;
@@ -236,13 +236,13 @@ struct Ctx {
     if (tv < T - 1) { vstep = tile_bytes_v; n = min(n, min(tp - pos, T - tv)); }
     int pg_j, pos_j, tp_j;
     locate(t_first + j, pg_j, pos_j, tp_j);
-    const int valid = rows_each[pg_j] - (tp_j - 1) * KVB;                // rows of this page's last tile
-    if (valid < KVB && pos_j == tp_j - 1) {
+    const int valid = rows_each[pg_j] - (tp_j - 1) * ATTN_KVB;           // rows of this page's last tile
+    if (valid < ATTN_KVB && pos_j == tp_j - 1) {
       set_mask(valid);
       n = 1;
     } else {
       if (masked) clear_mask();
-      n = min(n, (valid < KVB ? tp_j - 1 : tp_j) - pos_j);               // a run ends with tile j's page (before its ragged last tile)
+      n = min(n, (valid < ATTN_KVB ? tp_j - 1 : tp_j) - pos_j);          // a run ends with tile j's page (before its ragged last tile)
     }
     return __builtin_amdgcn_readfirstlane(n);
   }
@@ -457,7 +457,7 @@ MMPL_DEV void w64_block(const AttnArgs& a, int n_groups, const int* page_first, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 5, l31 = lane & 31;
 
-  const int n_qb = (a.Lq + QB - 1) / QB;
+  const int n_qb = (a.Lq + ATTN_QB - 1) / ATTN_QB;
   int head, qb, part = 0, tail_idx = 0;
   {
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
@@ -485,13 +485,13 @@ MMPL_DEV void w64_block(const AttnArgs& a, int n_groups, const int* page_first, 
   // ---- Q fragments -> a[128:191], prescaled: lane (l31, hi) holds Q[row][16c + 8*hi .. +8] * scale * log2(e).  The DiT forward
   // folds that factor into q where q is produced (qknorm_kernel, before the rounding to bf16: q_prescaled); a raw q is scaled
   // here, at the price of a second rounding.
-  const float c = a.scale * 1.4426950408889634f;
+  const float c = a.scale * ATTN_LOG2E;
   const float qmul = a.q_prescaled ? 1.0f : c;
   {
     const bf16_t* qbase = a.q + head * 128 + 8 * hi;
 #pragma unroll
     for (int X = 0; X < 2; ++X) {
-      const int qrow = min(qb * QB + wave * 64 + 32 * X + l31, a.Lq - 1);
+      const int qrow = min(qb * ATTN_QB + wave * 64 + 32 * X + l31, a.Lq - 1);
       const bf16_t* qp = qbase + (row0 + (size_t)qrow) * a.ldq;
       u32x4 qf[8];
 #pragma unroll
@@ -509,7 +509,7 @@ MMPL_DEV void w64_block(const AttnArgs& a, int n_groups, const int* page_first, 
   }
 
   int T_all = 0;
-  for (int p = 0; p < n_pages; ++p) T_all += (a.page_rows_each[p0 + p] + KVB - 1) / KVB;
+  for (int p = 0; p < n_pages; ++p) T_all += (a.page_rows_each[p0 + p] + ATTN_KVB - 1) / ATTN_KVB;
   const int t_first = SPLIT ? (int)((long long)part * T_all / sp) : 0;
   const int T = SPLIT ? (int)((long long)(part + 1) * T_all / sp) - t_first : T_all;     // tiles of THIS block
 
@@ -520,8 +520,8 @@ MMPL_DEV void w64_block(const AttnArgs& a, int n_groups, const int* page_first, 
   k.drow = lane >> 4; k.dchunk = lane & 15;
   k.prow = 16 * wave + k.drow;                        // LDS row of piece 4w; piece 4w + k: + 4 k
   k.t_first = t_first;
-  k.tile_bytes_k = (uint32_t)KVB * a.ldk * 2u;
-  k.tile_bytes_v = (uint32_t)KVB * a.ldv * 2u;
+  k.tile_bytes_k = (uint32_t)ATTN_KVB * a.ldk * 2u;
+  k.tile_bytes_v = (uint32_t)ATTN_KVB * a.ldv * 2u;
   k.wave_slot = wave * 4096;
   // the bank swizzle is keyed on the LDS row: K chunk ^= row & 15, V chunk ^= (row & 3) << 2
 #pragma unroll
@@ -622,22 +622,21 @@ MMPL_DEV void w64_block(const AttnArgs& a, int n_groups, const int* page_first, 
     else sfor<64>([&o](auto ii) { constexpr int i = decltype(ii)::value; asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(o[i]) : "i"(AO + 64 + i)); });
     const int rr = wave * 64 + 32 * X + l31;
     if (SPLIT) {
-      // partial of this KV range: O (fp32, relative to m_ref), then m (raw score units, as attn_merge_kernel expects), l per
-      // row -- [tail block][part][256 rows][128 + 2]
-      float* pbase = a.split_ws + ((size_t)tail_idx * sp + part) * (QB * 130);
-      float* op = pbase + (size_t)rr * 128 + 4 * hi;
+      // partial of this KV range (kernels.h: AttnPartial): O (fp32, relative to m_ref), m (raw score units), l per row
+      float* pbase = a.split_ws + ((size_t)tail_idx * sp + part) * AttnPartial::FLOATS;
+      float* op = pbase + AttnPartial::o(rr) + 4 * hi;
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
           *reinterpret_cast<f32x4*>(op + 32 * nb + 8 * g) = f32x4{o[16 * nb + 4 * g], o[16 * nb + 4 * g + 1], o[16 * nb + 4 * g + 2], o[16 * nb + 4 * g + 3]};
       if (hi == 0) {
-        pbase[QB * 128 + rr] = k.mref[X] / c;
-        pbase[QB * 129 + rr] = l_tot;
+        pbase[AttnPartial::m(rr)] = k.mref[X] / c;
+        pbase[AttnPartial::l(rr)] = l_tot;
       }
     } else {
       const float inv = 1.0f / l_tot;
-      const int q_out = qb * QB + rr;
+      const int q_out = qb * ATTN_QB + rr;
       if (q_out < a.Lq) {
         bf16_t* op = a.o + (row0 + (size_t)q_out) * a.ldo + head * 128 + 4 * hi;
 #pragma unroll
@@ -668,11 +667,5 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 #ifndef MMPL_ATTN_W64_GROUPS_TU
 int mmpl_attention_w64_smem() { return W64_SMEM; }
-const void* mmpl_attention_w64_symbol(int split) {
-  return split ? reinterpret_cast<const void*>(attn_w64_kernel<true>) : reinterpret_cast<const void*>(attn_w64_kernel<false>);
-}
-void mmpl_launch_attention_w64(const AttnArgs& a, int blocks, int local_base, int sp, bool split, hipStream_t s) {
-  if (split) hipLaunchKernelGGL(attn_w64_kernel<true>, dim3(blocks), dim3(256), W64_SMEM, s, a, local_base, sp);
-  else hipLaunchKernelGGL(attn_w64_kernel<false>, dim3(blocks), dim3(256), W64_SMEM, s, a, local_base, sp);
-}
+template <> AttnW64Kernels<AttnArgs> mmpl_attention_w64_kernels<AttnArgs>() { return {attn_w64_kernel<true>, attn_w64_kernel<false>}; }
 #endif

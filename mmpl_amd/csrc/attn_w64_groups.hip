@@ -5,10 +5,6 @@
 #define MMPL_ATTN_W64_GROUPS_TU 1
 #include "attn_w64.hip"
 
-const void* mmpl_attention_w64_groups_symbol(int split) {
-  return split ? reinterpret_cast<const void*>(attn_w64_groups_kernel<true>) : reinterpret_cast<const void*>(attn_w64_groups_kernel<false>);
-}
-void mmpl_launch_attention_w64_groups(const AttnGroupArgs& ga, int blocks, int local_base, int sp, bool split, hipStream_t s) {
-  if (split) hipLaunchKernelGGL(attn_w64_groups_kernel<true>, dim3(blocks), dim3(256), W64_SMEM, s, ga, local_base, sp);
-  else hipLaunchKernelGGL(attn_w64_groups_kernel<false>, dim3(blocks), dim3(256), W64_SMEM, s, ga, local_base, sp);
+template <> AttnW64Kernels<AttnGroupArgs> mmpl_attention_w64_kernels<AttnGroupArgs>() {
+  return {attn_w64_groups_kernel<true>, attn_w64_groups_kernel<false>};
 }

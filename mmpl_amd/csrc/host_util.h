@@ -1,5 +1,5 @@
 // Host-side scaffolding shared by every engine's orchestration (api.hip, t5.hip, vae.hip, taehv*.hip, i2v.hip): workspace carving,
-// weight binding, first-error capture and the two launcher argument structs that are filled in many places.  Host only, header only.
+// weight binding, first-error capture and the three launcher argument structs that are filled in many places.  Host only, header only.
 #pragma once
 #include <stddef.h>
 
@@ -57,5 +57,13 @@ inline LnArgs ln_args(const bf16_t* x, int ldx, bf16_t* y, int ldy, int rows, in
   LnArgs a = {};
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.rows = rows; a.d = d; a.eps = eps;
   a.rows_per_frame = 1;
+  return a;
+}
+
+// o = softmax(scale . q k^T) v over H heads of 128, Lq query rows, pages of page_rows rows; everything else zero.  The caller names
+// its pages (n_pages, k_pages, v_pages, page_group) and whatever else the launch uses.
+inline AttnArgs attn_args(const bf16_t* q, int ldq, bf16_t* o, int ldo, int ldk, int ldv, int page_rows, int Lq, int H, float scale) {
+  AttnArgs a = {};
+  a.q = q; a.ldq = ldq; a.o = o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv; a.page_rows = page_rows; a.Lq = Lq; a.H = H; a.scale = scale;
   return a;
 }

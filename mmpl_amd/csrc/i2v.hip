@@ -40,10 +40,8 @@ hipError_t layernorm(const bf16_t* x, bf16_t* y, int rows, int d, float eps, con
   return mmpl_launch_layernorm(a, s);
 }
 hipError_t attend(const bf16_t* q, bf16_t* o, const bf16_t* k, const bf16_t* v, int n_kv, int Lq, int dim, hipStream_t s) {
-  AttnArgs a = {};
-  a.q = q; a.ldq = dim; a.o = o; a.ldo = dim;
-  a.k_pages[0] = k; a.v_pages[0] = v; a.ldk = dim; a.ldv = dim;
-  a.n_pages = 1; a.page_rows = n_kv; a.Lq = Lq; a.H = dim / 128; a.scale = 1.0f / sqrtf(128.0f); a.cross = 1;
+  AttnArgs a = attn_args(q, dim, o, dim, dim, dim, n_kv, Lq, dim / 128, 1.0f / sqrtf(128.0f));
+  a.n_pages = 1; a.k_pages[0] = k; a.v_pages[0] = v; a.cross = 1;
   return mmpl_launch_attention(a, s);
 }
 int blocks_for(size_t n) { return (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256); }
@@ -169,10 +167,8 @@ int mmpl_clip_visual(const void* patches, int n_patch, int pk, int dim, int mlp_
     MMPL_HIP_TRY(layernorm(x, hbuf, n, dim, eps, W[0], W[1], s), "mmpl_clip_visual: norm1");
     MMPL_HIP_TRY(linear(hbuf, dim, W[2], W[3], big, n, 3 * hw, s), "mmpl_clip_visual: to_qkv");
     {
-      AttnArgs a = {};
-      a.q = big; a.ldq = 3 * hw; a.o = att; a.ldo = hw;
-      a.k_pages[0] = big + hw; a.v_pages[0] = big + 2 * hw; a.ldk = 3 * hw; a.ldv = 3 * hw;
-      a.n_pages = 1; a.page_rows = n; a.Lq = n; a.H = heads; a.scale = 1.0f / sqrtf((float)head_dim); a.cross = 1;
+      AttnArgs a = attn_args(big, 3 * hw, att, hw, 3 * hw, 3 * hw, n, n, heads, 1.0f / sqrtf((float)head_dim));
+      a.n_pages = 1; a.k_pages[0] = big + hw; a.v_pages[0] = big + 2 * hw; a.cross = 1;
       MMPL_HIP_TRY(mmpl_launch_attention(a, s), "mmpl_clip_visual: attention");
     }
     MMPL_HIP_TRY(linear_res(att, hw, W[4], W[5], x, n, dim, s), "mmpl_clip_visual: proj + residual");

@@ -275,20 +275,11 @@ int mmpl_gemm_ex(const void* A, int lda, const void* W, int ldw, const void* bia
   LAUNCH(mmpl_launch_gemm(g, (hipStream_t)stream), me);
 }
 
-// One launch of mmpl_launch_attention with everything AttnArgs carries (include/mmpl_hip.h).  The plan is the launcher's own
-// (mmpl_attn_plan, which mmpl_launch_attention consults for every choice); it is computed after the checks, because the plan of
-// the cross and the w64 kernel asks the device for its CU count.
-int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
-                     const unsigned char* page_group, int ldk, int ldv, int n_pages, int page_rows, int Lq, int num_heads,
-                     float softmax_scale, void* workspace, size_t workspace_bytes, int variant, int q_prescaled, int cross,
-                     int last_row_copies, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream) {
-  const char* me = "mmpl_attn_fwd_ex";
-  if (plan_out)
-    for (int i = 0; i < 8; ++i) plan_out[i] = 0;
-  REJECT(!q || !o || !k_pages || !v_pages, me, "null argument");
-  REJECT(n_pages < 1, me, "n_pages < 1");
-  REJECT(n_pages > MMPL_MAX_PAGES, me, "more than 24 pages");
-  REJECT(page_rows < 1 || Lq < 1 || num_heads < 1, me, "non-positive size");
+// What mmpl_attn_fwd_ex and mmpl_attn_fwd_groups_ex check on the arguments they share, in the order both report it, and the AttnArgs
+// those arguments fill (Lq: the rows of one launch or of one group; last_row_copies: 0 for a grouped launch).
+static int attn_entry_common(const char* me, const void* q, int ldq, void* o, int ldo, int ldk, int ldv, int page_rows, int Lq, int num_heads,
+                             float softmax_scale, void* workspace, size_t workspace_bytes, int variant, int q_prescaled, int last_row_copies,
+                             void* history, void* stats_dev, AttnArgs& a) {
   REJECT(!(softmax_scale > 0.f) || softmax_scale > 3.0e38f, me, "softmax_scale must be positive and finite");
   REJECT(variant != ATTN_AUTO && variant != ATTN_LOCKSTEP && variant != ATTN_W64 && variant != ATTN_W64 + 1, me, "unknown kernel variant");
   REJECT(ldq % 8, me, "ldq % 8");
@@ -305,22 +296,42 @@ int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const
   REJECT(misaligned(workspace, 16), me, "workspace not 16-byte aligned");
   REJECT(misaligned(history, 2), me, "history not 2-byte aligned");
   REJECT(misaligned(stats_dev, 8), me, "stats not 8-byte aligned");
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv; a.n_pages = n_pages;
-  a.page_rows = page_rows; a.Lq = Lq; a.H = num_heads; a.scale = softmax_scale;
+  a = attn_args((const bf16_t*)q, ldq, (bf16_t*)o, ldo, ldk, ldv, page_rows, Lq, num_heads, softmax_scale);
   a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
+  a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
+  a.q_prescaled = variant == ATTN_W64 + 1 || q_prescaled != 0;
+  a.last_row_copies = last_row_copies;
+  a.history = (unsigned char*)history;
+  a.redo_stats = (unsigned long long*)stats_dev;
+  return 0;
+}
+
+// One launch of mmpl_launch_attention with everything AttnArgs carries (include/mmpl_hip.h).  The plan is the launcher's own
+// (mmpl_attn_plan, which mmpl_launch_attention consults for every choice); it is computed after the checks, because the plan of
+// the cross and the w64 kernel asks the device for its CU count.
+int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
+                     const unsigned char* page_group, int ldk, int ldv, int n_pages, int page_rows, int Lq, int num_heads,
+                     float softmax_scale, void* workspace, size_t workspace_bytes, int variant, int q_prescaled, int cross,
+                     int last_row_copies, void* history, void* stats_dev, int* plan_out, mmpl_stream_t stream) {
+  const char* me = "mmpl_attn_fwd_ex";
+  if (plan_out)
+    for (int i = 0; i < 8; ++i) plan_out[i] = 0;
+  REJECT(!q || !o || !k_pages || !v_pages, me, "null argument");
+  REJECT(n_pages < 1, me, "n_pages < 1");
+  REJECT(n_pages > MMPL_MAX_PAGES, me, "more than 24 pages");
+  REJECT(page_rows < 1 || Lq < 1 || num_heads < 1, me, "non-positive size");
+  AttnArgs a;
+  if (int e = attn_entry_common(me, q, ldq, o, ldo, ldk, ldv, page_rows, Lq, num_heads, softmax_scale, workspace, workspace_bytes, variant,
+                                q_prescaled, last_row_copies, history, stats_dev, a))
+    return e;
+  a.n_pages = n_pages;
   for (int i = 0; i < n_pages; ++i) {
     REJECT(!k_pages[i] || !v_pages[i], me, "null page");
     REJECT(misaligned(k_pages[i], 16) || misaligned(v_pages[i], 16), me, "page not 16-byte aligned");
     a.k_pages[i] = (const bf16_t*)k_pages[i]; a.v_pages[i] = (const bf16_t*)v_pages[i];
     a.page_group[i] = page_group ? page_group[i] : 0;
   }
-  a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
-  a.q_prescaled = variant == ATTN_W64 + 1 || q_prescaled != 0;
   a.cross = cross != 0;
-  a.last_row_copies = last_row_copies;
-  a.history = (unsigned char*)history;
-  a.redo_stats = (unsigned long long*)stats_dev;
   const int resolved = mmpl_attn_resolve_variant(a);          // (no HIP call: the arguments and the run-time switches)
   REJECT(a.q_prescaled && resolved != ATTN_W64, me, "a prescaled q runs on the 64-rows-per-wave kernel only");
   REJECT(last_row_copies > 1 && resolved != ATTN_LOCKSTEP, me, "last_row_copies > 1 runs on the lock-step kernel only");
@@ -334,7 +345,7 @@ int mmpl_attn_fwd_ex(const void* q, int ldq, void* o, int ldo, const void* const
   LAUNCH(mmpl_launch_attention(a, (hipStream_t)stream), me);
 }
 
-// mmpl_launch_attention_groups on plain arguments: the checks of mmpl_attn_fwd_ex, once for the common arguments and once per page.
+// mmpl_launch_attention_groups on plain arguments: mmpl_attn_fwd_ex's checks of the common arguments and of every page.
 int mmpl_attn_fwd_groups_ex(const void* q, int ldq, void* o, int ldo, const void* const* k_pages, const void* const* v_pages,
                             const unsigned char* page_group, const int* group_n_pages, int n_groups, int group_rows, int ldk, int ldv,
                             int page_rows, int num_heads, float softmax_scale, void* workspace, size_t workspace_bytes, int variant,
@@ -346,29 +357,10 @@ int mmpl_attn_fwd_groups_ex(const void* q, int ldq, void* o, int ldo, const void
   REJECT(n_groups < 1, me, "n_groups < 1");
   REJECT(n_groups > MMPL_MAX_GROUPS, me, "more than 8 groups");
   REJECT(page_rows < 1 || group_rows < 1 || num_heads < 1, me, "non-positive size");
-  REJECT(!(softmax_scale > 0.f) || softmax_scale > 3.0e38f, me, "softmax_scale must be positive and finite");
-  REJECT(variant != ATTN_AUTO && variant != ATTN_LOCKSTEP && variant != ATTN_W64 && variant != ATTN_W64 + 1, me, "unknown kernel variant");
-  REJECT(ldq % 8, me, "ldq % 8");
-  REJECT(ldo % 8, me, "ldo % 8");
-  REJECT(ldk % 8, me, "ldk % 8");
-  REJECT(ldv % 8, me, "ldv % 8");
-  REJECT(ldq < 128 * num_heads, me, "ldq < 128 * num_heads");
-  REJECT(ldo < 128 * num_heads, me, "ldo < 128 * num_heads");
-  REJECT(ldk < 128 * num_heads, me, "ldk < 128 * num_heads");
-  REJECT(ldv < 128 * num_heads, me, "ldv < 128 * num_heads");
-  REJECT(misaligned(q, 16), me, "q not 16-byte aligned");
-  REJECT(misaligned(o, 16), me, "o not 16-byte aligned");
-  REJECT(misaligned(workspace, 16), me, "workspace not 16-byte aligned");
-  REJECT(misaligned(history, 2), me, "history not 2-byte aligned");
-  REJECT(misaligned(stats_dev, 8), me, "stats not 8-byte aligned");
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.ldq = ldq; a.o = (bf16_t*)o; a.ldo = ldo; a.ldk = ldk; a.ldv = ldv;
-  a.page_rows = page_rows; a.Lq = group_rows; a.H = num_heads; a.scale = softmax_scale;
-  a.split_ws = (float*)workspace; a.split_ws_bytes = workspace ? workspace_bytes : 0;
-  a.variant = variant > ATTN_W64 ? ATTN_W64 : variant;
-  a.q_prescaled = variant == ATTN_W64 + 1 || q_prescaled != 0;
-  a.history = (unsigned char*)history;
-  a.redo_stats = (unsigned long long*)stats_dev;
+  AttnArgs a;
+  if (int e = attn_entry_common(me, q, ldq, o, ldo, ldk, ldv, page_rows, group_rows, num_heads, softmax_scale, workspace, workspace_bytes,
+                                variant, q_prescaled, 0, history, stats_dev, a))
+    return e;
   REJECT(a.q_prescaled && mmpl_attn_resolve_variant(a) != ATTN_W64, me, "a prescaled q runs on the 64-rows-per-wave kernel only");
   AttnGroupPages lists[MMPL_MAX_GROUPS] = {};
   for (int g = 0, at = 0; g < n_groups; ++g) {

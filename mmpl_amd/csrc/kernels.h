@@ -67,6 +67,8 @@ hipError_t mmpl_launch_gemm(const GemmArgs& g, hipStream_t s);
 
 // ---------------------------------------------------------------- attention (attention.hip)
 constexpr int MMPL_MAX_PAGES = 24;
+constexpr int ATTN_QB = 256, ATTN_KVB = 64;            // query rows per block (work item), rows per KV tile: every attention kernel
+constexpr float ATTN_LOG2E = 1.4426950408889634f;      // the kernels compute p = exp2((s - m) * scale * log2(e))
 struct AttnArgs {
   const bf16_t* q; int ldq;       // row r, head h at q + r*ldq + h*128
   bf16_t* o; int ldo;
@@ -128,20 +130,28 @@ struct AttnGroupArgs {
   int n_groups;
   int page_first[MMPL_MAX_GROUPS + 1];
 };
+// The split-KV partial of one (tail query block, KV part): what a split block of attn_w64_kernel writes and attn_merge_kernel reads.
+// FLOATS fp32: O of query row r (relative to the part's reference m) at o(r) .. + 128, then m (raw score units) and l of the 256
+// rows at m(r) and l(r).  split_ws holds them as [tail block][part].
+struct AttnPartial {
+  static constexpr int FLOATS = ATTN_QB * (128 + 2);
+  static constexpr size_t BYTES = FLOATS * sizeof(float);
+  static constexpr size_t o(int r) { return (size_t)r * 128; }
+  static constexpr int m(int r) { return ATTN_QB * 128 + r; }
+  static constexpr int l(int r) { return ATTN_QB * 129 + r; }
+};
 enum { ATTN_AUTO = 0, ATTN_LOCKSTEP = 1, ATTN_W64 = 3 };      // (2 was the round-1 ping-pong kernel, removed)
 // The kernel ATTN_AUTO resolves to for a self-attention launch whose producer can fold the softmax scale into q before q is
 // rounded to bf16 (the DiT forward: qknorm_kernel's q_scale).  ATTN_W64 computes exp2(K.q) without a per-score multiply, so it
 // wants q = bf16(q_fp32 * scale * log2(e)); handing it a bf16 q to prescale itself costs a second rounding of q, which shows
 // on sharp softmax rows (large QK-norm gains) -- a raw-q ATTN_AUTO launch (the attention() seam) therefore takes ATTN_LOCKSTEP.
 int mmpl_attention_self_variant();
-// attn_w64.hip (4 waves x 64 query rows, one wave per SIMD)
+// attn_w64.hip (4 waves x 64 query rows, one wave per SIMD): the kernel pair {whole KV range, one split-KV part} that takes Args
+// (+ local_base, sp).  AttnArgs: attn_w64.hip; AttnGroupArgs: attn_w64_groups.hip, the grouped instantiations of the same body.
 int mmpl_attention_w64_smem();
-const void* mmpl_attention_w64_symbol(int split);
-void mmpl_launch_attention_w64(const AttnArgs& a, int blocks, int local_base, int sp, bool split, hipStream_t s);
-// attn_w64_groups.hip: the grouped instantiations of the same kernel body (same shared memory)
-const void* mmpl_attention_w64_groups_symbol(int split);
-void mmpl_launch_attention_w64_groups(const AttnGroupArgs& ga, int blocks, int local_base, int sp, bool split, hipStream_t s);
-size_t mmpl_attention_split_ws_bytes();     // upper bound of what a launch can use
+template <class Args> struct AttnW64Kernels { void (*split)(Args, int, int); void (*main)(Args, int, int); };
+template <class Args> AttnW64Kernels<Args> mmpl_attention_w64_kernels();
+inline size_t mmpl_attention_split_ws_bytes() { return 256 * AttnPartial::BYTES; }   // <= one block per CU in the tail round
 // What mmpl_launch_attention does with an AttnArgs: every choice of the launcher is made by mmpl_attn_plan and nowhere else (the
 // launcher reads it from the plan; mmpl_attn_fwd_ex reports it to the tests).  Host arithmetic on the arguments and the run-time
 // switches (mmpl_config.h); the CU count of the current device is looked up only for a valid launch of the cross or the w64 kernel.
@@ -164,8 +174,9 @@ struct AttnPlan {
 // The ATTN_* kernel an AttnArgs resolves to (ATTN_AUTO: the text cross-attention and every raw q -> ATTN_LOCKSTEP).
 int mmpl_attn_resolve_variant(const AttnArgs& a);
 AttnPlan mmpl_attn_plan(const AttnArgs& a);
-inline size_t mmpl_attention_history_state_bytes(int Lq, int H) { return ((size_t)H * ((Lq + 255) / 256) * 4 + 255) & ~(size_t)255; }
-inline size_t mmpl_attention_history_bytes(int Lq, int H) { return mmpl_attention_history_state_bytes(Lq, H) + (size_t)H * ((Lq + 255) / 256) * 4 * 128 * sizeof(short); }
+inline size_t mmpl_attention_history_states(int Lq, int H) { return (size_t)H * ((Lq + ATTN_QB - 1) / ATTN_QB) * 4; }
+inline size_t mmpl_attention_history_state_bytes(int Lq, int H) { return (mmpl_attention_history_states(Lq, H) + 255) & ~(size_t)255; }
+inline size_t mmpl_attention_history_bytes(int Lq, int H) { return mmpl_attention_history_state_bytes(Lq, H) + mmpl_attention_history_states(Lq, H) * 128 * sizeof(short); }
 hipError_t mmpl_launch_attention(const AttnArgs& a, hipStream_t s);
 // n_groups attentions of equal shape (AttnGroupArgs above), as the caller states them: `common` is the AttnArgs of ONE group (q / o:
 // group 0's first row; Lq = rows of a group; its own page fields are ignored), lists[g] the pages of group g.  common.history, when
@@ -178,8 +189,8 @@ struct AttnGroupPages {
 // Every choice of mmpl_launch_attention_groups is made here.  Each group's list is planned by itself first (mmpl_attn_plan: checks,
 // order, merge).  ONE grouped launch needs every group on attn_w64_kernel (so not MMPL_ATTN_V1), no history and at most MMPL_MAX_PAGES
 // merged pages in all; anything else runs as one mmpl_launch_attention per group (grouped == 0), which computes the same.  The grouped
-// launch's split-KV tail follows mmpl_attn_plan's rule on the TOTAL item count n_groups * H * ceil(Lq / 256) (and on the shortest
-// group's KV tiles, where the rule asks for 8 tiles per part).
+// launch's split-KV tail is the one tail rule (attention.hip: plan_tail) on the n_groups * H virtual heads and on the shortest group's
+// KV tiles.
 struct AttnGroupPlan {
   int invalid;            // the launcher answers hipErrorInvalidValue and launches nothing
   int grouped;            // 1: one grouped launch of `ga` by `p`; 0: n_groups launches of single[g]
